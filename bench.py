@@ -21,9 +21,14 @@ reduction of src/ndaccum.c:198-254 after the site loop of src/arbplfll.c:139-170
   --scaling weak              every rank holds --sites patterns (its block of an
       N x --sites alignment).
 
-After the ll region a short edge-gradient leg (arbplf-deriv: down + up pass,
-site-summed, 2E doubles all-reduced for N > 1) is timed and reported under
-"deriv"; it is not part of `value`.
+A plain run sets up, warms up, times the ll steps and prints the result line.
+--dump-outputs DIR writes what the last timed step computed (the log-likelihood
+sum, ll_sum.npy) for output-for-output comparison of two builds.  --full adds
+the legs that are not the headline figure: a short edge-gradient leg
+(arbplf-deriv: down + up pass, site-summed, 2E doubles all-reduced for N > 1)
+reported under "deriv", the CPU baseline (--no-cpu-baseline skips it) and the
+per-site cross-check of the GPU ll against the CPU checker ("check"); none of
+them is part of `value`.
 
 Launch: `python bench.py` (1 GPU) or
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`.
@@ -176,11 +181,15 @@ def main():
     ap.add_argument("--engine-option", action="append", default=[], metavar="ID=VALUE",
                     help="plk_set_option(ID, VALUE) before the run (kernel experiments; include/plk.h lists the options)")
     ap.add_argument("--categories", type=int, default=0, help="override the number of Gamma categories (experiments; not the metric's workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the edge-gradient leg, the CPU baseline and the cross-check against the CPU checker")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the log-likelihood sum of the last timed step to DIR/ll_sum.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the check")
     ap.add_argument("--dist", action="store_true", help="initialise torch.distributed (nccl) and all-reduce also when launched as one process")
     ap.add_argument("--torch-allreduce", action="store_true", help="N > 1: torch.distributed.all_reduce instead of the engine's own RCCL call")
     ap.add_argument("--sync-allreduce", action="store_true", help="N > 1: block the compute stream on every all-reduce (no overlap with the next step)")
-    ap.add_argument("--deriv-steps", type=int, default=3, help="steps of the edge-gradient leg (0 = skip)")
+    ap.add_argument("--deriv-steps", type=int, default=3, help="steps of the edge-gradient leg of --full (0 = skip)")
     ap.add_argument("--deriv-sites", type=int, default=0, help="sites per GPU of the edge-gradient leg (default: min(block, 2M))")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     args = ap.parse_args()
@@ -349,11 +358,15 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the {hi, lo} sum, written as the one double it stands for
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ll_sum.npy"), np.array([total], dtype=np.float64))
 
     # per-site values of the first sites of rank 0's block, for the cross-check against the CPU checker below
     ncheck = min(S, 4096)
     gpu_ll_head = None
-    if rank == 0:
+    if rank == 0 and args.full:
         site_ll = torch.empty(S, dtype=torch.float64, device=dev)
         eng.ll(out_device_ptr=site_ll.data_ptr(), want_sum=False)
         gpu_ll_head = site_ll[:ncheck].cpu().numpy()
@@ -361,7 +374,7 @@ def main():
 
     # edge-gradient leg: arbplf-deriv on the head of this rank's block (site-summed gradient, reduced across ranks)
     deriv_out = None
-    if args.deriv_steps > 0:
+    if args.full and args.deriv_steps > 0:
         Sd = min(S, args.deriv_sites or 2_000_000)
         if Sd != S:
             cd = torch.empty((wl.N, Sd), dtype=torch.uint8, device=dev)
@@ -474,7 +487,7 @@ def main():
         }
         if deriv_out is not None:
             out["deriv"] = deriv_out
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             if world == 1:
                 cb, cpu_ll = cpu_baseline(wl, min(2 * S, 20_000_000), args.cpu_seconds)
                 out["cpu_baseline"] = cb

@@ -14,7 +14,7 @@ root="$(pwd)"
 out="$root/gpurun_out/prof"
 mkdir -p "$out"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
-cmd=(python3 "$root/bench.py" --config "$cfg" --steps "$steps" --warmup 2 --no-cpu-baseline)
+cmd=(python3 "$root/bench.py" --full --config "$cfg" --steps "$steps" --warmup 2 --no-cpu-baseline)
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_cfg${cfg}_stats" -o run -- "${cmd[@]}" > "$out/${tag}_cfg${cfg}_stats.log" 2>&1 &&
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --kernel-include-regex '^(void )?k_' --output-format csv -d "$out/${tag}_cfg${cfg}_fetch" -o run -- "${cmd[@]}" > "$out/${tag}_cfg${cfg}_fetch.log" 2>&1 &&

@@ -6,7 +6,7 @@ tag="$1"; cfg="$2"; shift 2
 root="$(pwd)"; out="$root/gpurun_out/prof"; mkdir -p "$out"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
 cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_cfg${cfg}_stats" -o run -- python3 "$root/bench.py" --config "$cfg" --steps 5 --warmup 2 --no-cpu-baseline "$@" > "$out/${tag}_cfg${cfg}_stats.log" 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_cfg${cfg}_stats" -o run -- python3 "$root/bench.py" --full --config "$cfg" --steps 5 --warmup 2 --no-cpu-baseline "$@" > "$out/${tag}_cfg${cfg}_stats.log" 2>&1
 rc=$?
 cd "$root"
 find "$out" -name '*kernel_trace.csv' -delete 2>/dev/null

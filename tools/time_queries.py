@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Whole-step wall time of plk_deriv and plk_marginal (site-summed outputs, patterns resident) on a BASELINE config:
   python tools/time_queries.py --config 4 --sites 1000000
-prints one JSON line.  bench.py times ll and deriv; this adds the marginal query (and, with --hess-sites, the Hessian) for
+prints one JSON line.  bench.py --full times ll and deriv; this adds the marginal query (and, with --hess-sites, the Hessian) for
 DESIGN.md's table."""
 import argparse
 import json
