@@ -225,9 +225,11 @@ enum {
     PLK_INFO_LL_VARIANT = 7,        /* k = 4 tile kernel of the last evaluation: 1 assembly interpreter, 3 C++ interpreter,
                                        5 assembly interpreter with pair tables, 6 the same with two sites per lane, 0 another kernel */
     PLK_INFO_PAIR_TABLES = 8,       /* two-leaf subtrees the last k = 4 evaluation read from tables */
-    PLK_INFO_LL_EXEC_FLOPS = 9      /* fp64 flops per site the last ll traversal kernel executed (all categories): 2k^2 - k per
+    PLK_INFO_LL_EXEC_FLOPS = 9,     /* fp64 flops per site the last ll traversal kernel executed (all categories): 2k^2 - k per
                                        matrix-vector product it ran (k padded to 16 rows on the matrix cores), k per elementwise
                                        multiply (leaf rows, stack pops); table look-ups, moves and rescaling count nothing */
+    PLK_INFO_UPDOWN_KERNEL = 10     /* down / up kernels of the last deriv, marginal or expectation query: 0 = none yet,
+                                       1 = k = 4 kernels, 2 = generic, 3 = fp64 MFMA, 4 = register-resident vector (9 <= k <= 20) */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused

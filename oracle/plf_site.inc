@@ -266,7 +266,11 @@ static void SUF(site_edge_expect)(const orc_problem *p, void *wsv, long s,
     for (int c = 0; c < p->C; c++) {
         REAL cat_lhood = (REAL)p->cat_prior[c] * SUF(site_lhood)(p, w, c, 1, NULL);
         site_lhood += cat_lhood;
-        if (cat_lhood == 0) continue;
+        /* every category counts, also one whose likelihood is 0 at this site (the rate-0 category under data that
+         * changes along the tree): the category loops of src/arbplfdwell.c:228-278 and src/arbplftrans.c skip none,
+         * and fe^T F L_b need not vanish there for a direction L with off-diagonal entries (include/plk.h,
+         * plk_edge_expect).  The JSON drivers cannot tell the difference: for their directions (diagonal, or weights
+         * o Qn) F_{c,e} is 0 wherever P_{c,e} is, so their terms vanish with the category likelihood */
         SUF(site_forward)(p, w, c);
         for (int idx = 0; idx < E; idx++) {
             if (edge_requested && !edge_requested[idx]) continue;

@@ -5,7 +5,7 @@ Tolerance: per-site |ll_gpu - ll_oracle| <= 1e-12 * max(1, |ll_oracle|)
 import numpy as np
 import pytest
 
-from helpers import oracle_site_ll, oracle_model, rel_err
+from helpers import custom_workload, oracle_site_ll, oracle_model, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -162,17 +162,10 @@ def test_vector_kernel_pair_tables_equal_the_plain_program(oracle, T, k, S):
     PLK_OPT_PAIR_TABLES on, the default) against the same kernel on the plain program and against the oracle, with
     missing data and ambiguity at the leaves."""
     from phyly_amd import engine as E, synth
-    model = "aa20" if k == 20 else None
-    wl = synth.Workload(T=T, k=k, tree="yule", model=model, seed=31) if model else None
-    if wl is None:
-        wl = synth.Workload(T=T, k=20, tree="yule", model="aa20", seed=32)
-        # a 12-state model: the top-left block of the 20-state one
-        wl.k = k
-        wl.Q = [row[:k] for row in wl.Q[:k]]
-        wl.defs = np.vstack([np.eye(k), np.ones((1, k))])
-        wl.nchar = k + 1
-        wl.k0 = None
-        wl._cum = None
+    if k == 20:
+        wl = synth.Workload(T=T, k=k, tree="yule", model="aa20", seed=31)
+    else:
+        wl = custom_workload(k, T, C=1, root="equilibrium", seed=32)        # a non-reversible 12-state model
     eng = E.Engine(0)
     wl.setup_engine(eng)
     codes = wl.random_codes(S, seed=5, missing_frac=0.1)
