@@ -41,11 +41,17 @@ char *arbplf_em_update_string(void *userdata, const char *s_in, int *retcode);
 /* the Hessian of the log likelihood (hess_query behind arbplf_second_order_run,
  * src/arbplfhess.c:1279-1343, :1736-1771), fp64 and uncertified */
 char *arbplf_hess_string(void *userdata, const char *s_in, int *retcode);
+/* what the Hessian is for (inv_hess_query, newton_delta_query, newton_point_query of src/arbplfhess.c:1238-1267,
+ * :1372-1388, :1427-1443): its inverse, the Newton step -H^-1 g, and edge_rate_coefficients + that step.  A Hessian
+ * that is singular to working precision is refused (plk_solve_second_order in plk.h). */
+char *arbplf_inv_hess_string(void *userdata, const char *s_in, int *retcode);
+char *arbplf_newton_delta_string(void *userdata, const char *s_in, int *retcode);
+char *arbplf_newton_update_string(void *userdata, const char *s_in, int *retcode);
 
 /* Host-only validation of an input document (JSON grammar, model_and_data,
  * reductions) exactly as the corresponding query would perform it, without
- * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess".
- * 0 = accepted. */
+ * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
+ * "inv_hess" | "newton_delta" | "newton_update".  0 = accepted. */
 int arbplf_validate_string(const char *what, const char *s_in);
 
 /* stdin -> stdout filter used by the CLI mains (run_string_script,

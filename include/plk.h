@@ -194,6 +194,27 @@ int plk_fit_edge_rates(plk_engine *h, int method, int max_iter, double ftol, con
 int plk_hess(plk_engine *h, double *hess_sums_out);
 
 /*
+ * Gradient and Hessian of sum_s w_s ll_s from ONE run: pass 0 of the Hessian produces g / f per site anyway, so a
+ * Newton step (src/arbplfhess.c:169-234) does not pay a separate plk_deriv.  grad_sums_out: NULL or [E][2], hess_sums_out:
+ * NULL or [E][E][2] (not both NULL), double-double entries in CSR edge order.  plk_hess(h, out) is
+ * plk_second_order(h, NULL, out).  k = 4 with compact codes and at most 4 rate categories runs the one-thread-per-site
+ * second-order pass (plk_hess4.h: four edge-modified models per launch, two or one for the last rows), everything else the generic passes.
+ */
+int plk_second_order(plk_engine *h, double *grad_sums_out, double *hess_sums_out);
+
+/*
+ * The solve behind arbplf-inv-hess / -newton-delta / -newton-update; host only, no engine and no GPU involved.
+ * hess: [E][E][2] and grad: [E][2] (NULL unless delta_out is asked for) as (hi, lo) pairs, any consistent edge order.
+ * inv_out: NULL or [E][E] = H^-1, symmetrised; delta_out: NULL or [E] = -H^-1 g; cond_out: NULL or the infinity-norm
+ * condition number ||H|| ||H^-1|| from the computed inverse.  Gauss-Jordan elimination with partial pivoting on [H | I] in
+ * IEEE binary128, rounded once.
+ * Returns PLK_E_ARG -- nothing but *cond_out written -- for a zero pivot and when cond * E * 1e-11 >= 1: the Hessian is
+ * good to 1e-11 of its largest entry, so no digit of such a solve means anything (the reference's precision loop does
+ * not terminate on a singular Hessian, src/arbplfhess.c:1225-1236).
+ */
+int plk_solve_second_order(int E, const double *hess, const double *grad, double *inv_out, double *delta_out, double *cond_out);
+
+/*
  * One process per GPU: the reduction step of the site-sharded path on RCCL, issued from the engine.
  * Sites are independent given (tree, Q, rates); every rank evaluates its block of site patterns and the only exchange
  * is the sum of the aggregated outputs (src/ndaccum.c:198-254 is the reference's only cross-site step): 2 doubles for
@@ -228,8 +249,9 @@ enum {
     PLK_INFO_LL_EXEC_FLOPS = 9,     /* fp64 flops per site the last ll traversal kernel executed (all categories): 2k^2 - k per
                                        matrix-vector product it ran (k padded to 16 rows on the matrix cores), k per elementwise
                                        multiply (leaf rows, stack pops); table look-ups, moves and rescaling count nothing */
-    PLK_INFO_UPDOWN_KERNEL = 10     /* down / up kernels of the last deriv, marginal or expectation query: 0 = none yet,
-                                       1 = k = 4 kernels, 2 = generic, 3 = fp64 MFMA, 4 = register-resident vector (9 <= k <= 20) */
+    PLK_INFO_UPDOWN_KERNEL = 10     /* down / up kernels of the last deriv, marginal, expectation or second-order query: 0 = none
+                                       yet, 1 = k = 4 kernels, 2 = generic, 3 = fp64 MFMA, 4 = register-resident vector
+                                       (9 <= k <= 20), 5 = k = 4 second-order pass (after plk_hess / plk_second_order) */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -298,6 +320,7 @@ int plk_group_marginal(plk_group *g, const int *node_mask, double *site_out, dou
 int plk_group_edge_expect_multi(plk_group *g, int nL, const double *L_hi, const double *L_lo, int coef_mode,
                                 const int *edge_mask, double *site_out, double *sums_out);
 int plk_group_hess(plk_group *g, double *hess_sums_out);
+int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out);   /* either may be NULL */
 
 #ifdef __cplusplus
 }

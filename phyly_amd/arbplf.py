@@ -81,6 +81,21 @@ def arbplf_hess(s):
     return _call("arbplf_hess", s)
 
 
+def arbplf_inv_hess(s):
+    """inverse of that Hessian: the covariance estimate of the fitted edge rates (src/arbplfhess.c:1238-1267)"""
+    return _call("arbplf_inv_hess", s)
+
+
+def arbplf_newton_delta(s):
+    """the Newton step -H^-1 g in the edge rate coefficients (src/arbplfhess.c:1372-1388)"""
+    return _call("arbplf_newton_delta", s)
+
+
+def arbplf_newton_update(s):
+    """edge rate coefficients after one unclamped Newton step (src/arbplfhess.c:1427-1443)"""
+    return _call("arbplf_newton_update", s)
+
+
 def _out_of_scope(name):
     def f(s):
         raise RuntimeError("arbplf likelihood error: %s is outside the MI355X hot path of this build" % name)
@@ -88,7 +103,6 @@ def _out_of_scope(name):
     return f
 
 
-# the reference module's other entry points (src/arbplf.c:521-534) are out of scope
-for _name in ("arbplf_inv_hess",
-              "arbplf_newton_delta", "arbplf_newton_update", "arbplf_newton_refine"):
+# certified refinement needs interval arithmetic (src/arbplf.c:521-534): out of scope
+for _name in ("arbplf_newton_refine",):
     globals()[_name] = _out_of_scope(_name)

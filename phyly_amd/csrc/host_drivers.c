@@ -678,6 +678,69 @@ done:
     return rc;
 }
 
+/* arbplf-inv-hess, arbplf-newton-delta, arbplf-newton-update (src/arbplfhess.c:1238-1267 inv_hess_query, :1372-1388
+ * newton_delta_query, :1427-1443 newton_point_query; parsing shared with hess): gradient and Hessian of the
+ * site-aggregated log likelihood from one engine run, then the host solve.  mode 0: H^-1, E^2 rows; 1: delta = -H^-1 g;
+ * 2: edge_rate_coefficients + delta, unclamped.  User edge order throughout. */
+static int run_second_order_solve(const jval *root, jbuf *out, int mode)
+{
+    query q;
+    int rc = -1;
+    double *gs = NULL, *hs = NULL, *hu = NULL, *gu = NULL, *inv = NULL, *delta = NULL;
+    query_init(&q);
+    if (query_parse(&q, 6, root)) goto done;
+    if (query_prepare(&q)) goto done;
+    const int E = q.m.E;
+    const size_t n = (size_t)E;
+    gs = calloc(n * 2 + 2, sizeof(double)); hs = calloc(n * n * 2 + 2, sizeof(double));
+    hu = calloc(n * n * 2 + 2, sizeof(double)); gu = calloc(n * 2 + 2, sizeof(double));
+    inv = calloc(n * n + 1, sizeof(double)); delta = calloc(n + 1, sizeof(double));
+    if (!gs || !hs || !hu || !gu || !inv || !delta) goto done;
+    if (q.U > 0 && E > 0 && plk_group_second_order(q.eng, gs, hs)) { fprintf(stderr, "error: %s\n", plk_group_last_error(q.eng)); goto done; }
+    for (int a = 0; a < E; a++) {
+        const size_t ea = (size_t)q.m.edge_order[a];
+        const long double g = ((long double)gs[2 * ea] + (long double)gs[2 * ea + 1]) / q.div_site;
+        if (check_finite((double)g, "a derivative of the log likelihood")) goto done;
+        split_ld(g, &gu[2 * a], &gu[2 * a + 1]);
+        for (int b = 0; b < E; b++) {
+            const size_t pos = ea * n + (size_t)q.m.edge_order[b];
+            const long double v = ((long double)hs[2 * pos] + (long double)hs[2 * pos + 1]) / q.div_site;
+            if (check_finite((double)v, "a second derivative of the log likelihood")) goto done;
+            split_ld(v, &hu[2 * (a * n + b)], &hu[2 * (a * n + b) + 1]);
+        }
+    }
+    if (E < 1 || plk_solve_second_order(E, hu, gu, inv, delta, NULL)) {
+        fprintf(stderr, "error: Hessian is singular to working precision; the reference does not terminate on such input\n");
+        goto done;
+    }
+    if (mode == 0) {
+        jbuf_puts(out, "{\"columns\": [\"first_edge\", \"second_edge\", \"value\"], \"data\": [");
+        for (int a = 0; a < E; a++)
+            for (int b = 0; b < E; b++) {
+                if (a || b) jbuf_puts(out, ", ");
+                jbuf_puts(out, "["); jbuf_int(out, a); jbuf_puts(out, ", "); jbuf_int(out, b); jbuf_puts(out, ", ");
+                jbuf_real(out, clean(inv[a * n + b])); jbuf_puts(out, "]");
+            }
+    } else {
+        jbuf_puts(out, "{\"columns\": [\"edge\", \"value\"], \"data\": [");
+        for (int a = 0; a < E; a++) {
+            double v = delta[a];
+            if (mode == 2) v += q.m.edge_rates_csr[q.m.edge_order[a]];
+            if (a) jbuf_puts(out, ", ");
+            jbuf_puts(out, "["); jbuf_int(out, a); jbuf_puts(out, ", "); jbuf_real(out, clean(v)); jbuf_puts(out, "]");
+        }
+    }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(gs); free(hs); free(hu); free(gu); free(inv); free(delta);
+    query_clear(&q);
+    return rc;
+}
+static int run_inv_hess(const jval *root, jbuf *out) { return run_second_order_solve(root, out, 0); }
+static int run_newton_delta(const jval *root, jbuf *out) { return run_second_order_solve(root, out, 1); }
+static int run_newton_update(const jval *root, jbuf *out) { return run_second_order_solve(root, out, 2); }
+
 /* ------------------------------------------------------------------ string API */
 static char *string_hom(int (*run)(const jval *, jbuf *), void *userdata, const char *s_in, int *retcode)
 {
@@ -712,14 +775,19 @@ char *arbplf_dwell_string(void *userdata, const char *s_in, int *retcode) { retu
 char *arbplf_trans_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_trans, userdata, s_in, retcode); }
 char *arbplf_em_update_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_em_update, userdata, s_in, retcode); }
 char *arbplf_hess_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_hess, userdata, s_in, retcode); }
+char *arbplf_inv_hess_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_inv_hess, userdata, s_in, retcode); }
+char *arbplf_newton_delta_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_newton_delta, userdata, s_in, retcode); }
+char *arbplf_newton_update_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_newton_update, userdata, s_in, retcode); }
 
 /* Host-only validation (JSON grammar, model, reductions); no GPU is touched.
- * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update" or "hess".  Returns 0 when the input would be accepted. */
+ * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta" or "newton_update".
+ * Returns 0 when the input would be accepted. */
 int arbplf_validate_string(const char *what, const char *s_in)
 {
     char err[256];
     int kind = !strcmp(what, "ll") ? 0 : !strcmp(what, "deriv") ? 1 : !strcmp(what, "marginal") ? 2 :
-               !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 : -1;
+               !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 :
+               (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 : -1;
     if (kind < 0 || !s_in) return -1;
     json_doc *doc = json_doc_parse(s_in, err, sizeof err);
     if (!doc) { fprintf(stderr, "%s\n", err); return -1; }

@@ -228,7 +228,8 @@ int plk_group_set_site_weights(plk_group *g, const double *w)
 /* every engine writes its per-site rows at its global offset and its partial sums into its own slice of `part`;
  * the slices are then added in engine order */
 typedef struct {
-    int kind;                      /* 0 ll, 1 deriv, 2 marginal, 3 edge expectations, 4 hess */
+    int kind;                      /* 0 ll, 1 deriv, 2 marginal, 3 edge expectations, 4 hess, 5 gradient and / or Hessian */
+    int want_grad, want_hess;      /* kind 5 */
     const int *mask;
     double *site_out;              /* global buffer or NULL */
     size_t site_row;               /* doubles per site in site_out */
@@ -237,6 +238,11 @@ typedef struct {
     int nL, coef_mode;
     const double *L_hi, *L_lo;
 } q_ctx;
+
+/* The engine's gradient-and-Hessian entry is bound weakly: the host-only test programs (tests/group_check.c,
+ * tests/sanitize_host.c) link this file against stand-in engines that have the older entry points only; there the same
+ * sums come from plk_deriv and plk_hess.  libarbplf_amd.so always has the entry, so the library never takes that branch. */
+extern int plk_second_order(plk_engine *h, double *grad_sums_out, double *hess_sums_out) __attribute__((weak));
 
 static int job_query(plk_group *g, int i, void *p)
 {
@@ -248,6 +254,13 @@ static int job_query(plk_group *g, int i, void *p)
     case 1: return plk_deriv(g->eng[i], c->mask, site, sums);
     case 2: return plk_marginal(g->eng[i], c->mask, site, sums);
     case 3: return plk_edge_expect_multi(g->eng[i], c->nL, c->L_hi, c->L_lo, c->coef_mode, c->mask, site, sums);
+    case 5: {                                     /* [E] gradient and / or [E][E] Hessian, in that order */
+        double *gs = c->want_grad ? sums : NULL;
+        double *hs = c->want_hess ? sums + (c->want_grad ? 2 * (size_t)g->E : 0) : NULL;
+        if (plk_second_order) return plk_second_order(g->eng[i], gs, hs);
+        int rc = gs ? plk_deriv(g->eng[i], NULL, NULL, gs) : 0;
+        return rc || !hs ? rc : plk_hess(g->eng[i], hs);
+    }
     default: return plk_hess(g->eng[i], sums);
     }
 }
@@ -322,4 +335,22 @@ int plk_group_hess(plk_group *g, double *hess_sums_out)
     q_ctx c = {0};
     c.kind = 4; c.nsum = (size_t)g->E * g->E;
     return run_query(g, &c, hess_sums_out);
+}
+
+/* gradient and Hessian sums of the engines added as one vector of E and / or E*E double-double entries: only what is
+ * asked for is computed, allocated and reduced */
+int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out)
+{
+    if (!g || (!grad_sums_out && !hess_sums_out)) return PLK_E_ARG;
+    const size_t E = (size_t)g->E, ng = grad_sums_out ? E : 0, nh = hess_sums_out ? E * E : 0;
+    q_ctx c = {0};
+    c.kind = 5; c.nsum = ng + nh; c.want_grad = grad_sums_out != NULL; c.want_hess = hess_sums_out != NULL;
+    if (!grad_sums_out) return run_query(g, &c, hess_sums_out);
+    if (!hess_sums_out) return run_query(g, &c, grad_sums_out);
+    double *both = calloc(2 * c.nsum + 2, sizeof(double));
+    if (!both) return fail(g, PLK_E_NOMEM, "plk_group: out of host memory");
+    const int rc = run_query(g, &c, both);
+    if (!rc) { memcpy(grad_sums_out, both, 2 * ng * sizeof(double)); memcpy(hess_sums_out, both + 2 * ng, 2 * nh * sizeof(double)); }
+    free(both);
+    return rc;
 }

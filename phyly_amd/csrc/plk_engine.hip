@@ -803,6 +803,7 @@ __device__ __forceinline__ double wave64_sum_lane63(double x)
 #include "plk_vec.h"
 #include "plk_updown_vec.h"
 #include "plk_updown4.h"
+#include "plk_hess4.h"
 
 /* ====================================================================== */
 /* K2+K3 generic: any k <= K, stack slots in HBM                           */
@@ -1112,6 +1113,8 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_down_store(UpArgs a)
         /* combine the categories at the largest exponent: LH = sum_c prior_c lh_c 2^(X_c - Xmax).  When every term is
          * zero (an edge-modified model of plk_hess at a site that does not depend on the edge) the exponent of the
          * vectors themselves is kept, so that the division by the unmodified likelihood stays finite */
+        /* (a category whose own term is exactly zero takes no part in xmax; were its X_c more than 1023 above xmax, its
+         * weight 2^(X_c - xmax) below would overflow.  Not reached by any known input; k_hess4_down does the same) */
         if (xmax == INT_MIN) xmax = xall == INT_MIN ? 0 : xall;
         if (a.XM) a.XM[sl] = (double)xmax;
         for (int c = 0; c < a.C; c++) {
@@ -3418,20 +3421,11 @@ static void launch_hess_pass_k(plk_engine *h, const UpArgs &a, unsigned grid)
  * first-order passes (each pass stores its factors; the common exponents of the modified and the unmodified model
  * are reconciled in the division).
  */
-extern "C" int plk_hess(plk_engine *h, double *hess_sums_out /* [E][E][2] */)
+/* Qn^2 in double-double on the host, uploaded as [2][k*k] (hi, lo) */
+static int upload_Q2(plk_engine *h, double **d_Q2)
 {
-    if (!plk_live(h) || !hess_sums_out) return PLK_E_ARG;
-    if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_hess: tree, model and patterns must be set"; return PLK_E_ARG; }
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
-    if ((rc = ensure_dP(h))) return rc;
-    const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
-    const long S = h->S;
-    const size_t kk = (size_t)k * k, strm = (size_t)C * E * K * K;
-    if (E == 0) return PLK_OK;
-
-    /* Qn^2 in double-double on the host */
+    const int k = h->k;
+    const size_t kk = (size_t)k * k;
     std::vector<double> Q2(2 * kk);
     for (int i = 0; i < k; i++)
         for (int j = 0; j < k; j++) {
@@ -3441,6 +3435,18 @@ extern "C" int plk_hess(plk_engine *h, double *hess_sums_out /* [E][E][2] */)
                                          dd_make(h->Qn[(size_t)l * k + j], h->Qn[kk + (size_t)l * k + j])));
             Q2[(size_t)i * k + j] = acc.hi; Q2[kk + (size_t)i * k + j] = acc.lo;
         }
+    return dev_upload(h, d_Q2, Q2.data(), Q2.size());
+}
+
+/* the E + 1 passes on the generic vector kernels (any k, dense patterns, any number of categories): Hrow[j][i] += the
+ * weighted sums of row j of H / f, G[i][j] += sum_s w_s (g_i / f)(g_j / f) for i >= j, gsum[i] += sum_s w_s g_i / f */
+static int second_order_generic(plk_engine *h, std::vector<long double> &Hrow, std::vector<long double> &G, long double *gsum)
+{
+    int rc;
+    const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
+    const long S = h->S;
+    const size_t kk = (size_t)k * k, strm = (size_t)C * E * K * K;
+
     double *d_Q2 = nullptr, *d_d2P = nullptr, *d_PT = nullptr, *d_PN = nullptr, *d_DT = nullptr, *d_DN = nullptr, *d_D2T = nullptr;
     double *d_LH0 = nullptr, *d_D0 = nullptr, *d_XM0 = nullptr;
     dd *d_G = nullptr;
@@ -3449,7 +3455,7 @@ extern "C" int plk_hess(plk_engine *h, double *hess_sums_out /* [E][E][2] */)
         void *ps[] = {d_Q2, d_d2P, d_PT, d_PN, d_DT, d_DN, d_D2T, d_LH0, d_D0, d_XM0, d_G, d_has, d_ns};
         for (void *p : ps) if (p) (void)hipFree(p);
     };
-    if ((rc = dev_upload(h, &d_Q2, Q2.data(), Q2.size())) || (rc = dev_alloc(h, &d_d2P, (size_t)C * E * kk)) ||
+    if ((rc = upload_Q2(h, &d_Q2)) || (rc = dev_alloc(h, &d_d2P, (size_t)C * E * kk)) ||
         (rc = dev_alloc(h, &d_PT, strm)) || (rc = dev_alloc(h, &d_PN, strm)) || (rc = dev_alloc(h, &d_DT, strm)) ||
         (rc = dev_alloc(h, &d_DN, strm)) || (rc = dev_alloc(h, &d_D2T, strm)) || (rc = dev_alloc(h, &d_G, (size_t)E * E))) { cleanup(); return rc; }
     hipLaunchKernelGGL(k_d2p, dim3(C * E), dim3(kk >= 256 ? 256 : 64), 0, h->stream, k, E, d_Q2, h->d_Pdd, h->d_cat_rates, d_d2P);
@@ -3484,7 +3490,6 @@ extern "C" int plk_hess(plk_engine *h, double *hess_sums_out /* [E][E][2] */)
         (rc = dev_alloc(h, &d_LH0, (size_t)chunk)) || (rc = dev_alloc(h, &d_XM0, (size_t)chunk)) ||
         (rc = dev_alloc(h, &d_D0, (size_t)E * chunk))) { cleanup(); return rc; }
 
-    std::vector<long double> Hrow((size_t)E * E, 0.0L), G((size_t)E * E, 0.0L);
     std::vector<dd> gh((size_t)E * E);
     for (long s0 = 0; s0 < S; s0 += chunk) {
         const long n = std::min(chunk, S - s0);
@@ -3524,6 +3529,7 @@ extern "C" int plk_hess(plk_engine *h, double *hess_sums_out /* [E][E][2] */)
         if (e != hipSuccess) { cleanup(); h->err = std::string("plk_hess: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
         for (int i = 0; i < E; i++)
             for (int j = 0; j <= i; j++) G[(size_t)i * E + j] += (long double)gh[(size_t)i * E + j].hi + (long double)gh[(size_t)i * E + j].lo;
+        if (gsum && (rc = wsum_rows(h, E, n, d_D0, w, gsum))) { cleanup(); return rc; }
         /* passes 1..E: row j of the likelihood Hessian, normalised by the unmodified likelihood */
         a.LHdiv = d_LH0; a.XMdiv = d_XM0;
         for (int j = 0; j < E; j++) {
@@ -3534,13 +3540,176 @@ extern "C" int plk_hess(plk_engine *h, double *hess_sums_out /* [E][E][2] */)
         }
     }
     cleanup();
-    for (int i = 0; i < E; i++)
-        for (int j = 0; j <= i; j++) {
-            /* both triangles of the likelihood Hessian were computed; average them */
-            const long double v = (Hrow[(size_t)i * E + j] + Hrow[(size_t)j * E + i]) * 0.5L - G[(size_t)i * E + j];
-            const double hi = (double)v, lo = (double)(v - (long double)hi);
-            hess_sums_out[2 * ((size_t)i * E + j)] = hess_sums_out[2 * ((size_t)j * E + i)] = hi;
-            hess_sums_out[2 * ((size_t)i * E + j) + 1] = hess_sums_out[2 * ((size_t)j * E + i) + 1] = lo;
-        }
     return PLK_OK;
+}
+
+/* the k = 4 second-order pass (plk_hess4.h) applies: compact codes, at most four rate categories */
+static bool use_hess4(const plk_engine *h)
+{
+    return !h->opt_force_generic && h->k == 4 && h->pat_mode == 1 && h->C <= 4 && h->E > 0;
+}
+
+template <int NM>
+static void launch_hess4(plk_engine *h, const Hess4Args &a, unsigned grid)
+{
+    hipLaunchKernelGGL(k_hess4_down<NM>, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
+    hipLaunchKernelGGL(k_hess4_up<NM>, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
+}
+
+/* rows of the Hessian the next launch carries when `left` rows remain: 4, 2 or 1 models, no idle row (three rows: 2 + 1) */
+static int hess4_nm(int left) { return left >= 4 ? 4 : (left >= 2 ? 2 : 1); }
+
+/* the same sums as second_order_generic on the k = 4 kernels: pass 0 (one model, no modified edge), then
+ * launches of four edge-modified models each (two or one for the last rows) */
+static int second_order_k4(plk_engine *h, std::vector<long double> &Hrow, std::vector<long double> &G, long double *gsum)
+{
+    int rc;
+    const int N = h->N, E = h->E, C = h->C;
+    const long S = h->S;
+    if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
+    const int ntips = (int)h->tip_edge.size();
+    std::vector<int> edge_tip(E, -1), node_int(N, -1), node_scale(N, -1);
+    for (int t = 0; t < ntips; t++) edge_tip[h->tip_edge[t]] = t;
+    int nin = 0, nsc = 0;
+    for (int a = 0; a < N; a++) if (h->indptr[a + 1] > h->indptr[a]) node_int[a] = nin++;
+    for (int a = 0; a < N; a++) if (node_int[a] >= 0 && h->scale_node[a]) node_scale[a] = nsc++;
+    std::vector<int> te = h->tip_edge;
+    te.push_back(-1);
+    if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
+    std::vector<int> hd(h->node_has_data.begin(), h->node_has_data.end());
+
+    double *d_Q2 = nullptr, *d_d2P = nullptr, *d_tab = nullptr, *d_LH0 = nullptr, *d_XM0 = nullptr, *d_D0 = nullptr;
+    dd *d_G = nullptr;
+    int *d_et = nullptr, *d_ni = nullptr, *d_ns = nullptr, *d_te = nullptr, *d_has = nullptr;
+    auto cleanup = [&]() {
+        void *ps[] = {d_Q2, d_d2P, d_tab, d_LH0, d_XM0, d_D0, d_G, d_et, d_ni, d_ns, d_te, d_has};
+        for (void *p : ps) if (p) (void)hipFree(p);
+    };
+    const size_t ntab = (size_t)C * (ntips + 1) * h->nchar * 4;
+    if ((rc = upload_Q2(h, &d_Q2)) || (rc = dev_alloc(h, &d_d2P, (size_t)C * E * 16)) || (rc = dev_alloc(h, &d_tab, 3 * ntab)) ||
+        (rc = dev_alloc(h, &d_G, (size_t)E * E)) || (rc = dev_upload(h, &d_et, edge_tip.data(), (size_t)E)) ||
+        (rc = dev_upload(h, &d_ni, node_int.data(), (size_t)N)) || (rc = dev_upload(h, &d_ns, node_scale.data(), (size_t)N)) ||
+        (rc = dev_upload(h, &d_te, te.data(), te.size())) || (rc = dev_upload(h, &d_has, hd.data(), (size_t)N))) { cleanup(); return rc; }
+    double *d_tip = d_tab, *d_dtip = d_tab + ntab, *d_d2tip = d_tab + 2 * ntab;
+    hipLaunchKernelGGL(k_d2p, dim3(C * E), dim3(64), 0, h->stream, 4, E, d_Q2, h->d_Pdd, h->d_cat_rates, d_d2P);
+    hipLaunchKernelGGL(k_build_tip, dim3(ntips + 1, C), dim3(64), 0, h->stream, E, ntips + 1, h->nchar, d_te, h->d_Pdd, h->d_defs, d_tip);
+    hipLaunchKernelGGL(k_build_dtip4, dim3(ntips + 1, C), dim3(64), 0, h->stream, E, ntips, h->nchar, d_te, h->d_dP, h->d_defs, d_dtip, 1);
+    hipLaunchKernelGGL(k_build_dtip4, dim3(ntips + 1, C), dim3(64), 0, h->stream, E, ntips, h->nchar, d_te, d_d2P, h->d_defs, d_d2tip, 1);
+    if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_second_order: matrix set-up failed"; return PLK_E_DEVICE; }
+
+    const int NMX = hess4_nm(E);
+    const size_t vs1 = (size_t)nin * C * 4, sc1 = (size_t)nsc * C;        /* per site and model */
+    const size_t per_model = 2 * vs1 + sc1 + 2 * (size_t)C + 2 + (size_t)E;
+    const size_t per_site_d = (size_t)NMX * per_model;
+    const size_t per_site = (per_site_d + 2 + (size_t)E) * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
+    budget += h->work_cap * sizeof(double);
+    long chunk = (long)std::min<size_t>((size_t)S, budget / per_site);
+    if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
+    if (chunk < 1) { cleanup(); h->err = "plk_second_order: not enough device memory for one site"; return PLK_E_NOMEM; }
+    if (chunk < S) chunk = std::max<long>(UD4_BLOCK, chunk / UD4_BLOCK * UD4_BLOCK);
+    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site_d * (size_t)chunk)) ||
+        (rc = dev_alloc(h, &d_LH0, (size_t)chunk)) || (rc = dev_alloc(h, &d_XM0, (size_t)chunk)) ||
+        (rc = dev_alloc(h, &d_D0, (size_t)E * chunk))) { cleanup(); return rc; }
+
+    std::vector<dd> gh((size_t)E * E);
+    for (long s0 = 0; s0 < S; s0 += chunk) {
+        const long n = std::min(chunk, S - s0);
+        Hess4Args a;
+        a.Spad = h->Spad; a.s0 = s0; a.n = n;
+        a.N = N; a.E = E; a.C = C; a.nchar = h->nchar; a.ntips = ntips; a.root_mode = h->root_mode;
+        a.indptr = h->d_indptr; a.indices = h->d_indices; a.preorder = h->d_preorder;
+        a.node_has_data = d_has; a.edge_tip = d_et; a.node_int = d_ni; a.node_scale = d_ns;
+        a.P = h->d_P; a.dP = h->d_dP; a.d2P = d_d2P; a.tip = d_tip; a.dtip = d_dtip; a.d2tip = d_d2tip;
+        a.codes = h->d_codes; a.cat_prior = h->d_cat_prior; a.root_w = h->d_root_w;
+        a.vstride = vs1 * n; a.scstride = sc1 * n;
+        double *p = h->d_work;
+        a.LN = p; p += (size_t)NMX * vs1 * n;
+        a.FN = p; p += (size_t)NMX * vs1 * n;
+        a.SC = p; p += (size_t)NMX * sc1 * n;
+        a.CW = p; p += (size_t)NMX * C * n;
+        a.XC = p; p += (size_t)NMX * C * n;
+        a.XM = p; p += (size_t)NMX * n;
+        a.LH = p; p += (size_t)NMX * n;
+        a.DV = p; p += (size_t)NMX * E * n;
+        const unsigned grid = (unsigned)((n + UD4_BLOCK - 1) / UD4_BLOCK);
+        const double *w = h->d_w ? h->d_w + s0 : nullptr;
+        /* pass 0: the model itself -> f and g / f */
+        for (int m = 0; m < H4_MAX_NM; m++) a.mod[m] = -1;
+        a.LHdiv = nullptr; a.XMdiv = nullptr;
+        launch_hess4<1>(h, a, grid);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(d_LH0, a.LH, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_XM0, a.XM, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_D0, a.DV, (size_t)E * n * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_gram, dim3(E, E), dim3(256), 0, h->stream, E, n, d_D0, w, d_G);
+            e = hipMemcpyAsync(gh.data(), d_G, (size_t)E * E * sizeof(dd), hipMemcpyDeviceToHost, h->stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) { cleanup(); h->err = std::string("plk_second_order: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
+        for (int i = 0; i < E; i++)
+            for (int j = 0; j <= i; j++) G[(size_t)i * E + j] += (long double)gh[(size_t)i * E + j].hi + (long double)gh[(size_t)i * E + j].lo;
+        if (gsum && (rc = wsum_rows(h, E, n, d_D0, w, gsum))) { cleanup(); return rc; }
+        /* rows j0 .. j0 + rows - 1 of the likelihood Hessian per launch, normalised by the unmodified likelihood */
+        a.LHdiv = d_LH0; a.XMdiv = d_XM0;
+        for (int j0 = 0; j0 < E;) {
+            const int nm = hess4_nm(E - j0), rows = nm;
+            for (int m = 0; m < H4_MAX_NM; m++) a.mod[m] = m < rows ? j0 + m : -1;
+            if (nm == 4) launch_hess4<4>(h, a, grid);
+            else if (nm == 2) launch_hess4<2>(h, a, grid);
+            else launch_hess4<1>(h, a, grid);
+            if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_second_order: kernel launch failed"; return PLK_E_DEVICE; }
+            if ((rc = wsum_rows(h, rows * E, n, a.DV, w, Hrow.data() + (size_t)j0 * E))) { cleanup(); return rc; }
+            j0 += rows;
+        }
+    }
+    cleanup();
+    return PLK_OK;
+}
+
+/*
+ * Site-weighted gradient and Hessian from one run: pass 0 of the Hessian already produces g / f per site, so a
+ * Newton step (src/arbplfhess.c:169-234 needs both) does not pay a separate derivative query.  k = 4 with compact
+ * codes and at most four rate categories runs the one-thread-per-site pass of plk_hess4.h, everything else the
+ * generic passes.
+ */
+extern "C" int plk_second_order(plk_engine *h, double *grad_sums_out /* [E][2] or NULL */, double *hess_sums_out /* [E][E][2] or NULL */)
+{
+    if (!plk_live(h) || (!grad_sums_out && !hess_sums_out)) return PLK_E_ARG;
+    if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_second_order: tree, model and patterns must be set"; return PLK_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
+    if ((rc = ensure_dP(h))) return rc;
+    const int E = h->E;
+    if (E == 0) return PLK_OK;
+    std::vector<long double> Hrow((size_t)E * E, 0.0L), G((size_t)E * E, 0.0L), gsum((size_t)E, 0.0L);
+    if (use_hess4(h)) { h->info_updown_kernel = 5; rc = second_order_k4(h, Hrow, G, grad_sums_out ? gsum.data() : nullptr); }
+    else { h->info_updown_kernel = 2; rc = second_order_generic(h, Hrow, G, grad_sums_out ? gsum.data() : nullptr); }
+    if (rc) return rc;
+    if (grad_sums_out)
+        for (int i = 0; i < E; i++) {
+            const double hi = (double)gsum[i];
+            grad_sums_out[2 * i] = hi;
+            grad_sums_out[2 * i + 1] = (double)(gsum[i] - (long double)hi);
+        }
+    if (hess_sums_out)
+        for (int i = 0; i < E; i++)
+            for (int j = 0; j <= i; j++) {
+                /* both triangles of the likelihood Hessian were computed; average them */
+                const long double v = (Hrow[(size_t)i * E + j] + Hrow[(size_t)j * E + i]) * 0.5L - G[(size_t)i * E + j];
+                const double hi = (double)v, lo = (double)(v - (long double)hi);
+                hess_sums_out[2 * ((size_t)i * E + j)] = hess_sums_out[2 * ((size_t)j * E + i)] = hi;
+                hess_sums_out[2 * ((size_t)i * E + j) + 1] = hess_sums_out[2 * ((size_t)j * E + i) + 1] = lo;
+            }
+    return PLK_OK;
+}
+
+extern "C" int plk_hess(plk_engine *h, double *hess_sums_out /* [E][E][2] */)
+{
+    if (!hess_sums_out) return PLK_E_ARG;
+    return plk_second_order(h, nullptr, hess_sums_out);
 }

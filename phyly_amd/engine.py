@@ -64,6 +64,8 @@ def load_library():
     lib.plk_get_frechet_matrices.argtypes = [vp, vp, vp, ci, vp]
     lib.plk_fit_edge_rates.argtypes = [vp, ci, ci, ctypes.c_double, vp, vp, vp, ctypes.POINTER(ci), ctypes.POINTER(cl)]
     lib.plk_hess.argtypes = [vp, vp]
+    lib.plk_second_order.argtypes = [vp, vp, vp]
+    lib.plk_solve_second_order.argtypes = [ci, vp, vp, vp, vp, vp]
     lib.plk_get_transition_matrices.argtypes = [vp, vp]
     lib.plk_get_info.argtypes = [vp, ci, ctypes.POINTER(cl)]
     lib.plk_set_option.argtypes = [vp, ci, cl]
@@ -251,6 +253,13 @@ class Engine:
         out = np.zeros((self.E, self.E, 2))
         self._check(self._lib.plk_hess(self._h, _ptr(out)))
         return out[..., 0] + out[..., 1]
+
+    def second_order(self):
+        """([E] gradient, [E][E] Hessian) of the weighted log likelihood in the edge rates (CSR order) from one run"""
+        grad = np.zeros((self.E, 2))
+        out = np.zeros((self.E, self.E, 2))
+        self._check(self._lib.plk_second_order(self._h, _ptr(grad), _ptr(out)))
+        return grad[:, 0] + grad[:, 1], out[..., 0] + out[..., 1]
 
     def transition_matrices(self):
         P = np.empty((self.C, self.E, self.k, self.k))
