@@ -47,11 +47,18 @@ char *arbplf_hess_string(void *userdata, const char *s_in, int *retcode);
 char *arbplf_inv_hess_string(void *userdata, const char *s_in, int *retcode);
 char *arbplf_newton_delta_string(void *userdata, const char *s_in, int *retcode);
 char *arbplf_newton_update_string(void *userdata, const char *s_in, int *retcode);
+/* Rate-category posteriors and posterior mean site rates of a rate mixture (empirical Bayes; the reference has no such
+ * command).  cat_posterior: model_and_data, optional site_reduction and category_reduction (the reference's reduction
+ * grammar), columns ["site", "category", "value"] with aggregated axes dropped; categories in the order of the mixture,
+ * the invariable one last.  site_rate: model_and_data, optional site_reduction, columns ["site", "value"].  A model
+ * without a mixture has one category: posterior 1, rate 1. */
+char *arbplf_cat_posterior_string(void *userdata, const char *s_in, int *retcode);
+char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode);
 
 /* Host-only validation of an input document (JSON grammar, model_and_data,
  * reductions) exactly as the corresponding query would perform it, without
  * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
- * "inv_hess" | "newton_delta" | "newton_update".  0 = accepted. */
+ * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate".  0 = accepted. */
 int arbplf_validate_string(const char *what, const char *s_in);
 
 /* stdin -> stdout filter used by the CLI mains (run_string_script,

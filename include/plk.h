@@ -144,6 +144,21 @@ int plk_marginal(plk_engine *h, const int *node_mask,
                  double *site_out, double *sums_out);
 
 /*
+ * Rate-category posteriors and posterior mean site rates (empirical Bayes; the reference has no such query).
+ * With L_{s,c} the site likelihood under category c alone (root prior included), in the category order of plk_set_model:
+ *     post[s][c] = cat_prior_c L_{s,c} / sum_c' cat_prior_c' L_{s,c'}        rate[s] = sum_c post[s][c] cat_rates[c]
+ * One traversal for all categories (plk_catpost.h).  post_out: NULL or [S][C] host; rate_out: NULL or [S] host;
+ * post_sums_out: NULL or [C][2]; rate_sum_out: NULL or [2]: double-double sums over sites of w_s post[s][c] and
+ * w_s rate[s].  A category of prior 0 has posterior exactly 0.  A site of likelihood 0 gets NaN in post and rate (-inf in
+ * site_ll); when sums are asked for and such a site has a non-zero weight the call fails with PLK_E_ARG ("site likelihood
+ * zero").  plk_ll and every other query give the same bits whether or not this call ran in between.
+ * plk_cat_posterior_ll is the same call with the by-products: site_ll_out NULL or [S] host, ll_sum_out NULL or [2].
+ */
+int plk_cat_posterior(plk_engine *h, double *post_out, double *rate_out, double *post_sums_out, double *rate_sum_out);
+int plk_cat_posterior_ll(plk_engine *h, double *post_out, double *rate_out, double *site_ll_out,
+                         double *post_sums_out, double *rate_sum_out, double *ll_sum_out);
+
+/*
  * Conditional edge expectations: the shared core of arbplf-dwell, arbplf-trans
  * and arbplf-em-update.  For a direction matrix L (k x k, given as
  * an unevaluated sum L_hi + L_lo; L_lo may be NULL) the engine forms, per category c
@@ -249,9 +264,14 @@ enum {
     PLK_INFO_LL_EXEC_FLOPS = 9,     /* fp64 flops per site the last ll traversal kernel executed (all categories): 2k^2 - k per
                                        matrix-vector product it ran (k padded to 16 rows on the matrix cores), k per elementwise
                                        multiply (leaf rows, stack pops); table look-ups, moves and rescaling count nothing */
-    PLK_INFO_UPDOWN_KERNEL = 10     /* down / up kernels of the last deriv, marginal, expectation or second-order query: 0 = none
+    PLK_INFO_UPDOWN_KERNEL = 10,    /* down / up kernels of the last deriv, marginal, expectation or second-order query: 0 = none
                                        yet, 1 = k = 4 kernels, 2 = generic, 3 = fp64 MFMA, 4 = register-resident vector
                                        (9 <= k <= 20), 5 = k = 4 second-order pass (after plk_hess / plk_second_order) */
+    PLK_INFO_CAT_POSTERIOR_KERNEL = 11, /* kernel of the last plk_cat_posterior: 0 = none yet, 1 = k = 4 register kernel
+                                       (compact codes, at most 8 categories), 2 = generic */
+    PLK_INFO_CATEGORIES = 12,       /* rate categories of the model (0 before plk_set_model) */
+    PLK_INFO_LAST_CAT_POSTERIOR_NS = 13 /* HIP-event time of the device work of the last plk_cat_posterior (K1 when the rates
+                                       changed, tables, kernel, sums); for tools/time_cat_posterior.py */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -319,6 +339,8 @@ int plk_group_deriv(plk_group *g, const int *edge_mask, double *site_edge_out, d
 int plk_group_marginal(plk_group *g, const int *node_mask, double *site_out, double *sums_out);
 int plk_group_edge_expect_multi(plk_group *g, int nL, const double *L_hi, const double *L_lo, int coef_mode,
                                 const int *edge_mask, double *site_out, double *sums_out);
+/* post_out [S][C] and rate_out [S] at their global positions; post_sums_out [C][2], rate_sum_out [2] (any may be NULL) */
+int plk_group_cat_posterior(plk_group *g, double *post_out, double *rate_out, double *post_sums_out, double *rate_sum_out);
 int plk_group_hess(plk_group *g, double *hess_sums_out);
 int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out);   /* either may be NULL */
 

@@ -96,6 +96,16 @@ def arbplf_newton_update(s):
     return _call("arbplf_newton_update", s)
 
 
+def arbplf_cat_posterior(s):
+    """posterior probability of each rate category at each site (no counterpart in the reference)"""
+    return _call("arbplf_cat_posterior", s)
+
+
+def arbplf_site_rate(s):
+    """posterior mean relative rate of each site: sum over categories of posterior * category rate"""
+    return _call("arbplf_site_rate", s)
+
+
 def _out_of_scope(name):
     def f(s):
         raise RuntimeError("arbplf likelihood error: %s is outside the MI355X hot path of this build" % name)

@@ -235,7 +235,8 @@ static int check_finite(double v, const char *what)
     return -1;
 }
 
-/* _parse of the drivers: kind 0 ll, 1 deriv, 2 marginal, 3 dwell, 4 trans, 5 em-update
+/* _parse of the drivers: kind 0 ll, 1 deriv, 2 marginal, 3 dwell, 4 trans, 5 em-update, 6 the second-order family,
+ * 7 cat-posterior, 8 site-rate (no counterpart in the reference: its reduction grammar, its table layout)
  * (src/arbplfll.c:250-288, src/arbplfderiv.c:445-493, src/arbplfmarginal.c:348-405,
  *  src/arbplfdwell.c:507-566, src/arbplftrans.c:553-614, src/arbplfem.c:505-545) */
 static int query_parse(query *q, int kind, const jval *root)
@@ -246,8 +247,9 @@ static int query_parse(query *q, int kind, const jval *root)
     static const char *const all_marg[] = {"model_and_data", "site_reduction", "node_reduction", "state_reduction", NULL};
     static const char *const all_dwell[] = {"model_and_data", "site_reduction", "edge_reduction", "state_reduction", NULL};
     static const char *const all_trans[] = {"model_and_data", "site_reduction", "edge_reduction", "trans_reduction", NULL};
+    static const char *const all_catpost[] = {"model_and_data", "site_reduction", "category_reduction", NULL};
     const char *const *allowed = kind == 0 ? all_ll : kind == 1 ? all_deriv : kind == 2 ? all_marg :
-                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : all_ll;
+                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : kind == 7 ? all_catpost : all_ll;
     if (host_check_keys(root, req, allowed, "input")) return -1;
     if (host_model_parse(&q->m, j_get(root, "model_and_data"))) return -1;
     if (host_reduction_parse(&q->r_site, (int)q->m.S, "site", j_get(root, "site_reduction"))) return -1;
@@ -258,6 +260,8 @@ static int query_parse(query *q, int kind, const jval *root)
     if (kind == 3 && host_reduction_parse(&q->r_b, q->m.k, "state", j_get(root, "state_reduction"))) return -1;
     if (kind == 4 && host_pair_reduction_parse(&q->r_b, &q->pair_first, &q->pair_second, q->m.k, "trans",
                                                j_get(root, "trans_reduction"))) return -1;
+    /* the category axis has the length the mixture gives it (Gamma categories first, the invariable one last) */
+    if (kind == 7 && host_reduction_parse(&q->r_a, arbplf_k0_category_count(&q->m.mix), "category", j_get(root, "category_reduction"))) return -1;
     if (kind == 6 && !j_get(root, "site_reduction")) { fprintf(stderr, "error: site_reduction is required\n"); return -1; }
     if ((kind == 5 || kind == 6) && q->r_site.agg_mode == AGG_NONE) { fprintf(stderr, "error: aggregation over sites is required\n"); return -1; }
     return 0;
@@ -741,6 +745,123 @@ static int run_inv_hess(const jval *root, jbuf *out) { return run_second_order_s
 static int run_newton_delta(const jval *root, jbuf *out) { return run_second_order_solve(root, out, 1); }
 static int run_newton_update(const jval *root, jbuf *out) { return run_second_order_solve(root, out, 2); }
 
+/* ------------------------------------------------------------------ cat-posterior / site-rate */
+/* a failed sums call of the engine because a weighted site has likelihood zero gets the drivers' usual diagnostic */
+static int catpost_failed(const query *q, const char *what)
+{
+    const char *msg = plk_group_last_error(q->eng);
+    if (strstr(msg, "site likelihood zero")) return check_finite(NAN, what);
+    fprintf(stderr, "error: %s\n", msg);
+    return -1;
+}
+
+/* arbplf-cat-posterior: posterior probability of every rate category at every site, axes site x category.  Site-aggregated
+ * requests take the engine's device-side sums; the [sites][categories] plane comes to the host only for per-site rows. */
+static int run_cat_posterior(const jval *root, jbuf *out)
+{
+    query q;
+    int rc = -1;
+    double *vals = NULL, *sums = NULL;
+    long double *w_cat = NULL;
+    query_init(&q);
+    if (query_parse(&q, 7, root)) goto done;
+    if (query_prepare(&q)) goto done;
+    const host_reduction *rcat = &q.r_a;
+    const int C = rcat->n;
+    w_cat = malloc((size_t)(C + 1) * sizeof(long double));
+    if (!w_cat) goto done;
+    long double div_cat = 1;
+    const int site_agg = q.r_site.agg_mode != AGG_NONE, cat_agg = rcat->agg_mode != AGG_NONE;
+    if (cat_agg) host_reduction_weights(rcat, w_cat, &div_cat);
+    const int need = q.U > 0 && rcat->selection_len > 0;
+    if (need && q.C != C) { fprintf(stderr, "internal error: category count\n"); goto done; }
+    if (site_agg) {
+        sums = calloc((size_t)C * 2 + 2, sizeof(double));
+        if (!sums) goto done;
+        if (need && plk_group_cat_posterior(q.eng, NULL, NULL, sums, NULL)) { catpost_failed(&q, "a site-aggregated category posterior"); goto done; }
+    } else {
+        vals = calloc((size_t)q.U * C + 1, sizeof(double));
+        if (!vals) goto done;
+        if (need && plk_group_cat_posterior(q.eng, vals, NULL, NULL, NULL)) { catpost_failed(&q, "a category posterior"); goto done; }
+    }
+    const char *names[] = {"site", "category"};
+    const host_reduction *reds[] = {&q.r_site, rcat};
+    table_begin(out, names, reds, 2);
+    int first = 1;
+    const int nsite_rows = site_agg ? 1 : q.r_site.selection_len;
+    const int ncat_rows = cat_agg ? 1 : rcat->selection_len;
+    for (int si = 0; si < nsite_rows; si++) {
+        const int s = site_agg ? -1 : q.r_site.selection[si];
+        const long u = site_agg ? -1 : q.site_to_u[s];
+        for (int ci = 0; ci < ncat_rows; ci++) {
+            long double v = 0;
+            const int c_lo = cat_agg ? 0 : rcat->selection[ci], c_hi = cat_agg ? C : c_lo + 1;
+            for (int c = c_lo; c < c_hi; c++) {
+                if (cat_agg && w_cat[c] == 0) continue;
+                const long double wc = cat_agg ? w_cat[c] / div_cat : 1;
+                const long double x = site_agg ? ((long double)sums[2 * c] + (long double)sums[2 * c + 1]) / q.div_site
+                                               : (long double)vals[(size_t)u * C + c];
+                v += x * wc;
+            }
+            double d = clean(v);
+            if (check_finite(d, "a category posterior")) goto done;
+            if (!first) jbuf_puts(out, ", ");
+            first = 0;
+            jbuf_puts(out, "[");
+            if (!site_agg) { jbuf_int(out, s); jbuf_puts(out, ", "); }
+            if (!cat_agg) { jbuf_int(out, rcat->selection[ci]); jbuf_puts(out, ", "); }
+            jbuf_real(out, d);
+            jbuf_puts(out, "]");
+        }
+    }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(vals); free(sums); free(w_cat);
+    query_clear(&q);
+    return rc;
+}
+
+/* arbplf-site-rate: the posterior mean relative rate of every site, sum_c post[s][c] * rate_c */
+static int run_site_rate(const jval *root, jbuf *out)
+{
+    query q;
+    int rc = -1;
+    double *rate = NULL;
+    query_init(&q);
+    if (query_parse(&q, 8, root)) goto done;
+    if (query_prepare(&q)) goto done;
+    const char *names[] = {"site"};
+    const host_reduction *reds[] = {&q.r_site};
+    table_begin(out, names, reds, 1);
+    if (q.r_site.agg_mode != AGG_NONE) {
+        double sum[2] = {0, 0};
+        if (q.U > 0 && plk_group_cat_posterior(q.eng, NULL, NULL, NULL, sum)) { catpost_failed(&q, "the aggregated site rate"); goto done; }
+        double v = clean(((long double)sum[0] + (long double)sum[1]) / q.div_site);
+        if (check_finite(v, "the aggregated site rate")) goto done;
+        jbuf_puts(out, "[");
+        jbuf_real(out, v);
+        jbuf_puts(out, "]");
+    } else {
+        rate = malloc((size_t)(q.U + 1) * sizeof(double));
+        if (!rate) goto done;
+        if (q.U > 0 && plk_group_cat_posterior(q.eng, NULL, rate, NULL, NULL)) { catpost_failed(&q, "a site rate"); goto done; }
+        for (int i = 0; i < q.r_site.selection_len; i++) {
+            int s = q.r_site.selection[i];
+            double v = clean(rate[q.site_to_u[s]]);
+            if (check_finite(v, "a site rate")) goto done;
+            if (i) jbuf_puts(out, ", ");
+            jbuf_puts(out, "["); jbuf_int(out, s); jbuf_puts(out, ", "); jbuf_real(out, v); jbuf_puts(out, "]");
+        }
+    }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(rate);
+    query_clear(&q);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ string API */
 static char *string_hom(int (*run)(const jval *, jbuf *), void *userdata, const char *s_in, int *retcode)
 {
@@ -778,16 +899,20 @@ char *arbplf_hess_string(void *userdata, const char *s_in, int *retcode) { retur
 char *arbplf_inv_hess_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_inv_hess, userdata, s_in, retcode); }
 char *arbplf_newton_delta_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_newton_delta, userdata, s_in, retcode); }
 char *arbplf_newton_update_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_newton_update, userdata, s_in, retcode); }
+char *arbplf_cat_posterior_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_cat_posterior, userdata, s_in, retcode); }
+char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_site_rate, userdata, s_in, retcode); }
 
 /* Host-only validation (JSON grammar, model, reductions); no GPU is touched.
- * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta" or "newton_update".
+ * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta", "newton_update",
+ * "cat_posterior" or "site_rate".
  * Returns 0 when the input would be accepted. */
 int arbplf_validate_string(const char *what, const char *s_in)
 {
     char err[256];
     int kind = !strcmp(what, "ll") ? 0 : !strcmp(what, "deriv") ? 1 : !strcmp(what, "marginal") ? 2 :
                !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 :
-               (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 : -1;
+               (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 :
+               !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : -1;
     if (kind < 0 || !s_in) return -1;
     json_doc *doc = json_doc_parse(s_in, err, sizeof err);
     if (!doc) { fprintf(stderr, "%s\n", err); return -1; }

@@ -329,6 +329,55 @@ int plk_group_edge_expect_multi(plk_group *g, int nL, const double *L_hi, const 
     return run_query(g, &c, sums_out);
 }
 
+/* rate-category posteriors: two per-site outputs of different row widths, C + 1 sums.  Bound weakly for the same reason
+ * as plk_second_order above: the stand-in engines of the host-only test programs do not have it. */
+extern int plk_cat_posterior(plk_engine *h, double *post_out, double *rate_out, double *post_sums_out, double *rate_sum_out) __attribute__((weak));
+extern int plk_get_info(plk_engine *h, int what, long *out) __attribute__((weak));
+
+typedef struct { int C; double *post, *rate, *part; int want_post_sums, want_rate_sum; } cp_ctx;
+
+static int job_cat_posterior(plk_group *g, int i, void *p)
+{
+    cp_ctx *c = p;
+    double *sums = c->part ? c->part + (size_t)i * (c->C + 1) * 2 : NULL;
+    return plk_cat_posterior(g->eng[i], c->post ? c->post + (size_t)g->s0[i] * c->C : NULL, c->rate ? c->rate + g->s0[i] : NULL,
+                             c->want_post_sums ? sums : NULL, c->want_rate_sum ? sums + 2 * (size_t)c->C : NULL);
+}
+
+int plk_group_cat_posterior(plk_group *g, double *post_out, double *rate_out, double *post_sums_out, double *rate_sum_out)
+{
+    if (!g) return PLK_E_ARG;
+    if (!plk_cat_posterior || !plk_get_info) return fail(g, PLK_E_UNSUPPORTED, "plk_group_cat_posterior: the engine has no plk_cat_posterior");
+    if (!g->have_patterns) return fail(g, PLK_E_ARG, "plk_group: tree, model and patterns must be set");
+    long C = 0;
+    if (plk_get_info(g->eng[0], PLK_INFO_CATEGORIES, &C) || C < 1) return fail(g, PLK_E_ARG, "plk_group_cat_posterior: the model is not set");
+    cp_ctx c = {(int)C, post_out, rate_out, NULL, post_sums_out != NULL, rate_sum_out != NULL};
+    const int want_sums = c.want_post_sums || c.want_rate_sum;
+    if (want_sums) {
+        c.part = calloc((size_t)g->G * (C + 1) * 2 + 2, sizeof(double));
+        if (!c.part) return fail(g, PLK_E_NOMEM, "plk_group: out of host memory");
+    }
+    int rc = for_each(g, job_cat_posterior, &c, 1);
+    if (!rc && want_sums) {
+        for (long r = 0; r <= C; r++) {
+            double *dst = r < C ? (post_sums_out ? post_sums_out + 2 * r : NULL) : rate_sum_out;
+            if (!dst) continue;
+            if (g->G == 1) { dst[0] = c.part[2 * r]; dst[1] = c.part[2 * r + 1]; continue; }   /* one engine: its sums, bit for bit */
+            long double acc = 0;
+            for (int i = 0; i < g->G; i++) {
+                if (g->s0[i + 1] == g->s0[i]) continue;
+                acc += (long double)c.part[((size_t)i * (C + 1) + r) * 2];
+                acc += (long double)c.part[((size_t)i * (C + 1) + r) * 2 + 1];
+            }
+            const double hi = (double)acc;
+            dst[0] = hi;
+            dst[1] = (double)(acc - (long double)hi);
+        }
+    }
+    free(c.part);
+    return rc;
+}
+
 int plk_group_hess(plk_group *g, double *hess_sums_out)
 {
     if (!g || !hess_sums_out) return PLK_E_ARG;

@@ -1,0 +1,8 @@
+/* arbplf-site-rate: JSON on stdin -> JSON on stdout, exit status 0 on success.
+ * The posterior mean relative rate of each site (no counterpart in the reference; same filter as its run_json_script). */
+#include "arbplf.h"
+
+int main(void)
+{
+    return arbplf_run_stdin(arbplf_site_rate_string);
+}

@@ -134,6 +134,21 @@ struct plk_engine {
     int mfma_first_mv = -1, mfma_first_slot = -1, mfma_first_row = 0, vec_second_row = 0;
     size_t ps_cap = 0, tip_cap = 0;
 
+    /* rate-category posteriors (plk_catpost.h): the query's own copies of the program formats and of the P-dependent
+     * tables, so that what plk_ll has cached (pair-table, assembly or C++ formats, whichever it selected) is never touched.
+     * cp_kind: 0 nothing uploaded for the current program, 1 the C++ interpreter's k = 4 formats, 2 the generic ones */
+    int cp_kind = 0;
+    bool cp_tables_valid = false;        /* the query's matrix stream and tip tables hold the current P (cleared by K1) */
+    PlkFused cpf;
+    hipEvent_t cp_ev0 = nullptr, cp_ev1 = nullptr;   /* around the device work of the last call (PLK_INFO_LAST_CAT_POSTERIOR_NS) */
+    long info_cat_posterior_ns = 0;
+    int4 *d_cp_fops = nullptr;
+    int2 *d_cp_ops = nullptr;
+    int *d_cp_mat_edge = nullptr, *d_cp_tip_edge = nullptr, *d_cp_obs_nodes = nullptr, *d_cp_op_edge = nullptr, *d_cp_expo = nullptr, *d_cp_flag = nullptr;
+    double *d_cp_PS = nullptr, *d_cp_tip = nullptr, *d_cp_out = nullptr;
+    dd *d_cp_partial = nullptr;
+    size_t cp_ps_cap = 0, cp_tip_cap = 0, cp_out_cap = 0, cp_expo_cap = 0, cp_partial_cap = 0;
+
     /* workspaces */
     double *d_slots = nullptr; size_t slots_cap = 0;
     double *d_site_ll = nullptr; size_t site_ll_cap = 0;
@@ -144,7 +159,7 @@ struct plk_engine {
     long opt_force_generic = 0, opt_site_chunk = 0, opt_fused_ns = 0, opt_fused_asm = 1, opt_mfma = 1, opt_up_nodes = 2, opt_pair_tables = 1, opt_vec_reg_stack = 1, opt_mfma_ns2 = 0;
     void *comm = nullptr;                /* ncclComm_t of the one-process-per-GPU reduction step */
     int comm_ranks = 0;
-    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_exec_flops = 0;
+    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
 static std::string g_create_error;
@@ -938,6 +953,8 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_ll_generic(GenArgs a)
     }
 }
 
+#include "plk_catpost.h"
+
 /* ====================================================================== */
 /* K2 with stored vectors + K4/K5/K6 (up pass): deriv and marginal         */
 /* ====================================================================== */
@@ -1371,12 +1388,16 @@ extern "C" void plk_destroy(plk_engine *h)
     void *ptrs[] = {h->d_indptr, h->d_indices, h->d_preorder, h->d_Qn, h->d_edge_rates, h->d_cat_rates,
                     h->d_cat_prior, h->d_root_w, h->d_Pdd, h->d_P, h->d_dP, h->d_scratch, h->d_codes,
                     h->d_defs, h->d_B, h->d_w, h->d_ops, h->d_fops, h->d_words, h->d_mat_edge, h->d_edge_slot, h->d_op_edge, h->d_tip_edge, h->d_obs_nodes,
-                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work};
+                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
+                    h->d_cp_fops, h->d_cp_ops, h->d_cp_mat_edge, h->d_cp_tip_edge, h->d_cp_obs_nodes, h->d_cp_op_edge, h->d_cp_expo, h->d_cp_flag,
+                    h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev2) (void)hipEventDestroy(h->ev2);
     if (h->ev3) (void)hipEventDestroy(h->ev3);
+    if (h->cp_ev0) (void)hipEventDestroy(h->cp_ev0);
+    if (h->cp_ev1) (void)hipEventDestroy(h->cp_ev1);
     for (int i = 0; i < 64; i++) for (int j = 0; j < 2; j++) if (h->evk[i][j]) (void)hipEventDestroy(h->evk[i][j]);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
@@ -1434,6 +1455,9 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LL_KERNEL_COUNT: *out = h->evk_count; h->evk_count = 0; return PLK_OK;
     case PLK_INFO_LL_KERNEL: *out = h->info_ll_kernel; return PLK_OK;
     case PLK_INFO_UPDOWN_KERNEL: *out = h->info_updown_kernel; return PLK_OK;
+    case PLK_INFO_CAT_POSTERIOR_KERNEL: *out = h->info_cat_posterior_kernel; return PLK_OK;
+    case PLK_INFO_CATEGORIES: *out = h->C; return PLK_OK;
+    case PLK_INFO_LAST_CAT_POSTERIOR_NS: *out = h->info_cat_posterior_ns; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && ((h->fmt_pt && h->fmt_kind == 1) || (h->vec_pt && h->fmt_kind == 4)) ? h->fpt.npairs : 0; return PLK_OK;
@@ -1523,6 +1547,7 @@ static int run_expm(plk_engine *h, bool post = false, bool need_dP = true)
     h->model_dirty = false;
     h->dp_valid = need_dP;
     h->tables_dirty = !post;
+    h->cp_tables_valid = false;
     return PLK_OK;
 }
 
@@ -1713,6 +1738,7 @@ static int build_program(plk_engine *h)
     h->prog_dirty = false;
     h->fmt_dirty = true;
     h->tables_dirty = true;
+    h->cp_kind = 0;
     return PLK_OK;
 }
 
@@ -3193,6 +3219,166 @@ extern "C" int plk_marginal(plk_engine *h, const int *node_mask, double *site_ou
 /* ====================================================================== */
 /* Edge-rate optimisation with the patterns resident      */
 /* ====================================================================== */
+
+/* ---------------------------------------------------------------------- */
+/* rate-category posteriors and posterior mean site rates (plk_catpost.h)  */
+/* ---------------------------------------------------------------------- */
+
+/* the k = 4 kernel: what use_fused asks of the C++ interpreter (its LDS image at one site per lane), C terms in registers */
+static bool use_catpost4(const plk_engine *h)
+{
+    if (h->opt_force_generic || h->k != 4 || h->pat_mode != 1 || h->C > PLK_CATPOST_REG_C) return false;
+    if (h->slots_needed > PLK_FUSED_SLOTS) return false;
+    return plk_fused_lds_bytes(h->pg, h->nchar, PLK_TILE) <= PLK_LDS_LIMIT;
+}
+
+template <int K>
+static void launch_catpost_generic(plk_engine *h, const CatPostGenArgs &a, unsigned grid)
+{
+    hipLaunchKernelGGL(k_catpost_generic<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a);
+}
+
+/* every output may be NULL; per-site outputs are host buffers ([S][C], [S], [S]), sums {hi, lo} pairs ([C][2], [2], [2]) */
+static int cat_posterior_impl(plk_engine *h, double *post_out, double *rate_out, double *site_ll_out,
+                              double *post_sums_out, double *rate_sum_out, double *ll_sum_out)
+{
+    if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_cat_posterior: tree, model and patterns must be set"; return PLK_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if (!h->cp_ev0) { HIPCHK(h, hipEventCreate(&h->cp_ev0)); HIPCHK(h, hipEventCreate(&h->cp_ev1)); }
+    HIPCHK(h, hipEventRecord(h->cp_ev0, h->stream));
+    /* the program and P are brought up to date the way plk_ll does it; the formats plk_ll has cached stay as they are */
+    if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
+    if (h->model_dirty) { if ((rc = run_expm(h, true, false))) return rc; }
+    const long S = h->S;
+    const int C = h->C, K = h->K, nops = (int)h->ops.size(), ntips = (int)h->tip_edge.size();
+    const bool k4 = use_catpost4(h);
+    const int kind = k4 ? 1 : 2;
+    const bool want_sums = post_sums_out || rate_sum_out || ll_sum_out;
+    if (h->cp_kind != kind) {
+        if (k4) {
+            plk_fused_build(h->N, h->pg, h->cpf);
+            std::vector<int> me = h->cpf.mat_edge, te = h->tip_edge;
+            me.push_back(-1);                            /* the spare matrix is all zeros */
+            te.push_back(-1);                            /* pseudo slot: the raw definitions */
+            if ((rc = dev_upload(h, &h->d_cp_fops, reinterpret_cast<const int4 *>(h->cpf.fops.data()), h->cpf.fops.size())) ||
+                (rc = dev_upload(h, &h->d_cp_mat_edge, me.data(), me.size())) ||
+                (rc = dev_upload(h, &h->d_cp_tip_edge, te.data(), te.size())) ||
+                (rc = dev_upload(h, &h->d_cp_obs_nodes, h->obs_nodes.data(), h->obs_nodes.size()))) return rc;
+        } else {
+            if ((rc = dev_upload(h, &h->d_cp_ops, reinterpret_cast<const int2 *>(h->ops.data()), h->ops.size())) ||
+                (rc = dev_upload(h, &h->d_cp_op_edge, h->op_edge.data(), h->op_edge.size()))) return rc;
+        }
+        h->cp_kind = kind;
+        h->cp_tables_valid = false;
+    }
+    if (!h->d_cp_flag) { if ((rc = dev_alloc(h, &h->d_cp_flag, 1))) return rc; }
+    HIPCHK(h, hipMemsetAsync(h->d_cp_flag, 0, sizeof(int), h->stream));
+    /* outputs: [C][S] posteriors, [S] rates, [S] log likelihoods */
+    if ((rc = dev_reserve(h, &h->d_cp_out, &h->cp_out_cap, (size_t)(C + 2) * S))) return rc;
+    double *d_post = h->d_cp_out, *d_rate = h->d_cp_out + (size_t)C * S, *d_ll = d_rate + S;
+    const unsigned grid = k4 ? (unsigned)((S + PLK_TILE - 1) / PLK_TILE) : (unsigned)((S + GEN_BLOCK - 1) / GEN_BLOCK);
+    const int rows = C + 2;
+    if (want_sums) { if ((rc = dev_reserve(h, &h->d_cp_partial, &h->cp_partial_cap, (size_t)rows * grid + rows))) return rc; }
+    dd *d_sums = h->d_cp_partial, *d_part = want_sums ? h->d_cp_partial + rows : nullptr;
+    if (k4) {
+        const int nmat1 = (int)h->cpf.mat_edge.size() + 1;
+        if ((rc = dev_reserve(h, &h->d_cp_PS, &h->cp_ps_cap, (size_t)C * nmat1 * 16))) return rc;
+        if ((rc = dev_reserve(h, &h->d_cp_tip, &h->cp_tip_cap, (size_t)C * (ntips + 1) * h->nchar * 4))) return rc;
+        if (!h->cp_tables_valid) {
+            /* the matrix stream and the tip tables of the current P: rebuilt after K1 ran or the program changed */
+            hipLaunchKernelGGL(k_build_stream, dim3(nmat1, C), dim3(64), 0, h->stream, 4, 4, h->E, nmat1, h->d_cp_mat_edge, h->d_P, h->d_cp_PS);
+            hipLaunchKernelGGL(k_build_tip, dim3(ntips + 1, C), dim3(64), 0, h->stream,
+                               h->E, ntips + 1, h->nchar, h->d_cp_tip_edge, h->d_Pdd, h->d_defs, h->d_cp_tip);
+            HIPCHK(h, hipGetLastError());
+            h->cp_tables_valid = true;
+        }
+        CatPostArgs a;
+        a.f.S = S; a.f.Spad = h->Spad; a.f.C = C; a.f.nops = nops; a.f.nmat = nmat1 - 1;
+        a.f.ntips = ntips + 1; a.f.nchar = h->nchar; a.f.nobs = (int)h->obs_nodes.size();
+        a.f.ops = h->d_cp_fops; a.f.PS = h->d_cp_PS; a.f.tip = h->d_cp_tip;
+        a.f.codes = h->d_codes; a.f.obs_nodes = h->d_cp_obs_nodes; a.f.defs = h->d_defs;
+        a.f.cat_prior = h->d_cat_prior; a.f.root_w = h->d_root_w; a.f.w = h->d_w;
+        a.f.site_ll = d_ll; a.f.partial = nullptr;
+        a.f.root_mode = h->root_mode; a.f.first_row = h->cpf.first_row;
+        a.cat_rates = h->d_cat_rates; a.post = d_post; a.rate = d_rate; a.partial = d_part; a.zero_flag = h->d_cp_flag;
+        const size_t lds = plk_fused_lds_bytes(h->pg, h->nchar, PLK_TILE);
+        const int D = h->slots_needed <= 4 ? 4 : (h->slots_needed <= 8 ? 8 : 16);
+        /* replay the interpreter's fetches and LDS addresses on the host before launching (plk_program.h) */
+        const std::string bad = plk_fused_check_cpp(h->N, h->pg, h->cpf, h->nchar, D, 1, lds);
+        if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
+        if (D == 4) hipLaunchKernelGGL(k_ll_fused4_catpost<4>, dim3(grid), dim3(PLK_TILE), lds, h->stream, a);
+        else if (D == 8) hipLaunchKernelGGL(k_ll_fused4_catpost<8>, dim3(grid), dim3(PLK_TILE), lds, h->stream, a);
+        else hipLaunchKernelGGL(k_ll_fused4_catpost<16>, dim3(grid), dim3(PLK_TILE), lds, h->stream, a);
+        h->info_cat_posterior_kernel = 1;
+    } else {
+        if ((rc = dev_reserve(h, &h->d_cp_PS, &h->cp_ps_cap, (size_t)C * std::max(nops, 1) * K * K))) return rc;
+        if ((rc = dev_reserve(h, &h->d_cp_expo, &h->cp_expo_cap, (size_t)C * S))) return rc;
+        const int nslots = std::max(h->slots_needed, 1);
+        if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)nslots * h->k * S))) return rc;
+        if (nops > 0 && !h->cp_tables_valid)
+            hipLaunchKernelGGL(k_build_stream, dim3(nops, C), dim3(K * K >= 256 ? 256 : 64), 0, h->stream,
+                               h->k, K, h->E, nops, h->d_cp_op_edge, h->d_P, h->d_cp_PS);
+        h->cp_tables_valid = true;
+        CatPostGenArgs a;
+        a.g.S = S; a.g.Spad = h->Spad; a.g.k = h->k; a.g.C = C; a.g.nops = nops; a.g.nchar = h->nchar;
+        a.g.pat_mode = h->pat_mode; a.g.root_mode = h->root_mode; a.g.ops = h->d_cp_ops; a.g.PS = h->d_cp_PS;
+        a.g.codes = h->d_codes; a.g.defs = h->d_defs; a.g.B = h->d_B; a.g.cat_prior = h->d_cat_prior;
+        a.g.root_w = h->d_root_w; a.g.w = h->d_w; a.g.slots = h->d_slots; a.g.site_ll = d_ll; a.g.partial = nullptr;
+        a.cat_rates = h->d_cat_rates; a.post = d_post; a.expo = h->d_cp_expo; a.rate = d_rate; a.partial = d_part; a.zero_flag = h->d_cp_flag;
+        switch (K) {
+        case 2: launch_catpost_generic<2>(h, a, grid); break;
+        case 4: launch_catpost_generic<4>(h, a, grid); break;
+        case 8: launch_catpost_generic<8>(h, a, grid); break;
+        case 16: launch_catpost_generic<16>(h, a, grid); break;
+        case 20: launch_catpost_generic<20>(h, a, grid); break;
+        case 32: launch_catpost_generic<32>(h, a, grid); break;
+        case 61: launch_catpost_generic<61>(h, a, grid); break;
+        default: launch_catpost_generic<64>(h, a, grid); break;
+        }
+        h->info_cat_posterior_kernel = 2;
+    }
+    HIPCHK(h, hipGetLastError());
+    if (want_sums) {
+        /* fixed-order double-double sums of the workgroups' partials, one block per output row */
+        hipLaunchKernelGGL(k_dd_final, dim3(rows), dim3(256), 0, h->stream, (int)grid, d_part, d_sums);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipEventRecord(h->cp_ev1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    {
+        float ms = 0;
+        HIPCHK(h, hipEventElapsedTime(&ms, h->cp_ev0, h->cp_ev1));
+        h->info_cat_posterior_ns = (long)(ms * 1e6);
+    }
+    if (want_sums) {
+        int flag = 0;
+        HIPCHK(h, hipMemcpy(&flag, h->d_cp_flag, sizeof(int), hipMemcpyDeviceToHost));
+        if (flag) { h->err = "plk_cat_posterior: site likelihood zero at a site of non-zero weight, the sums are undefined"; return PLK_E_ARG; }
+        std::vector<dd> host(rows);
+        HIPCHK(h, hipMemcpy(host.data(), d_sums, rows * sizeof(dd), hipMemcpyDeviceToHost));
+        if (post_sums_out) for (int c = 0; c < C; c++) { post_sums_out[2 * c] = host[c].hi; post_sums_out[2 * c + 1] = host[c].lo; }
+        if (rate_sum_out) { rate_sum_out[0] = host[C].hi; rate_sum_out[1] = host[C].lo; }
+        if (ll_sum_out) { ll_sum_out[0] = host[C + 1].hi; ll_sum_out[1] = host[C + 1].lo; }
+    }
+    if (post_out) { if ((rc = copy_site_rows(h, (size_t)C, S, 0, d_post, post_out))) return rc; }
+    if (rate_out) HIPCHK(h, hipMemcpy(rate_out, d_rate, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    if (site_ll_out) HIPCHK(h, hipMemcpy(site_ll_out, d_ll, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    return PLK_OK;
+}
+
+extern "C" int plk_cat_posterior_ll(plk_engine *h, double *post_out, double *rate_out, double *site_ll_out,
+                                    double *post_sums_out, double *rate_sum_out, double *ll_sum_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    return cat_posterior_impl(h, post_out, rate_out, site_ll_out, post_sums_out, rate_sum_out, ll_sum_out);
+}
+
+extern "C" int plk_cat_posterior(plk_engine *h, double *post_out, double *rate_out, double *post_sums_out, double *rate_sum_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    return cat_posterior_impl(h, post_out, rate_out, nullptr, post_sums_out, rate_sum_out, nullptr);
+}
 
 static int fit_objective(plk_engine *h, const std::vector<double> &rates, long double *ll_out)
 {

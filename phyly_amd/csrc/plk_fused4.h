@@ -103,7 +103,8 @@ __device__ __forceinline__ void stack_popmul(int d, int j, double &c0, double &c
     "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127"
 
 /* one traversal op: OUT = f(IN) for the NS sites of this lane (IN and OUT are distinct
- * register sets; the caller alternates them so that no result has to be copied back) */
+ * register sets; the caller alternates them so that no result has to be copied back).
+ * plk_catpost.h carries the same op set at NS = 1 (PLK_CP_EXEC): the two must change together. */
 #define PLK_FUSED_EXEC(OX, OY, OZ, IN, OUT)                                                              \
     do {                                                                                                  \
         const int code_ = (OX) & 0xff;                                                                    \

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PHYLY_AMD_LIB") or os.path.join(_HERE, "csrc", "libar
 HOST, DEVICE = 0, 1
 ROOT_NONE, ROOT_CUSTOM, ROOT_UNIFORM, ROOT_EQUILIBRIUM = 1, 2, 3, 4
 INFO_LL_KERNEL, INFO_STACK_SLOTS, INFO_PROGRAM_OPS, INFO_LL_KERNEL_NS, INFO_LL_TOTAL_NS, INFO_LL_KERNEL_NS_SUM, INFO_LL_KERNEL_COUNT, INFO_LL_VARIANT, INFO_PAIR_TABLES, INFO_LL_EXEC_FLOPS, \
-    INFO_UPDOWN_KERNEL = range(11)
+    INFO_UPDOWN_KERNEL, INFO_CAT_POSTERIOR_KERNEL, INFO_CATEGORIES, INFO_CAT_POSTERIOR_NS = range(14)
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 COEF_PRIOR, COEF_PRIOR_RATE_EDGE, COEF_PRIOR_RATE = 0, 1, 2
 FIT_EM, FIT_LBFGS = 0, 1
@@ -66,6 +66,8 @@ def load_library():
     lib.plk_hess.argtypes = [vp, vp]
     lib.plk_second_order.argtypes = [vp, vp, vp]
     lib.plk_solve_second_order.argtypes = [ci, vp, vp, vp, vp, vp]
+    lib.plk_cat_posterior.argtypes = [vp, vp, vp, vp, vp]
+    lib.plk_cat_posterior_ll.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.plk_get_transition_matrices.argtypes = [vp, vp]
     lib.plk_get_info.argtypes = [vp, ci, ctypes.POINTER(cl)]
     lib.plk_set_option.argtypes = [vp, ci, cl]
@@ -260,6 +262,22 @@ class Engine:
         out = np.zeros((self.E, self.E, 2))
         self._check(self._lib.plk_second_order(self._h, _ptr(grad), _ptr(out)))
         return grad[:, 0] + grad[:, 1], out[..., 0] + out[..., 1]
+
+    def cat_posterior(self, per_site=True, want_sums=True, want_ll=False):
+        """rate-category posteriors and posterior mean site rates (include/plk.h:plk_cat_posterior)
+        -> (post [S][C] or None, rate [S] or None, post_sums [C][2] or None, rate_sum (hi, lo) or None);
+        want_ll appends the by-products (site_ll [S] or None, ll_sum (hi, lo) or None)"""
+        post = np.empty((self.S, self.C)) if per_site else None
+        rate = np.empty(self.S) if per_site else None
+        psum = np.zeros((self.C, 2)) if want_sums else None
+        rsum = np.zeros(2) if want_sums else None
+        if not want_ll:
+            self._check(self._lib.plk_cat_posterior(self._h, _ptr(post), _ptr(rate), _ptr(psum), _ptr(rsum)))
+            return post, rate, psum, (tuple(rsum) if want_sums else None)
+        sll = np.empty(self.S) if per_site else None
+        lsum = np.zeros(2) if want_sums else None
+        self._check(self._lib.plk_cat_posterior_ll(self._h, _ptr(post), _ptr(rate), _ptr(sll), _ptr(psum), _ptr(rsum), _ptr(lsum)))
+        return post, rate, psum, (tuple(rsum) if want_sums else None), sll, (tuple(lsum) if want_sums else None)
 
     def transition_matrices(self):
         P = np.empty((self.C, self.E, self.k, self.k))

@@ -1,0 +1,120 @@
+"""Expected values and workloads for the rate-category posterior tests (test infrastructure; may use oracle/).
+
+The oracle has no posterior query.  Its per-site log likelihood under ONE category is exact enough to build one: for each
+category c the prepared workspace is cut down to that category (C = 1, its P, prior 1), which gives log L_{s,c}; the
+posteriors are the soft-max of log prior_c + log L_{s,c}, taken in long double."""
+import ctypes
+
+import numpy as np
+
+from phyly_amd import engine as _E, synth
+
+
+def rtol(E, k, C):
+    """the bound of the issue: every L_{s,c} is a sum of products of non-negative numbers, each of the E edges adds one
+    k-term dot product whose P entries are good to a few ulp, the posterior is a ratio of two such quantities"""
+    return 4.0 * (E * (k + 8) + C + 8) * 2.0 ** -53
+
+
+def category_log_lhoods(oracle, m, w, precise=2, nthreads=0, **data):
+    """log L_{s,c} as [S][C] long double (data: B=... or codes=..., defs=... as for oracle.site_ll)"""
+    C = int(w["C"])
+    Pq = np.asarray(w["Pq"]).reshape(C, -1)
+    cols = []
+    for c in range(C):
+        wc = dict(w, C=1, P=np.ascontiguousarray(w["P"][c:c + 1]), Pq=np.ascontiguousarray(Pq[c]), cat_prior=np.ones(1))
+        ll, _ = oracle.site_ll(m, wc, precise=precise, nthreads=nthreads, **data)
+        cols.append(np.asarray(ll, dtype=np.longdouble))
+    return np.stack(cols, axis=1)
+
+
+def posteriors(oracle, m, w, precise=2, nthreads=0, **data):
+    """-> (post [S][C], rate [S], site_ll [S]) in long double; a prior of 0 gives a posterior of exactly 0"""
+    logL = category_log_lhoods(oracle, m, w, precise=precise, nthreads=nthreads, **data)
+    prior = np.asarray(w["cat_prior"], dtype=np.longdouble)
+    with np.errstate(divide="ignore"):
+        t = np.log(prior)[None, :] + logL
+    mx = np.max(t, axis=1, keepdims=True)
+    x = np.exp(t - mx)
+    tot = np.sum(x, axis=1, keepdims=True)
+    post = x / tot
+    rate = post @ np.asarray(w["cat_rates"], dtype=np.longdouble)
+    return post, rate, (mx + np.log(tot))[:, 0]
+
+
+class MixtureWorkload(synth.Workload):
+    """synth.Workload on one of its k = 4 models with the rate mixture replaced: None, a gamma_rate_mixture dict
+    (invariable_prior allowed) or a custom (rates, prior) pair, which goes through the product's K0 as rate_mixture"""
+
+    def __init__(self, T, model, tree, seed, mixture="model", k=4):
+        synth.Workload.__init__(self, T=T, k=k, tree=tree, model=model, seed=seed)
+        if mixture != "model":
+            self.mixture = mixture
+
+    def prepare(self):
+        if self.k0 is None and isinstance(self.mixture, tuple):
+            lib = _E.load_library()
+            rates, prior = (np.ascontiguousarray(v, dtype=np.float64) for v in self.mixture)
+            dp = ctypes.POINTER(ctypes.c_double)
+            mix = synth._K0Mixture()
+            mix.mode, mix.n = 2, len(rates)
+            mix.rates, mix.prior = rates.ctypes.data_as(dp), prior.ctypes.data_as(dp)
+            Q = np.ascontiguousarray(self.Q, dtype=np.float64)
+            C = len(rates)
+            out = dict(C=C, cat_rates=np.zeros(C), cat_prior=np.zeros(C), pi=np.zeros(self.k), Qn=np.zeros((self.k, self.k)),
+                       Qn_lo=np.zeros((self.k, self.k)))
+            lib.arbplf_k0_prepare.argtypes = [ctypes.c_int, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                              ctypes.POINTER(synth._K0Mixture), dp, dp, dp, dp, dp]
+            rc = lib.arbplf_k0_prepare(self.k, Q.ctypes.data_as(dp), 1, 1.0, 1, ctypes.byref(mix),
+                                       *(out[n].ctypes.data_as(dp) for n in ("cat_rates", "cat_prior", "pi", "Qn", "Qn_lo")))
+            if rc != C:
+                raise RuntimeError("arbplf_k0_prepare failed")
+            self.k0 = out
+        return synth.Workload.prepare(self)
+
+    def json_model(self, codes_host):
+        if not isinstance(self.mixture, tuple):
+            return synth.Workload.json_model(self, codes_host)
+        mix, self.mixture = self.mixture, None
+        try:
+            md = synth.Workload.json_model(self, codes_host)
+        finally:
+            self.mixture = mix
+        md["rate_mixture"] = dict(rates=[float(v) for v in mix[0]], prior=[float(v) for v in mix[1]])
+        return md
+
+
+ZERO_PRIOR_8 = ([0.02, 0.1, 0.3, 0.6, 1.0, 1.6, 2.5, 4.0], [0.05, 0.1, 0.15, 0.0, 0.25, 0.2, 0.15, 0.1])
+
+# the small engine cases of the issue: name -> (workload arguments, expected C)
+SMALL = {
+    "hky85": (dict(T=12, model="hky85", tree="balanced", seed=71, mixture=None), 1),
+    "gtr_g4": (dict(T=14, model="gtr_g4", tree="yule", seed=72), 4),
+    "gtr_g4_i": (dict(T=14, model="gtr_g4", tree="yule", seed=73, mixture=dict(gamma_shape=0.7, gamma_categories=4, invariable_prior=0.2)), 5),
+    "custom8_zero_prior": (dict(T=11, model="gtr_g4", tree="yule", seed=74, mixture=ZERO_PRIOR_8), 8),
+}
+
+
+def small_workload(name):
+    return MixtureWorkload(**SMALL[name][0])
+
+
+def oracle_for(oracle, wl, codes, precise=2, nthreads=0):
+    """(m, w, post, rate, site_ll) of a workload and its codes[N][S]"""
+    m = oracle.parse_model(wl.json_model(codes[:, :1]))
+    w = oracle.prepare(m)
+    post, rate, sll = posteriors(oracle, m, w, precise=precise, nthreads=nthreads,
+                                 codes=np.ascontiguousarray(codes.T), defs=wl.defs)
+    return m, w, post, rate, sll
+
+
+def document_table(oracle, doc, what):
+    """the table arbplf-cat-posterior ("cat_posterior") or arbplf-site-rate ("site_rate") must print for a document"""
+    m = oracle.parse_model(doc["model_and_data"])
+    w = oracle.prepare(m)
+    r_site = oracle._red(doc, "site_reduction", m.S, "site")
+    post, rate, _ = posteriors(oracle, m, w, B=m.B)
+    if what == "site_rate":
+        return oracle._table(rate, [r_site], ["site"])
+    r_cat = oracle._red(doc, "category_reduction", int(w["C"]), "category")
+    return oracle._table(post, [r_site, r_cat], ["site", "category"])
