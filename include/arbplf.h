@@ -54,11 +54,17 @@ char *arbplf_newton_update_string(void *userdata, const char *s_in, int *retcode
  * without a mixture has one category: posterior 1, rate 1. */
 char *arbplf_cat_posterior_string(void *userdata, const char *s_in, int *retcode);
 char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode);
+/* Gradient of the site-aggregated log likelihood in the entries of rate_matrix (the reference has no such command; it
+ * differentiates in the edge rates only).  model_and_data plus a site_reduction whose aggregation is mandatory ("sum",
+ * "avg" or a weight array; selection optional); any other key is rejected.  Columns ["first_state", "second_state",
+ * "value"]: d/dq_ij for every ordered pair i != j, row-major, the diagonal being minus the row sums; the rate divisor
+ * (a number or "equilibrium_exit_rate") and an equilibrium root prior are differentiated through. */
+char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *retcode);
 
 /* Host-only validation of an input document (JSON grammar, model_and_data,
  * reductions) exactly as the corresponding query would perform it, without
  * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
- * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate".  0 = accepted. */
+ * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate" | "rate_matrix_deriv".  0 = accepted. */
 int arbplf_validate_string(const char *what, const char *s_in);
 
 /* stdin -> stdout filter used by the CLI mains (run_string_script,

@@ -22,6 +22,8 @@
  *   plk_marginal        <- marginal _nd_accum_update + evaluate_site_forward +
  *                          evaluate_site_marginal_unnormalized
  *                          (src/arbplfmarginal.c:111-264)
+ * and add what the reference does not have: plk_cat_posterior (rate-category posteriors), plk_edge_pair_sums and
+ * plk_rate_matrix_sens (site-summed outer products per edge; the gradient of the log likelihood in the rate matrix).
  *
  * Conventions: every function returns 0 on success and a nonzero PLK_E_* code
  * on failure (plk_last_error() gives the text).  The caller owns all buffers
@@ -181,6 +183,47 @@ int plk_edge_expect(plk_engine *h, const double *L_hi, const double *L_lo, int c
  * em-update's two expectations, dwell per state, trans per state pair. */
 int plk_edge_expect_multi(plk_engine *h, int nL, const double *L_hi, const double *L_lo, int coef_mode,
                           const int *edge_mask, double *site_out, double *sums_out);
+/*
+ * Edge pair sums (the reference has no such query).  For every category c and edge e = (a -> b), with fe the vector above
+ * the edge (forward vector of a, its observation and the messages of b's siblings) and L_b the vector below it:
+ *     W[c][e][i][j] = sum_s w_s prior_c fe_{s,c,e}[i] L_{s,c,b}[j] / lhood_s
+ *     R[c][i]       = sum_s w_s prior_c (B_root o messages)_{s,c}[i] / lhood_s        (root vector without the root prior)
+ * Every site-summed edge form is a contraction of W: sum_s w_s x_{s,e} = sum_c <W[c][e], M_{c,e}> for dP or a scaled
+ * Frechet matrix M, and <W[c][e], P[c][e]> = sum_s w_s post_{s,c} on every edge.  One down pass and one up pass
+ * (plk_pairsums.h); the partial sums live on a fixed grid, so their storage does not depend on S, and the order of every
+ * sum is fixed (two calls give the same bits).  Preconditions as for plk_deriv; edge_mask: NULL (all) or E ints.
+ * W_out: [C][E][k][k][2] double-double entries in CSR edge order, masked edges exactly 0; root_out: NULL or [C][k][2].
+ * A site of likelihood 0 with a non-zero weight makes the call fail with PLK_E_ARG ("site likelihood zero"); with weight
+ * 0 it contributes nothing.  Other queries give the same bits whether or not this call ran in between.
+ */
+int plk_edge_pair_sums(plk_engine *h, const int *edge_mask, double *W_out, double *root_out);
+
+/*
+ * Gradient of sum_s w_s ll_s in the normalised rate matrix, all k^2 entries taken as independent:
+ *     G[i][j] = d/dQn[i][j] = sum_{c,e} s (F_{c,e}(W[c][e]^T))^T,   s = cat_rate_c * edge_rate_e
+ * (F the Frechet matrix of plk_edge_expect; the adjoint identity <W, F(L)> = <L, F(W^T)^T> turns k^2 directions into one
+ * per (category, edge)), and root_out[i] = d/droot_w[i] = sum_c R[c][i].  One down pass, one up pass, one Frechet K1 run.
+ * G_out: [k][k][2], root_out: NULL or [k][2], double-double.  plk_rate_matrix_chain takes both to the user's parameters.
+ */
+int plk_rate_matrix_sens(plk_engine *h, double *G_out, double *root_out);
+
+/*
+ * The chain rule from (G, root) of plk_rate_matrix_sens to the raw off-diagonal entries q_ij of the user's rate_matrix;
+ * host only, no engine and no GPU involved, IEEE binary128 rounded once.  The diagonal of rate_matrix is ignored (it is
+ * minus the row sums, as at parse time).  With d the divisor, Qn = Q / d, pi the stationary distribution and
+ * Z = (1 pi^T - Q)^-1:
+ *   fixed divisor           d/dq_ij = (G_ij - G_ii) / d
+ *   PLK_DIVISOR_EXIT_RATE   d = sum_m pi_m sum_{n != m} q_mn; adds (df/dd)(dd/dq_ij) with df/dd = -(1/d) sum_mn G_mn Qn_mn,
+ *                           dd/dq_ij = pi_i + sum_m (dpi_m/dq_ij)(-Q_mm),  dpi/dq_ij = pi_i (e_j - e_i)^T Z
+ *   PLK_ROOT_EQUILIBRIUM    adds sum_m root_m dpi_m/dq_ij (custom, uniform and no root prior do not depend on Q)
+ * rate_matrix: [k][k]; divisor: the number (ignored for PLK_DIVISOR_EXIT_RATE); G: [k][k][2]; root: [k][2], NULL unless
+ * root_mode is PLK_ROOT_EQUILIBRIUM; grad_out: [k][k], diagonal 0.  err / errlen: NULL / 0 or a buffer for the diagnostic.
+ * Returns PLK_E_ARG for bad arguments and for a reducible rate matrix when pi is needed ("rate matrix is reducible").
+ */
+enum { PLK_DIVISOR_NUMBER = 0, PLK_DIVISOR_EXIT_RATE = 1 };
+int plk_rate_matrix_chain(int k, const double *rate_matrix, int divisor_mode, double divisor, int root_mode,
+                          const double *G, const double *root, double *grad_out, char *err, size_t errlen);
+
 /* the scaled Frechet matrices coef_{c,e} * F_{c,e} themselves, [C][E][k][k] host (tests) */
 int plk_get_frechet_matrices(plk_engine *h, const double *L_hi, const double *L_lo, int coef_mode,
                              double *F_out);
@@ -270,8 +313,13 @@ enum {
     PLK_INFO_CAT_POSTERIOR_KERNEL = 11, /* kernel of the last plk_cat_posterior: 0 = none yet, 1 = k = 4 register kernel
                                        (compact codes, at most 8 categories), 2 = generic */
     PLK_INFO_CATEGORIES = 12,       /* rate categories of the model (0 before plk_set_model) */
-    PLK_INFO_LAST_CAT_POSTERIOR_NS = 13 /* HIP-event time of the device work of the last plk_cat_posterior (K1 when the rates
+    PLK_INFO_LAST_CAT_POSTERIOR_NS = 13, /* HIP-event time of the device work of the last plk_cat_posterior (K1 when the rates
                                        changed, tables, kernel, sums); for tools/time_cat_posterior.py */
+    PLK_INFO_PAIR_SUMS_KERNEL = 14, /* up pass of the last plk_edge_pair_sums / plk_rate_matrix_sens: 0 = none yet, 1 = the k = 4
+                                       kernel (compact codes, at most 4 categories), 2 = generic */
+    PLK_INFO_LAST_QUERY_NS = 15     /* HIP-event time from the first to the last device operation of the last plk_deriv,
+                                       plk_edge_expect(_multi), plk_edge_pair_sums or plk_rate_matrix_sens (0 when it could not
+                                       be taken); for tools/time_rate_matrix_deriv.py */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -341,6 +389,10 @@ int plk_group_edge_expect_multi(plk_group *g, int nL, const double *L_hi, const 
                                 const int *edge_mask, double *site_out, double *sums_out);
 /* post_out [S][C] and rate_out [S] at their global positions; post_sums_out [C][2], rate_sum_out [2] (any may be NULL) */
 int plk_group_cat_posterior(plk_group *g, double *post_out, double *rate_out, double *post_sums_out, double *rate_sum_out);
+/* W_out [C][E][k][k][2], root_out NULL or [C][k][2]; G_out [k][k][2], root_out NULL or [k][2]: partial sums of the engines
+ * added in engine order (long double), as for the other sums */
+int plk_group_edge_pair_sums(plk_group *g, const int *edge_mask, double *W_out, double *root_out);
+int plk_group_rate_matrix_sens(plk_group *g, double *G_out, double *root_out);
 int plk_group_hess(plk_group *g, double *hess_sums_out);
 int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out);   /* either may be NULL */
 

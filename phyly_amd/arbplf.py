@@ -106,6 +106,12 @@ def arbplf_site_rate(s):
     return _call("arbplf_site_rate", s)
 
 
+def arbplf_rate_matrix_deriv(s):
+    """gradient of the site-aggregated log likelihood in the off-diagonal entries of rate_matrix (no counterpart in the
+    reference): columns first_state, second_state, value"""
+    return _call("arbplf_rate_matrix_deriv", s)
+
+
 def _out_of_scope(name):
     def f(s):
         raise RuntimeError("arbplf likelihood error: %s is outside the MI355X hot path of this build" % name)

@@ -236,7 +236,7 @@ static int check_finite(double v, const char *what)
 }
 
 /* _parse of the drivers: kind 0 ll, 1 deriv, 2 marginal, 3 dwell, 4 trans, 5 em-update, 6 the second-order family,
- * 7 cat-posterior, 8 site-rate (no counterpart in the reference: its reduction grammar, its table layout)
+ * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv (no counterpart in the reference: its reduction grammar, its table layout)
  * (src/arbplfll.c:250-288, src/arbplfderiv.c:445-493, src/arbplfmarginal.c:348-405,
  *  src/arbplfdwell.c:507-566, src/arbplftrans.c:553-614, src/arbplfem.c:505-545) */
 static int query_parse(query *q, int kind, const jval *root)
@@ -262,8 +262,8 @@ static int query_parse(query *q, int kind, const jval *root)
                                                j_get(root, "trans_reduction"))) return -1;
     /* the category axis has the length the mixture gives it (Gamma categories first, the invariable one last) */
     if (kind == 7 && host_reduction_parse(&q->r_a, arbplf_k0_category_count(&q->m.mix), "category", j_get(root, "category_reduction"))) return -1;
-    if (kind == 6 && !j_get(root, "site_reduction")) { fprintf(stderr, "error: site_reduction is required\n"); return -1; }
-    if ((kind == 5 || kind == 6) && q->r_site.agg_mode == AGG_NONE) { fprintf(stderr, "error: aggregation over sites is required\n"); return -1; }
+    if ((kind == 6 || kind == 9) && !j_get(root, "site_reduction")) { fprintf(stderr, "error: site_reduction is required\n"); return -1; }
+    if ((kind == 5 || kind == 6 || kind == 9) && q->r_site.agg_mode == AGG_NONE) { fprintf(stderr, "error: aggregation over sites is required\n"); return -1; }
     return 0;
 }
 
@@ -862,6 +862,57 @@ done:
     return rc;
 }
 
+/* ------------------------------------------------------------------ rate-matrix-deriv */
+/* arbplf-rate-matrix-deriv: d(site-aggregated log likelihood) / d(rate_matrix entry), every ordered pair of distinct
+ * states, row-major.  The engine gives the gradient in the normalised matrix and in the root weights from one down
+ * pass, one up pass and one Frechet run (plk_rate_matrix_sens); plk_rate_matrix_chain takes them through the divisor,
+ * the stationary distribution and the equilibrium root prior to the raw entries. */
+static int run_rate_matrix_deriv(const jval *root, jbuf *out)
+{
+    query q;
+    int rc = -1;
+    double *G = NULL, *rt = NULL, *grad = NULL;
+    query_init(&q);
+    if (query_parse(&q, 9, root)) goto done;
+    if (query_prepare(&q)) goto done;
+    const int k = q.m.k;
+    G = calloc((size_t)k * k * 2 + 2, sizeof(double));
+    rt = calloc((size_t)k * 2 + 2, sizeof(double));
+    grad = calloc((size_t)k * k + 1, sizeof(double));
+    if (!G || !rt || !grad) goto done;
+    if (q.U > 0) {
+        if (plk_group_rate_matrix_sens(q.eng, G, rt)) {
+            const char *msg = plk_group_last_error(q.eng);
+            if (strstr(msg, "site likelihood zero")) check_finite(NAN, "the rate matrix gradient");
+            else fprintf(stderr, "error: %s\n", msg);
+            goto done;
+        }
+        char err[160];
+        if (plk_rate_matrix_chain(k, q.m.rate_matrix, q.m.use_equilibrium_divisor ? PLK_DIVISOR_EXIT_RATE : PLK_DIVISOR_NUMBER, q.m.rate_divisor,
+                                  q.m.root_mode, G, rt, grad, err, sizeof err)) {
+            fprintf(stderr, "error: %s\n", err[0] ? err : "the chain rule of the rate matrix gradient failed");
+            goto done;
+        }
+    }
+    jbuf_puts(out, "{\"columns\": [\"first_state\", \"second_state\", \"value\"], \"data\": [");
+    int first = 1;
+    for (int i = 0; i < k; i++)
+        for (int j = 0; j < k; j++) {
+            if (i == j) continue;
+            double v = clean((long double)grad[(size_t)i * k + j] / q.div_site);
+            if (check_finite(v, "the rate matrix gradient")) goto done;
+            if (!first) jbuf_puts(out, ", ");
+            first = 0;
+            jbuf_puts(out, "["); jbuf_int(out, i); jbuf_puts(out, ", "); jbuf_int(out, j); jbuf_puts(out, ", "); jbuf_real(out, v); jbuf_puts(out, "]");
+        }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(G); free(rt); free(grad);
+    query_clear(&q);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ string API */
 static char *string_hom(int (*run)(const jval *, jbuf *), void *userdata, const char *s_in, int *retcode)
 {
@@ -901,10 +952,11 @@ char *arbplf_newton_delta_string(void *userdata, const char *s_in, int *retcode)
 char *arbplf_newton_update_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_newton_update, userdata, s_in, retcode); }
 char *arbplf_cat_posterior_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_cat_posterior, userdata, s_in, retcode); }
 char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_site_rate, userdata, s_in, retcode); }
+char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_rate_matrix_deriv, userdata, s_in, retcode); }
 
 /* Host-only validation (JSON grammar, model, reductions); no GPU is touched.
  * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta", "newton_update",
- * "cat_posterior" or "site_rate".
+ * "cat_posterior", "site_rate" or "rate_matrix_deriv".
  * Returns 0 when the input would be accepted. */
 int arbplf_validate_string(const char *what, const char *s_in)
 {
@@ -912,7 +964,7 @@ int arbplf_validate_string(const char *what, const char *s_in)
     int kind = !strcmp(what, "ll") ? 0 : !strcmp(what, "deriv") ? 1 : !strcmp(what, "marginal") ? 2 :
                !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 :
                (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 :
-               !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : -1;
+               !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : !strcmp(what, "rate_matrix_deriv") ? 9 : -1;
     if (kind < 0 || !s_in) return -1;
     json_doc *doc = json_doc_parse(s_in, err, sizeof err);
     if (!doc) { fprintf(stderr, "%s\n", err); return -1; }

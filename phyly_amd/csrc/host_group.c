@@ -378,6 +378,64 @@ int plk_group_cat_posterior(plk_group *g, double *post_out, double *rate_out, do
     return rc;
 }
 
+/* edge pair sums and the gradient in the rate matrix: sums only.  Weak for the same reason as above. */
+extern int plk_edge_pair_sums(plk_engine *h, const int *edge_mask, double *W_out, double *root_out) __attribute__((weak));
+extern int plk_rate_matrix_sens(plk_engine *h, double *G_out, double *root_out) __attribute__((weak));
+
+typedef struct { int sens; const int *mask; size_t n_main, n_root; int want_root; double *part; } ps_ctx;
+
+static int job_pair_sums(plk_group *g, int i, void *p)
+{
+    ps_ctx *c = p;
+    double *mainp = c->part + (size_t)i * (c->n_main + c->n_root) * 2;
+    double *rootp = c->want_root ? mainp + 2 * c->n_main : NULL;
+    if (g->s0[i + 1] == g->s0[i]) return PLK_OK;           /* an engine without sites adds nothing */
+    return c->sens ? plk_rate_matrix_sens(g->eng[i], mainp, rootp) : plk_edge_pair_sums(g->eng[i], c->mask, mainp, rootp);
+}
+
+static int group_pair_sums(plk_group *g, int sens, const int *edge_mask, double *main_out, double *root_out)
+{
+    if (!g || !main_out) return PLK_E_ARG;
+    if (!plk_edge_pair_sums || !plk_rate_matrix_sens || !plk_get_info) return fail(g, PLK_E_UNSUPPORTED, "plk_group: the engine has no plk_edge_pair_sums");
+    if (!g->have_patterns) return fail(g, PLK_E_ARG, "plk_group: tree, model and patterns must be set");
+    long C = 0;
+    if (plk_get_info(g->eng[0], PLK_INFO_CATEGORIES, &C) || C < 1) return fail(g, PLK_E_ARG, "plk_group: the model is not set");
+    const size_t kk = (size_t)g->k * g->k;
+    ps_ctx c = {sens, edge_mask, sens ? kk : (size_t)C * g->E * kk, sens ? (size_t)g->k : (size_t)C * g->k, root_out != NULL, NULL};
+    const size_t per = c.n_main + c.n_root;
+    c.part = calloc((size_t)g->G * per * 2 + 2, sizeof(double));
+    if (!c.part) return fail(g, PLK_E_NOMEM, "plk_group: out of host memory");
+    int rc = for_each(g, job_pair_sums, &c, 1);
+    if (!rc) {
+        for (size_t r = 0; r < per; r++) {
+            double *dst = r < c.n_main ? main_out + 2 * r : (root_out ? root_out + 2 * (r - c.n_main) : NULL);
+            if (!dst) continue;
+            if (g->G == 1) { dst[0] = c.part[2 * r]; dst[1] = c.part[2 * r + 1]; continue; }   /* one engine: its sums, bit for bit */
+            long double acc = 0;
+            for (int i = 0; i < g->G; i++) {
+                if (g->s0[i + 1] == g->s0[i]) continue;
+                acc += (long double)c.part[((size_t)i * per + r) * 2];
+                acc += (long double)c.part[((size_t)i * per + r) * 2 + 1];
+            }
+            const double hi = (double)acc;
+            dst[0] = hi;
+            dst[1] = (double)(acc - (long double)hi);
+        }
+    }
+    free(c.part);
+    return rc;
+}
+
+int plk_group_edge_pair_sums(plk_group *g, const int *edge_mask, double *W_out, double *root_out)
+{
+    return group_pair_sums(g, 0, edge_mask, W_out, root_out);
+}
+
+int plk_group_rate_matrix_sens(plk_group *g, double *G_out, double *root_out)
+{
+    return group_pair_sums(g, 1, NULL, G_out, root_out);
+}
+
 int plk_group_hess(plk_group *g, double *hess_sums_out)
 {
     if (!g || !hess_sums_out) return PLK_E_ARG;

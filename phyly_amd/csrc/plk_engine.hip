@@ -159,6 +159,8 @@ struct plk_engine {
     long opt_force_generic = 0, opt_site_chunk = 0, opt_fused_ns = 0, opt_fused_asm = 1, opt_mfma = 1, opt_up_nodes = 2, opt_pair_tables = 1, opt_vec_reg_stack = 1, opt_mfma_ns2 = 0;
     void *comm = nullptr;                /* ncclComm_t of the one-process-per-GPU reduction step */
     int comm_ranks = 0;
+    long info_pair_sums_kernel = 0, info_query_ns = 0;
+    hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
     long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
@@ -448,7 +450,7 @@ __global__ __launch_bounds__(1024) void k_expm_dd(int ks, int E, const double *_
                           const double *__restrict__ cat_rates,
                           dd *__restrict__ Pdd, double *__restrict__ P, double *__restrict__ dP,
                           dd *gscratch, int use_lds,
-                          const double *__restrict__ Lm /* [2][ks*ks] */, int coef_mode,
+                          const double *__restrict__ Lm /* [2][ks*ks] */, long Lm_stride /* doubles between the directions of consecutive (category, edge) blocks; 0: one direction for all */, int coef_mode,
                           const int *__restrict__ edge_mask, double *__restrict__ Fout, ExpmPost post)
 {
     extern __shared__ double smem_raw[];
@@ -459,6 +461,7 @@ __global__ __launch_bounds__(1024) void k_expm_dd(int ks, int E, const double *_
     const int c = ce / E, e = ce - c * E;
     const int k = FRECHET ? 2 * ks : ks;
     const int kk = k * k, kks = ks * ks;
+    if (FRECHET) Lm += (size_t)ce * Lm_stride;
     if (FRECHET && edge_mask && !edge_mask[e]) {
         for (int idx = threadIdx.x; idx < kks; idx += blockDim.x) Fout[(size_t)ce * kks + idx] = 0.0;
         return;
@@ -1295,6 +1298,8 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_up(UpArgs a)
     }
 }
 
+#include "plk_pairsums.h"
+
 /* padded edge-indexed matrix streams for the up/down kernels:
  * mode 0: out[j*K+i] = M[i][j] (transposed), mode 1: out[i*K+j] = M[i][j] */
 __global__ void k_build_edge_stream(int k, int K, int mode, const double *__restrict__ M, double *__restrict__ out)
@@ -1397,6 +1402,8 @@ extern "C" void plk_destroy(plk_engine *h)
     if (h->ev2) (void)hipEventDestroy(h->ev2);
     if (h->ev3) (void)hipEventDestroy(h->ev3);
     if (h->cp_ev0) (void)hipEventDestroy(h->cp_ev0);
+    if (h->q_ev0) (void)hipEventDestroy(h->q_ev0);
+    if (h->q_ev1) (void)hipEventDestroy(h->q_ev1);
     if (h->cp_ev1) (void)hipEventDestroy(h->cp_ev1);
     for (int i = 0; i < 64; i++) for (int j = 0; j < 2; j++) if (h->evk[i][j]) (void)hipEventDestroy(h->evk[i][j]);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1458,6 +1465,8 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_CAT_POSTERIOR_KERNEL: *out = h->info_cat_posterior_kernel; return PLK_OK;
     case PLK_INFO_CATEGORIES: *out = h->C; return PLK_OK;
     case PLK_INFO_LAST_CAT_POSTERIOR_NS: *out = h->info_cat_posterior_ns; return PLK_OK;
+    case PLK_INFO_PAIR_SUMS_KERNEL: *out = h->info_pair_sums_kernel; return PLK_OK;
+    case PLK_INFO_LAST_QUERY_NS: *out = h->info_query_ns; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && ((h->fmt_pt && h->fmt_kind == 1) || (h->vec_pt && h->fmt_kind == 4)) ? h->fpt.npairs : 0; return PLK_OK;
@@ -1536,7 +1545,7 @@ static int run_expm(plk_engine *h, bool post = false, bool need_dP = true)
     ep.skip_dP = need_dP ? 0 : 1;
     hipLaunchKernelGGL(k_expm_dd<false>, dim3(C * E), dim3(threads), lds_bytes, h->stream,
                        k, E, h->d_Qn, h->d_edge_rates, h->d_cat_rates, h->d_Pdd, h->d_P, h->d_dP,
-                       h->d_scratch, use_lds, (const double *)nullptr, 0, (const int *)nullptr, (double *)nullptr, ep);
+                       h->d_scratch, use_lds, (const double *)nullptr, 0L, 0, (const int *)nullptr, (double *)nullptr, ep);
     HIPCHK(h, hipGetLastError());
     if (post && h->fmt_pt) {
         const int ntab = (int)h->fpt.tab_unit.size();
@@ -2311,6 +2320,14 @@ static void launch_updown(plk_engine *h, const UpArgs &a, unsigned grid, bool de
     else hipLaunchKernelGGL((k_up<K, false, true>), dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a);
 }
 
+/* generic down pass + the outer-product up pass on its fixed grid (plk_pairsums.h) */
+template <int K>
+static void launch_pairsums(plk_engine *h, const UpArgs &a, const PairSumOut &o, unsigned grid, unsigned pgrid)
+{
+    hipLaunchKernelGGL(k_down_store<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a);
+    hipLaunchKernelGGL(k_up_pairsums<K>, dim3(pgrid), dim3(GEN_BLOCK), 0, h->stream, a, o, (int)grid);
+}
+
 /* rows x n weighted sums of X (row stride n) accumulated into acc[rows] (long double pairs) */
 static int wsum_rows(plk_engine *h, int rows, long n, const double *X, const double *w, long double *acc)
 {
@@ -2545,8 +2562,32 @@ static int run_updown_mfma(plk_engine *h, bool deriv, bool marg, const int *edge
 }
 
 /* deriv / marginal for k = 4 with compact codes: interleaved-vector kernels (plk_updown4.h) */
+/* plk_edge_pair_sums asks the down / up drivers for the outer-product pass instead of an edge form: deriv = marg = false,
+ * no edge-form matrices; acc receives [C][E][k][k] edge rows and then [C][k] root rows */
+struct PairSumReq {
+    std::vector<long double> acc;
+    bool want_root = false;
+    bool zero_lh = false;        /* a site of likelihood 0 with a non-zero weight was met */
+};
+/* workgroups of the pair-sum passes: fixed by the device, so the partial sums never grow with S */
+static unsigned pair_sums_grid(const plk_engine *h, long nbatch) { return (unsigned)std::min<long>(nbatch, 4L * h->num_cus); }
+
+static int pair_sums_finish(plk_engine *h, PairSumReq *ps, size_t rows, unsigned grid, const double *part, const int *d_flag)
+{
+    int rc;
+    for (size_t r0 = 0; r0 < rows; r0 += 32768) {       /* gridDim.y of k_wsum_rows */
+        const size_t nr = std::min<size_t>(32768, rows - r0);
+        if ((rc = wsum_rows(h, (int)nr, (long)grid, part + r0 * grid, nullptr, ps->acc.data() + r0))) return rc;
+    }
+    int flag = 0;
+    HIPCHK(h, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (flag) ps->zero_lh = true;
+    return PLK_OK;
+}
+
 static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
-                       double *site_out, double *sums_out, const double *d_M, int dzero, int nM)
+                       double *site_out, double *sums_out, const double *d_M, int dzero, int nM, PairSumReq *ps = nullptr)
 {
     int rc;
     const int N = h->N, E = h->E, C = h->C;
@@ -2569,6 +2610,7 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     int *d_et = nullptr, *d_ei = nullptr, *d_ni = nullptr, *d_te = nullptr, *d_emask = nullptr, *d_nmask = nullptr;
     int *d_has = nullptr, *d_ns = nullptr, *d_oe2 = nullptr, *d_obs2 = nullptr;
     int4 *d_ops2 = nullptr;
+    int *d_psflag = nullptr;
     /* nodes the up pass handles inside their parent's visit (see Up4Args.node_inline) */
     std::vector<int> node_inline(N, 0);
     int *d_inl = nullptr;
@@ -2665,7 +2707,8 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
         const size_t o_pt = npairs4 ? put(pair_tabs.data(), pair_tabs.size()) : 0;
         const size_t o_rb = any_rebuild ? put(rebuild_tab.data(), rebuild_tab.size()) : 0;
         nptab = (size_t)C * npairs4 * h->nchar * h->nchar * 4;
-        if ((rc = dev_reserve(h, &h->d_u4pack, &h->u4pack_cap, pack.size() + 4))) return rc;
+        if ((rc = dev_reserve(h, &h->d_u4pack, &h->u4pack_cap, pack.size() + 4))) return rc;    /* the spare word after the tables: the pair-sum pass's flag */
+        d_psflag = h->d_u4pack + pack.size();
         if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, ntab * (size_t)(1 + nM) + nptab))) return rc;
         HIPCHK(h, hipMemcpyAsync(h->d_u4pack, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));      /* pack is a local */
@@ -2701,7 +2744,13 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     if (chunk < 1) { cleanup(); h->err = "plk_deriv/plk_marginal: not enough device memory for one site"; return PLK_E_NOMEM; }
     if (chunk < S) chunk = std::max<long>(UD4_BLOCK, chunk / UD4_BLOCK * UD4_BLOCK);
     const size_t mvs_doubles = msum_only ? (size_t)N * 4 * (size_t)((chunk + UD4_BLOCK - 1) / UD4_BLOCK) * (UD4_BLOCK / 64) : 0;   /* per-wave marginal sums */
-    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles))) { cleanup(); return rc; }
+    const size_t ps_rows = ps ? (size_t)C * E * 16 + (size_t)C * 4 : 0;
+    const size_t ps_doubles = ps ? ps_rows * pair_sums_grid(h, (chunk + PS4_BLOCK - 1) / PS4_BLOCK) : 0;
+    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles + ps_doubles))) { cleanup(); return rc; }
+    if (ps) {
+        ps->acc.assign(ps_rows, 0.0L);
+        HIPCHK(h, hipMemsetAsync(d_psflag, 0, sizeof(int), h->stream));
+    }
 
     std::vector<long double> dsum(deriv ? ER : 0, 0.0L), msum(marg ? (size_t)N * 4 : 0, 0.0L);
     for (long s0 = 0; s0 < S; s0 += chunk) {
@@ -2737,6 +2786,17 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
         else if (fused_ok && h->slots_needed <= 8) hipLaunchKernelGGL(k_down_fused4<8>, dim3(grid), dim3(UD4_BLOCK), lds_codes, h->stream, a, d_ops2, d_oe2, (int)h->ops.size(), d_obs2, nobs2, first_slot2, first_row2);
         else if (fused_ok && h->slots_needed <= 16) hipLaunchKernelGGL(k_down_fused4<16>, dim3(grid), dim3(UD4_BLOCK), lds_codes, h->stream, a, d_ops2, d_oe2, (int)h->ops.size(), d_obs2, nobs2, first_slot2, first_row2);
         else hipLaunchKernelGGL(k_down_store4, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
+        if (ps) {
+            const long nbatch = (n + PS4_BLOCK - 1) / PS4_BLOCK;
+            const unsigned pgrid = pair_sums_grid(h, nbatch);
+            PairSumOut o;
+            o.part = p; o.flag = d_psflag; o.wsite = h->d_w ? h->d_w + s0 : nullptr; o.want_root = ps->want_root ? 1 : 0;
+            HIPCHK(h, hipMemsetAsync(o.part, 0, ps_rows * pgrid * sizeof(double), h->stream));     /* masked edges: exactly 0 */
+            hipLaunchKernelGGL(k_up4_pairsums, dim3(pgrid), dim3(PS4_BLOCK), 0, h->stream, a, o, (int)nbatch);
+            if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_edge_pair_sums: kernel launch failed"; return PLK_E_DEVICE; }
+            if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, o.part, d_psflag))) { cleanup(); return rc; }
+            continue;
+        }
         if (nodes4 && C == 1) hipLaunchKernelGGL(k_up4_nodes<1>, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
         else if (nodes4) hipLaunchKernelGGL(k_up4_nodes<4>, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
         else if (deriv && marg) hipLaunchKernelGGL((k_up4<true, true>), dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
@@ -2927,25 +2987,30 @@ static bool use_updown4(const plk_engine *h)
 /* d_M: the per-(category, edge) matrices of the edge bilinear form fe^T M L_b: dP for the derivative
  * (dzero = 1: rows sum to zero), scaled Frechet matrices for dwell / trans / em-update (dzero = 0) */
 static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
-                      double *site_out, double *sums_out, const double *d_M_in = nullptr, int dzero = 1, int nM = 1)
+                      double *site_out, double *sums_out, const double *d_M_in = nullptr, int dzero = 1, int nM = 1, PairSumReq *ps = nullptr)
 {
     if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_deriv/plk_marginal: tree, model and patterns must be set"; return PLK_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
-    if (!d_M_in && (rc = ensure_dP(h))) return rc;
+    if (!d_M_in && !ps && (rc = ensure_dP(h))) return rc;
     const double *d_M = d_M_in ? d_M_in : h->d_dP;
+    if (ps) {
+        /* the k = 4 kernel takes compact codes and at most four categories; everything else the generic kernel below */
+        if (use_updown4(h) && h->C <= 4) { h->info_pair_sums_kernel = 1; return run_updown4(h, false, false, edge_mask, nullptr, nullptr, nullptr, nullptr, 0, 0, ps); }
+        h->info_pair_sums_kernel = 2;
+    } else
     if (use_updown_vec(h) && nM == 1) { h->info_updown_kernel = 4; return run_updown_vec(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
-    if (use_mfma(h)) { h->info_updown_kernel = 3; return run_updown_mfma(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
-    if (use_updown4(h)) { h->info_updown_kernel = 1; return run_updown4(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero, nM); }
+    else if (use_mfma(h)) { h->info_updown_kernel = 3; return run_updown_mfma(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
+    else if (use_updown4(h)) { h->info_updown_kernel = 1; return run_updown4(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero, nM); }
     if (nM != 1) { h->err = "internal: several edge forms per pass need the k = 4 kernels"; return PLK_E_ARG; }
-    h->info_updown_kernel = 2;
+    if (!ps) h->info_updown_kernel = 2;
     const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
     const long S = h->S;
     /* padded edge-indexed streams */
     double *d_PT = nullptr, *d_PN = nullptr, *d_DT = nullptr;
     int *d_emask = nullptr, *d_nmask = nullptr;
-    int *d_has = nullptr, *d_ns = nullptr;
+    int *d_has = nullptr, *d_ns = nullptr, *d_psflag = nullptr;
     const size_t strm = (size_t)C * E * K * K;
     auto cleanup = [&]() {
         if (d_PT) (void)hipFree(d_PT);
@@ -2955,12 +3020,13 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
         if (d_nmask) (void)hipFree(d_nmask);
         if (d_has) (void)hipFree(d_has);
         if (d_ns) (void)hipFree(d_ns);
+        if (d_psflag) (void)hipFree(d_psflag);
     };
     if ((rc = dev_alloc(h, &d_PT, strm)) || (rc = dev_alloc(h, &d_PN, strm)) || (rc = dev_alloc(h, &d_DT, strm))) { cleanup(); return rc; }
     const int bt = K * K >= 256 ? 256 : 64;
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, h->d_P, d_PT);
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 1, h->d_P, d_PN);
-    hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, d_M, d_DT);
+    if (!ps) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, d_M, d_DT);
     if (edge_mask && (rc = dev_upload(h, &d_emask, edge_mask, (size_t)E))) { cleanup(); return rc; }
     if (node_mask && (rc = dev_upload(h, &d_nmask, node_mask, (size_t)N))) { cleanup(); return rc; }
     if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
@@ -2981,7 +3047,14 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
     if (chunk < 1) { cleanup(); h->err = "plk_deriv/plk_marginal: not enough device memory for one site"; return PLK_E_NOMEM; }
     if (chunk < S) chunk = std::max<long>(GEN_BLOCK, chunk / GEN_BLOCK * GEN_BLOCK);
-    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk))) { cleanup(); return rc; }
+    const size_t ps_rows = ps ? (size_t)C * E * k * k + (size_t)C * k : 0;
+    const size_t ps_doubles = ps ? ps_rows * pair_sums_grid(h, (chunk + GEN_BLOCK - 1) / GEN_BLOCK) : 0;
+    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + ps_doubles))) { cleanup(); return rc; }
+    if (ps) {
+        ps->acc.assign(ps_rows, 0.0L);
+        if ((rc = dev_alloc(h, &d_psflag, 1))) { cleanup(); return rc; }
+        HIPCHKC(h, hipMemsetAsync(d_psflag, 0, sizeof(int), h->stream));
+    }
 
     std::vector<long double> dsum(deriv ? E : 0, 0.0L), msum(marg ? (size_t)N * k : 0, 0.0L);
     for (long s0 = 0; s0 < S; s0 += chunk) {
@@ -3008,6 +3081,25 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
         if (deriv) HIPCHKC(h, hipMemsetAsync(a.DV, 0, (size_t)E * n * sizeof(double), h->stream));
         if (marg) HIPCHKC(h, hipMemsetAsync(a.MV, 0, (size_t)N * k * n * sizeof(double), h->stream));
         const unsigned grid = (unsigned)((n + GEN_BLOCK - 1) / GEN_BLOCK);
+        if (ps) {
+            const unsigned pgrid = pair_sums_grid(h, (long)grid);
+            PairSumOut o;
+            o.part = p; o.flag = d_psflag; o.wsite = h->d_w ? h->d_w + s0 : nullptr; o.want_root = ps->want_root ? 1 : 0;
+            HIPCHKC(h, hipMemsetAsync(o.part, 0, ps_rows * pgrid * sizeof(double), h->stream));     /* masked edges: exactly 0 */
+            switch (K) {
+            case 2: launch_pairsums<2>(h, a, o, grid, pgrid); break;
+            case 4: launch_pairsums<4>(h, a, o, grid, pgrid); break;
+            case 8: launch_pairsums<8>(h, a, o, grid, pgrid); break;
+            case 16: launch_pairsums<16>(h, a, o, grid, pgrid); break;
+            case 20: launch_pairsums<20>(h, a, o, grid, pgrid); break;
+            case 32: launch_pairsums<32>(h, a, o, grid, pgrid); break;
+            case 61: launch_pairsums<61>(h, a, o, grid, pgrid); break;
+            default: launch_pairsums<64>(h, a, o, grid, pgrid); break;
+            }
+            if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_edge_pair_sums: kernel launch failed"; return PLK_E_DEVICE; }
+            if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, o.part, d_psflag))) { cleanup(); return rc; }
+            continue;
+        }
         switch (K) {
         case 2: launch_updown<2>(h, a, grid, deriv, marg); break;
         case 4: launch_updown<4>(h, a, grid, deriv, marg); break;
@@ -3093,9 +3185,30 @@ extern "C" int plk_comm_destroy(plk_engine *h)
     return PLK_OK;
 }
 
+/* HIP events around everything a query queues (PLK_INFO_LAST_QUERY_NS); the events are made on first use */
+struct QueryTimer {
+    plk_engine *h;
+    bool on = false;
+    explicit QueryTimer(plk_engine *h_) : h(h_)
+    {
+        if (hipSetDevice(h->device) != hipSuccess) return;
+        if (!h->q_ev0 && (hipEventCreate(&h->q_ev0) != hipSuccess || hipEventCreate(&h->q_ev1) != hipSuccess)) { h->q_ev0 = h->q_ev1 = nullptr; return; }
+        on = hipEventRecord(h->q_ev0, h->stream) == hipSuccess;
+    }
+    ~QueryTimer()
+    {
+        h->info_query_ns = 0;
+        if (!on) return;
+        float ms = 0.f;
+        if (hipEventRecord(h->q_ev1, h->stream) == hipSuccess && hipEventSynchronize(h->q_ev1) == hipSuccess &&
+            hipEventElapsedTime(&ms, h->q_ev0, h->q_ev1) == hipSuccess) h->info_query_ns = (long)(ms * 1e6);
+    }
+};
+
 extern "C" int plk_deriv(plk_engine *h, const int *edge_mask, double *site_edge_out, double *edge_sums_out)
 {
     if (!plk_live(h)) return PLK_E_ARG;
+    QueryTimer qt(h);
     return run_updown(h, true, false, edge_mask, nullptr, site_edge_out, edge_sums_out);
 }
 
@@ -3109,6 +3222,7 @@ extern "C" int plk_edge_expect_multi(plk_engine *h, int nL, const double *L_hi, 
     if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_edge_expect: tree, model and patterns must be set"; return PLK_E_ARG; }
     if (!L_hi || nL < 1 || coef_mode < PLK_COEF_PRIOR || coef_mode > PLK_COEF_PRIOR_RATE) { h->err = "plk_edge_expect: bad direction matrix or coefficient mode"; return PLK_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
+    QueryTimer qt(h);
     int rc;
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
     const int k = h->k, C = h->C, E = h->E;
@@ -3147,7 +3261,7 @@ extern "C" int plk_edge_expect_multi(plk_engine *h, int nL, const double *L_hi, 
         for (int m = 0; m < nm; m++) {
             hipLaunchKernelGGL(k_expm_dd<true>, dim3(C * E), dim3(threads), lds_bytes, h->stream,
                                k, E, h->d_Qn, h->d_edge_rates, h->d_cat_rates, (dd *)nullptr, (double *)nullptr, (double *)nullptr,
-                               d_scr, use_lds, d_L + (size_t)m * 2 * kk, coef_mode, d_mask, d_F + (size_t)m * C * E * kk, ExpmPost{});
+                               d_scr, use_lds, d_L + (size_t)m * 2 * kk, 0L, coef_mode, d_mask, d_F + (size_t)m * C * E * kk, ExpmPost{});
         }
         if (hipGetLastError() != hipSuccess) { h->err = "plk_edge_expect: Frechet kernel launch failed"; return PLK_E_DEVICE; }
         HIPCHK(h, hipStreamSynchronize(h->stream));          /* L is a host local */
@@ -3202,11 +3316,118 @@ extern "C" int plk_get_frechet_matrices(plk_engine *h, const double *L_hi, const
     if (!use_lds && (rc = dev_alloc(h, &d_scr, (size_t)C * E * EXPM_BUFFERS * n2))) { cleanup(); return rc; }
     hipLaunchKernelGGL(k_expm_dd<true>, dim3(C * E), dim3(threads), lds_bytes, h->stream,
                        k, E, h->d_Qn, h->d_edge_rates, h->d_cat_rates, (dd *)nullptr, (double *)nullptr, (double *)nullptr,
-                       d_scr, use_lds, d_L, coef_mode, (const int *)nullptr, d_F, ExpmPost{});
+                       d_scr, use_lds, d_L, 0L, coef_mode, (const int *)nullptr, d_F, ExpmPost{});
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(F_out, d_F, (size_t)C * E * kk * sizeof(double), hipMemcpyDeviceToHost);
     cleanup();
     if (e != hipSuccess) { h->err = std::string("plk_get_frechet_matrices: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
+    return PLK_OK;
+}
+
+/* ---------------------------------------------------------------------- */
+/* edge pair sums and the gradient in the rate matrix (plk_pairsums.h)     */
+/* ---------------------------------------------------------------------- */
+
+static int pair_sums_run(plk_engine *h, const int *edge_mask, PairSumReq &ps, const char *who)
+{
+    if (h->k == 0 || h->pat_mode == 0) { h->err = std::string(who) + ": tree, model and patterns must be set"; return PLK_E_ARG; }
+    if (h->E == 0) { h->err = std::string(who) + ": the tree has no edge"; return PLK_E_ARG; }
+    const int rc = run_updown(h, false, false, edge_mask, nullptr, nullptr, nullptr, nullptr, 1, 1, &ps);
+    if (rc) return rc;
+    if (ps.zero_lh) { h->err = std::string(who) + ": site likelihood zero at a site of non-zero weight, the sums are undefined"; return PLK_E_ARG; }
+    return PLK_OK;
+}
+
+static inline void put_dd(double *dst, long double v)
+{
+    const double hi = (double)v;
+    dst[0] = hi;
+    dst[1] = (double)(v - (long double)hi);
+}
+
+extern "C" int plk_edge_pair_sums(plk_engine *h, const int *edge_mask, double *W_out, double *root_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    if (!W_out) { h->err = "plk_edge_pair_sums: no output buffer"; return PLK_E_ARG; }
+    QueryTimer qt(h);
+    PairSumReq ps;
+    ps.want_root = root_out != nullptr;
+    int rc;
+    if ((rc = pair_sums_run(h, edge_mask, ps, "plk_edge_pair_sums"))) return rc;
+    const size_t nW = (size_t)h->C * h->E * h->k * h->k;
+    for (size_t r = 0; r < nW; r++) put_dd(W_out + 2 * r, ps.acc[r]);
+    if (root_out) for (size_t r = 0; r < (size_t)h->C * h->k; r++) put_dd(root_out + 2 * r, ps.acc[nW + r]);
+    return PLK_OK;
+}
+
+/*
+ * G[i][j] = d(sum_s w_s ll_s) / dQn[i][j] = sum_{c,e} <W[c][e], s F_{c,e}(e_i e_j^T)>, s = r_c t_e.  The Frechet
+ * derivative is self-adjoint under the trace pairing up to transposition, <W, F(L)> = <L, F(W^T)^T>, so one Frechet
+ * run per (category, edge) in direction W[c][e]^T gives all k^2 entries: G = sum_{c,e} s F_{c,e}(W[c][e]^T)^T.
+ * K1 takes its scaling-and-squaring count from the norm of the block matrix [[sQ, L], [0, sQ]] and W grows with the sum
+ * of the weights, so every direction is scaled by an exact power of two to infinity norm <= 1 (F is linear in L) and the
+ * factor is put back on the result.  The sum over (c, e) runs on the host in long double, in (c, e) order.
+ */
+extern "C" int plk_rate_matrix_sens(plk_engine *h, double *G_out, double *root_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    if (!G_out) { h->err = "plk_rate_matrix_sens: no output buffer"; return PLK_E_ARG; }
+    QueryTimer qt(h);
+    PairSumReq ps;
+    ps.want_root = root_out != nullptr;
+    int rc;
+    if ((rc = pair_sums_run(h, nullptr, ps, "plk_rate_matrix_sens"))) return rc;
+    const int k = h->k, C = h->C, E = h->E;
+    const size_t kk = (size_t)k * k, n2 = 4 * kk, CE = (size_t)C * E;
+    std::vector<double> L(CE * 2 * kk);
+    std::vector<int> expo(CE, 0);
+    for (size_t ce = 0; ce < CE; ce++) {
+        const long double *Wm = ps.acc.data() + ce * kk;
+        long double norm = 0;
+        for (int i = 0; i < k; i++) {          /* row i of W^T = column i of W */
+            long double row = 0;
+            for (int j = 0; j < k; j++) row += fabsl(Wm[(size_t)j * k + i]);
+            norm = std::max(norm, row);
+        }
+        if (!(norm < INFINITY)) { h->err = "plk_rate_matrix_sens: the pair sums are not finite"; return PLK_E_ARG; }
+        int e = 0;
+        if (norm > 0) (void)frexpl(norm, &e);   /* norm = m 2^e, m in [0.5, 1) */
+        expo[ce] = e;
+        double *hi = L.data() + ce * 2 * kk, *lo = hi + kk;
+        for (int i = 0; i < k; i++)
+            for (int j = 0; j < k; j++) {
+                const long double v = ldexpl(Wm[(size_t)j * k + i], -e);
+                hi[(size_t)i * k + j] = (double)v;
+                lo[(size_t)i * k + j] = (double)(v - (long double)hi[(size_t)i * k + j]);
+            }
+    }
+    const int threads = n2 >= 1024 ? 1024 : (n2 >= 256 ? 256 : 64);
+    int use_lds;
+    const size_t lds_bytes = expm_lds_bytes((size_t)2 * k, threads, &use_lds);
+    if ((rc = dev_reserve(h, &h->d_exL, &h->exL_cap, CE * 2 * kk)) ||
+        (rc = dev_reserve(h, &h->d_exF, &h->exF_cap, CE * kk)) ||
+        (!use_lds && (rc = dev_reserve(h, &h->d_exscr, &h->exscr_cap, CE * EXPM_BUFFERS * n2)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_exL, L.data(), L.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_expm_dd<true>, dim3(C * E), dim3(threads), lds_bytes, h->stream,
+                       k, E, h->d_Qn, h->d_edge_rates, h->d_cat_rates, (dd *)nullptr, (double *)nullptr, (double *)nullptr,
+                       h->d_exscr, use_lds, h->d_exL, (long)(2 * kk), (int)PLK_COEF_PRIOR_RATE_EDGE, (const int *)nullptr, h->d_exF, ExpmPost{});
+    if (hipGetLastError() != hipSuccess) { h->err = "plk_rate_matrix_sens: Frechet kernel launch failed"; return PLK_E_DEVICE; }
+    std::vector<double> F(CE * kk);
+    HIPCHK(h, hipMemcpyAsync(F.data(), h->d_exF, F.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<long double> G(kk, 0.0L);
+    for (size_t ce = 0; ce < CE; ce++)
+        for (int i = 0; i < k; i++)
+            for (int j = 0; j < k; j++) G[(size_t)i * k + j] += ldexpl((long double)F[ce * kk + (size_t)j * k + i], expo[ce]);
+    for (size_t r = 0; r < kk; r++) put_dd(G_out + 2 * r, G[r]);
+    if (root_out) {
+        const size_t nW = CE * kk;
+        for (int i = 0; i < k; i++) {
+            long double acc = 0;
+            for (int c = 0; c < C; c++) acc += ps.acc[nW + (size_t)c * k + i];
+            put_dd(root_out + 2 * i, acc);
+        }
+    }
     return PLK_OK;
 }
 

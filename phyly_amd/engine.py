@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PHYLY_AMD_LIB") or os.path.join(_HERE, "csrc", "libar
 HOST, DEVICE = 0, 1
 ROOT_NONE, ROOT_CUSTOM, ROOT_UNIFORM, ROOT_EQUILIBRIUM = 1, 2, 3, 4
 INFO_LL_KERNEL, INFO_STACK_SLOTS, INFO_PROGRAM_OPS, INFO_LL_KERNEL_NS, INFO_LL_TOTAL_NS, INFO_LL_KERNEL_NS_SUM, INFO_LL_KERNEL_COUNT, INFO_LL_VARIANT, INFO_PAIR_TABLES, INFO_LL_EXEC_FLOPS, \
-    INFO_UPDOWN_KERNEL, INFO_CAT_POSTERIOR_KERNEL, INFO_CATEGORIES, INFO_CAT_POSTERIOR_NS = range(14)
+    INFO_UPDOWN_KERNEL, INFO_CAT_POSTERIOR_KERNEL, INFO_CATEGORIES, INFO_CAT_POSTERIOR_NS, INFO_PAIR_SUMS_KERNEL, INFO_QUERY_NS = range(16)
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 COEF_PRIOR, COEF_PRIOR_RATE_EDGE, COEF_PRIOR_RATE = 0, 1, 2
 FIT_EM, FIT_LBFGS = 0, 1
@@ -68,6 +68,9 @@ def load_library():
     lib.plk_solve_second_order.argtypes = [ci, vp, vp, vp, vp, vp]
     lib.plk_cat_posterior.argtypes = [vp, vp, vp, vp, vp]
     lib.plk_cat_posterior_ll.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.plk_edge_pair_sums.argtypes = [vp, vp, vp, vp]
+    lib.plk_rate_matrix_sens.argtypes = [vp, vp, vp]
+    lib.plk_rate_matrix_chain.argtypes = [ci, vp, ci, ctypes.c_double, ci, vp, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
     lib.plk_get_transition_matrices.argtypes = [vp, vp]
     lib.plk_get_info.argtypes = [vp, ci, ctypes.POINTER(cl)]
     lib.plk_set_option.argtypes = [vp, ci, cl]
@@ -278,6 +281,23 @@ class Engine:
         lsum = np.zeros(2) if want_sums else None
         self._check(self._lib.plk_cat_posterior_ll(self._h, _ptr(post), _ptr(rate), _ptr(sll), _ptr(psum), _ptr(rsum), _ptr(lsum)))
         return post, rate, psum, (tuple(rsum) if want_sums else None), sll, (tuple(lsum) if want_sums else None)
+
+    def edge_pair_sums(self, edge_mask=None, want_root=True):
+        """site-summed outer products per category and edge (include/plk.h:plk_edge_pair_sums)
+        -> (W [C][E][k][k][2], root [C][k][2] or None), double-double entries, CSR edge order"""
+        W = np.zeros((self.C, self.E, self.k, self.k, 2))
+        root = np.zeros((self.C, self.k, 2)) if want_root else None
+        mask = _i32(edge_mask) if edge_mask is not None else None
+        self._check(self._lib.plk_edge_pair_sums(self._h, _ptr(mask), _ptr(W), _ptr(root)))
+        return W, root
+
+    def rate_matrix_sens(self, want_root=True):
+        """gradient of the weighted log likelihood in the normalised rate matrix and in the root weights
+        (include/plk.h:plk_rate_matrix_sens) -> (G [k][k][2], root [k][2] or None)"""
+        G = np.zeros((self.k, self.k, 2))
+        root = np.zeros((self.k, 2)) if want_root else None
+        self._check(self._lib.plk_rate_matrix_sens(self._h, _ptr(G), _ptr(root)))
+        return G, root
 
     def transition_matrices(self):
         P = np.empty((self.C, self.E, self.k, self.k))
