@@ -60,11 +60,21 @@ char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode);
  * "value"]: d/dq_ij for every ordered pair i != j, row-major, the diagonal being minus the row sums; the rate divisor
  * (a number or "equilibrium_exit_rate") and an equilibrium root prior are differentiated through. */
 char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *retcode);
+/* Gradient of the site-aggregated log likelihood in the parameters of the rate mixture (the reference has no such
+ * command).  The request grammar of rate_matrix_deriv: model_and_data plus a site_reduction whose aggregation is
+ * mandatory.  Columns ["parameter", "category", "value"].  gamma_rate_mixture and normalized_median_gamma_rate_mixture:
+ * ["gamma_shape", 0, v] and, when invariable_prior is given and not 0, ["invariable_prior", 0, v] (without an invariable
+ * category there is nothing to report; pass a tiny positive value for the one-sided derivative).  rate_mixture:
+ * ["rate", c, v] for every category, then ["prior", c, v] for every category when the prior is an array (priors taken as
+ * independent); an "equilibrium_exit_rate" divisor is differentiated through (it carries the expected rate).  A model
+ * without a mixture is refused. */
+char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode);
 
 /* Host-only validation of an input document (JSON grammar, model_and_data,
  * reductions) exactly as the corresponding query would perform it, without
  * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
- * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate" | "rate_matrix_deriv".  0 = accepted. */
+ * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate" | "rate_matrix_deriv" |
+ * "mixture_deriv".  0 = accepted. */
 int arbplf_validate_string(const char *what, const char *s_in);
 
 /* stdin -> stdout filter used by the CLI mains (run_string_script,

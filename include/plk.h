@@ -224,6 +224,45 @@ enum { PLK_DIVISOR_NUMBER = 0, PLK_DIVISOR_EXIT_RATE = 1 };
 int plk_rate_matrix_chain(int k, const double *rate_matrix, int divisor_mode, double divisor, int root_mode,
                           const double *G, const double *root, double *grad_out, char *err, size_t errlen);
 
+/*
+ * Gradient of sum_s w_s ll_s in the parameters of the rate mixture, priors and rates taken as independent (the reference
+ * has no such query).  With L_{s,c} the site likelihood under category c alone (root prior included), lhood_s = sum_c p_c L_{s,c}:
+ *     prior_out[c] = d/dp_c = sum_s w_s L_{s,c} / lhood_s                 (no factor p_c: right for a category of prior 0)
+ *     rate_out[c]  = d/dr_c = sum_e t_e sum_s w_s p_c fe_{s,c,e}^T (Qn P_{c,e}) L_{s,c,b} / lhood_s      (at fixed Qn)
+ * The direction matrices t_e Qn P_{c,e} are built as such (not as dP / r_c), so rate_out is right at r_c = 0, the
+ * invariable category, where P = I; edges of rate 0 contribute nothing.  One down pass and one up pass that keeps its
+ * 2 C numbers in registers and writes no per-site plane (plk_mixsens.h); fixed grid and fixed order of every sum as for
+ * plk_edge_pair_sums, whose preconditions and zero-likelihood behaviour apply (PLK_E_ARG, "site likelihood zero").
+ * prior_out, rate_out: [C][2] double-double.  Identities: sum_c p_c prior_out[c] = sum_s w_s;
+ * sum_c r_c rate_out[c] = sum_e t_e (edge sums of plk_deriv); p_c prior_out[c] = post_sums[c] of plk_cat_posterior.
+ * Other queries give the same bits whether or not this call ran in between.
+ */
+int plk_mixture_sens(plk_engine *h, double *prior_out, double *rate_out);
+
+/*
+ * The chain rule from (prior_out, rate_out) of plk_mixture_sens to the user's rate-mixture parameters, following the map
+ * of the model preparation (host_k0.c); host only, IEEE binary128 rounded once.  mode: the rate mixture as numbered in
+ * host_k0.h (2 custom with array prior, 3 custom with uniform prior, 4 gamma, 5 median gamma); n: custom: the number of
+ * categories, gamma: gamma_categories; rates / prior: the custom arrays (prior NULL for mode 3; both ignored for gamma).
+ *   custom, fixed divisor     d/drates[c] = rate_out[c], d/dprior[c] = prior_out[c]
+ *   custom, exit-rate divisor the divisor carries expect = sum_c r_c p_c; with T = sum_c r_c rate_out[c] (Euler: scaling
+ *                             Qn equals scaling every rate) d/drates[c] = rate_out[c] - p_c T / expect,
+ *                             d/dprior[c] = prior_out[c] - r_c T / expect; expect = 0 is refused
+ *   uniform prior             rates only, p_c = 1 / n, same divisor term
+ *   gamma (+I)                r_j = g_j(shape) / (1 - pi), p_j = (1 - pi) / n, last category r = 0, p = pi; expect = 1:
+ *                             d/dshape = sum_j rate_out[j] g_j'(shape) / (1 - pi),
+ *                             d/dpi = sum_j rate_out[j] r_j / (1 - pi) - (1/n) sum_j prior_out[j] + prior_out[n]
+ *                             (only when invariable_prior != 0: without an invariable category nothing is reported for it)
+ * prior_sens / rate_sens: [C][2] with C = n (+ 1 for gamma with invariable_prior != 0).
+ * drates_out: [n] (custom) ; dprior_out: [n] (mode 2) ; dshape_out, dinvariable_out: one double each (gamma).  Outputs that
+ * do not apply to the mode may be NULL and are left alone; *has_invariable_out (may be NULL) is 1 when dinvariable_out was
+ * written.  err / errlen as for plk_rate_matrix_chain.  Returns PLK_E_ARG for bad arguments, no mixture, expect = 0.
+ */
+int plk_mixture_chain(int mode, int n, const double *rates, const double *prior, double gamma_shape, double invariable_prior,
+                      int divisor_mode, const double *prior_sens, const double *rate_sens,
+                      double *drates_out, double *dprior_out, double *dshape_out, double *dinvariable_out,
+                      int *has_invariable_out, char *err, size_t errlen);
+
 /* the scaled Frechet matrices coef_{c,e} * F_{c,e} themselves, [C][E][k][k] host (tests) */
 int plk_get_frechet_matrices(plk_engine *h, const double *L_hi, const double *L_lo, int coef_mode,
                              double *F_out);
@@ -317,9 +356,12 @@ enum {
                                        changed, tables, kernel, sums); for tools/time_cat_posterior.py */
     PLK_INFO_PAIR_SUMS_KERNEL = 14, /* up pass of the last plk_edge_pair_sums / plk_rate_matrix_sens: 0 = none yet, 1 = the k = 4
                                        kernel (compact codes, at most 4 categories), 2 = generic */
-    PLK_INFO_LAST_QUERY_NS = 15     /* HIP-event time from the first to the last device operation of the last plk_deriv,
-                                       plk_edge_expect(_multi), plk_edge_pair_sums or plk_rate_matrix_sens (0 when it could not
-                                       be taken); for tools/time_rate_matrix_deriv.py */
+    PLK_INFO_LAST_QUERY_NS = 15,    /* HIP-event time from the first to the last device operation of the last plk_deriv,
+                                       plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens or plk_mixture_sens
+                                       (0 when it could not be taken); for tools/time_rate_matrix_deriv.py and
+                                       tools/time_mixture_deriv.py */
+    PLK_INFO_MIXTURE_SENS_KERNEL = 16 /* up pass of the last plk_mixture_sens: 0 = none yet, 1 = the k = 4 kernel (compact
+                                       codes, at most 4 categories), 2 = generic */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -393,6 +435,8 @@ int plk_group_cat_posterior(plk_group *g, double *post_out, double *rate_out, do
  * added in engine order (long double), as for the other sums */
 int plk_group_edge_pair_sums(plk_group *g, const int *edge_mask, double *W_out, double *root_out);
 int plk_group_rate_matrix_sens(plk_group *g, double *G_out, double *root_out);
+/* prior_out, rate_out [C][2]: partial sums of the engines added in engine order (long double) */
+int plk_group_mixture_sens(plk_group *g, double *prior_out, double *rate_out);
 int plk_group_hess(plk_group *g, double *hess_sums_out);
 int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out);   /* either may be NULL */
 

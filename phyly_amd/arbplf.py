@@ -112,6 +112,12 @@ def arbplf_rate_matrix_deriv(s):
     return _call("arbplf_rate_matrix_deriv", s)
 
 
+def arbplf_mixture_deriv(s):
+    """gradient of the site-aggregated log likelihood in the rate-mixture parameters (no counterpart in the reference):
+    columns parameter, category, value; gamma_shape / invariable_prior, or rate / prior of a custom rate_mixture"""
+    return _call("arbplf_mixture_deriv", s)
+
+
 def _out_of_scope(name):
     def f(s):
         raise RuntimeError("arbplf likelihood error: %s is outside the MI355X hot path of this build" % name)

@@ -236,7 +236,7 @@ static int check_finite(double v, const char *what)
 }
 
 /* _parse of the drivers: kind 0 ll, 1 deriv, 2 marginal, 3 dwell, 4 trans, 5 em-update, 6 the second-order family,
- * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv (no counterpart in the reference: its reduction grammar, its table layout)
+ * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv, 10 mixture-deriv (no counterpart in the reference: its reduction grammar, its table layout)
  * (src/arbplfll.c:250-288, src/arbplfderiv.c:445-493, src/arbplfmarginal.c:348-405,
  *  src/arbplfdwell.c:507-566, src/arbplftrans.c:553-614, src/arbplfem.c:505-545) */
 static int query_parse(query *q, int kind, const jval *root)
@@ -262,8 +262,9 @@ static int query_parse(query *q, int kind, const jval *root)
                                                j_get(root, "trans_reduction"))) return -1;
     /* the category axis has the length the mixture gives it (Gamma categories first, the invariable one last) */
     if (kind == 7 && host_reduction_parse(&q->r_a, arbplf_k0_category_count(&q->m.mix), "category", j_get(root, "category_reduction"))) return -1;
-    if ((kind == 6 || kind == 9) && !j_get(root, "site_reduction")) { fprintf(stderr, "error: site_reduction is required\n"); return -1; }
-    if ((kind == 5 || kind == 6 || kind == 9) && q->r_site.agg_mode == AGG_NONE) { fprintf(stderr, "error: aggregation over sites is required\n"); return -1; }
+    if ((kind == 6 || kind == 9 || kind == 10) && !j_get(root, "site_reduction")) { fprintf(stderr, "error: site_reduction is required\n"); return -1; }
+    if ((kind == 5 || kind == 6 || kind == 9 || kind == 10) && q->r_site.agg_mode == AGG_NONE) { fprintf(stderr, "error: aggregation over sites is required\n"); return -1; }
+    if (kind == 10 && q->m.mix.mode == K0_MIX_NONE) { fprintf(stderr, "error: the model has no rate mixture, there is nothing to differentiate\n"); return -1; }
     return 0;
 }
 
@@ -913,6 +914,83 @@ done:
     return rc;
 }
 
+/* ------------------------------------------------------------------ mixture-deriv */
+/* arbplf-mixture-deriv: d(site-aggregated log likelihood) / d(parameter of the rate mixture).  The engine gives the
+ * gradient in the category priors and rates, taken as independent, from one down pass and one up pass
+ * (plk_mixture_sens); plk_mixture_chain takes them to gamma_shape / invariable_prior or to the rates / prior arrays of a
+ * custom mixture, the exit-rate divisor's dependence on the expected rate included. */
+static void mixture_row(jbuf *out, int *first, const char *name, int c, double v)
+{
+    if (!*first) jbuf_puts(out, ", ");
+    *first = 0;
+    jbuf_puts(out, "[\""); jbuf_puts(out, name); jbuf_puts(out, "\", "); jbuf_int(out, c); jbuf_puts(out, ", "); jbuf_real(out, v); jbuf_puts(out, "]");
+}
+
+static int run_mixture_deriv(const jval *root, jbuf *out)
+{
+    query q;
+    int rc = -1;
+    double *ps = NULL, *rs = NULL, *dr = NULL, *dp = NULL;
+    query_init(&q);
+    if (query_parse(&q, 10, root)) goto done;
+    if (query_prepare(&q)) goto done;
+    const k0_mixture *mix = &q.m.mix;
+    const int C = arbplf_k0_category_count(mix), n = mix->n;
+    const int gamma = mix->mode == K0_MIX_GAMMA || mix->mode == K0_MIX_GAMMA_MEDIAN;
+    ps = calloc((size_t)C * 2 + 2, sizeof(double));
+    rs = calloc((size_t)C * 2 + 2, sizeof(double));
+    dr = calloc((size_t)n + 1, sizeof(double));
+    dp = calloc((size_t)n + 1, sizeof(double));
+    if (!ps || !rs || !dr || !dp) goto done;
+    double dshape = 0, dinv = 0;
+    int has_inv = gamma && mix->invariable_prior != 0;
+    if (q.U > 0) {
+        if (plk_group_mixture_sens(q.eng, ps, rs)) {
+            const char *msg = plk_group_last_error(q.eng);
+            if (strstr(msg, "site likelihood zero")) check_finite(NAN, "the mixture gradient");
+            else fprintf(stderr, "error: %s\n", msg);
+            goto done;
+        }
+        char err[200];
+        if (plk_mixture_chain(mix->mode, n, mix->rates, mix->prior, mix->gamma_shape, mix->invariable_prior,
+                              q.m.use_equilibrium_divisor ? PLK_DIVISOR_EXIT_RATE : PLK_DIVISOR_NUMBER, ps, rs,
+                              dr, dp, &dshape, &dinv, &has_inv, err, sizeof err)) {
+            fprintf(stderr, "error: %s\n", err[0] ? err : "the chain rule of the mixture gradient failed");
+            goto done;
+        }
+    }
+    jbuf_puts(out, "{\"columns\": [\"parameter\", \"category\", \"value\"], \"data\": [");
+    int first = 1;
+    if (gamma) {
+        double v = clean((long double)dshape / q.div_site);
+        if (check_finite(v, "the mixture gradient")) goto done;
+        mixture_row(out, &first, "gamma_shape", 0, v);
+        if (has_inv) {
+            v = clean((long double)dinv / q.div_site);
+            if (check_finite(v, "the mixture gradient")) goto done;
+            mixture_row(out, &first, "invariable_prior", 0, v);
+        }
+    } else {
+        for (int c = 0; c < n; c++) {
+            double v = clean((long double)dr[c] / q.div_site);
+            if (check_finite(v, "the mixture gradient")) goto done;
+            mixture_row(out, &first, "rate", c, v);
+        }
+        if (mix->mode == K0_MIX_CUSTOM)
+            for (int c = 0; c < n; c++) {
+                double v = clean((long double)dp[c] / q.div_site);
+                if (check_finite(v, "the mixture gradient")) goto done;
+                mixture_row(out, &first, "prior", c, v);
+            }
+    }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(ps); free(rs); free(dr); free(dp);
+    query_clear(&q);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ string API */
 static char *string_hom(int (*run)(const jval *, jbuf *), void *userdata, const char *s_in, int *retcode)
 {
@@ -953,10 +1031,11 @@ char *arbplf_newton_update_string(void *userdata, const char *s_in, int *retcode
 char *arbplf_cat_posterior_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_cat_posterior, userdata, s_in, retcode); }
 char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_site_rate, userdata, s_in, retcode); }
 char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_rate_matrix_deriv, userdata, s_in, retcode); }
+char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_mixture_deriv, userdata, s_in, retcode); }
 
 /* Host-only validation (JSON grammar, model, reductions); no GPU is touched.
  * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta", "newton_update",
- * "cat_posterior", "site_rate" or "rate_matrix_deriv".
+ * "cat_posterior", "site_rate", "rate_matrix_deriv" or "mixture_deriv".
  * Returns 0 when the input would be accepted. */
 int arbplf_validate_string(const char *what, const char *s_in)
 {
@@ -964,7 +1043,8 @@ int arbplf_validate_string(const char *what, const char *s_in)
     int kind = !strcmp(what, "ll") ? 0 : !strcmp(what, "deriv") ? 1 : !strcmp(what, "marginal") ? 2 :
                !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 :
                (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 :
-               !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : !strcmp(what, "rate_matrix_deriv") ? 9 : -1;
+               !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : !strcmp(what, "rate_matrix_deriv") ? 9 :
+               !strcmp(what, "mixture_deriv") ? 10 : -1;
     if (kind < 0 || !s_in) return -1;
     json_doc *doc = json_doc_parse(s_in, err, sizeof err);
     if (!doc) { fprintf(stderr, "%s\n", err); return -1; }

@@ -436,6 +436,50 @@ int plk_group_rate_matrix_sens(plk_group *g, double *G_out, double *root_out)
     return group_pair_sums(g, 1, NULL, G_out, root_out);
 }
 
+/* gradient in the rate-mixture parameters: 2 C sums.  Weak for the same reason as above. */
+extern int plk_mixture_sens(plk_engine *h, double *prior_out, double *rate_out) __attribute__((weak));
+
+typedef struct { size_t C; double *part; } mix_ctx;
+
+static int job_mixture_sens(plk_group *g, int i, void *p)
+{
+    mix_ctx *c = p;
+    if (g->s0[i + 1] == g->s0[i]) return PLK_OK;           /* an engine without sites adds nothing */
+    double *mine = c->part + (size_t)i * c->C * 4;
+    return plk_mixture_sens(g->eng[i], mine, mine + 2 * c->C);
+}
+
+int plk_group_mixture_sens(plk_group *g, double *prior_out, double *rate_out)
+{
+    if (!g || !prior_out || !rate_out) return PLK_E_ARG;
+    if (!plk_mixture_sens || !plk_get_info) return fail(g, PLK_E_UNSUPPORTED, "plk_group: the engine has no plk_mixture_sens");
+    if (!g->have_patterns) return fail(g, PLK_E_ARG, "plk_group: tree, model and patterns must be set");
+    long C = 0;
+    if (plk_get_info(g->eng[0], PLK_INFO_CATEGORIES, &C) || C < 1) return fail(g, PLK_E_ARG, "plk_group: the model is not set");
+    mix_ctx c = {(size_t)C, NULL};
+    const size_t per = 2 * c.C;
+    c.part = calloc((size_t)g->G * per * 2 + 2, sizeof(double));
+    if (!c.part) return fail(g, PLK_E_NOMEM, "plk_group: out of host memory");
+    int rc = for_each(g, job_mixture_sens, &c, 1);
+    if (!rc) {
+        for (size_t r = 0; r < per; r++) {
+            double *dst = r < c.C ? prior_out + 2 * r : rate_out + 2 * (r - c.C);
+            if (g->G == 1) { dst[0] = c.part[2 * r]; dst[1] = c.part[2 * r + 1]; continue; }   /* one engine: its sums, bit for bit */
+            long double acc = 0;
+            for (int i = 0; i < g->G; i++) {
+                if (g->s0[i + 1] == g->s0[i]) continue;
+                acc += (long double)c.part[((size_t)i * per + r) * 2];
+                acc += (long double)c.part[((size_t)i * per + r) * 2 + 1];
+            }
+            const double hi = (double)acc;
+            dst[0] = hi;
+            dst[1] = (double)(acc - (long double)hi);
+        }
+    }
+    free(c.part);
+    return rc;
+}
+
 int plk_group_hess(plk_group *g, double *hess_sums_out)
 {
     if (!g || !hess_sums_out) return PLK_E_ARG;

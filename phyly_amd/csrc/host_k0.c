@@ -19,10 +19,12 @@
  */
 #include <math.h>
 #include <quadmath.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "host_k0.h"
+#include "plk.h"
 
 typedef __float128 ld;
 
@@ -176,4 +178,97 @@ int arbplf_k0_prepare(int k, const double *rate_matrix,
     }
     free(Q); free(pi);
     return C;
+}
+
+/* ---------------------------------------------------------------------------------------------------------------- */
+/* chain rule of arbplf-mixture-deriv (include/plk.h: plk_mixture_chain)                                             */
+/* ---------------------------------------------------------------------------------------------------------------- */
+
+static int mix_fail(char *err, size_t errlen, const char *msg)
+{
+    if (err && errlen) snprintf(err, errlen, "%s", msg);
+    return PLK_E_ARG;
+}
+
+/*
+ * dg[j] = d g_j / d shape of gamma_rates, in binary128: central differences at h and h / 2 with h = shape * 2^-17 and
+ * one Richardson step, D = (4 D(h/2) - D(h)) / 3.
+ * Estimate, relative to max_j |g_j'|: gamma_rates is analytic in the shape and is evaluated to about 1e-32 relative
+ * (series cut at 1e-36, quantiles bisected to the last bit), so rounding contributes about 1e-32 / 2^-17 * 3 ~ 4e-27 in
+ * units of g / shape.  D(h) = g' + h^2 g''' / 6 + h^4 g^(5) / 120 + ..., so the Richardson step leaves -h^4 g^(5) / 480:
+ * with h / shape = 7.6e-6, (h / shape)^4 / 480 = 7e-24 times shape^4 g^(5) / g', which would have to reach 1e8 to matter
+ * (it is below 1e3 for 0.05 <= shape <= 100).  Both stay far below 1e-15.
+ */
+static int gamma_rates_deriv(int mode, int n, ld shape, ld *dg)
+{
+    ld *buf = calloc((size_t)4 * n, sizeof(ld));
+    if (!buf) return -1;
+    const ld h = ldexpq(shape, -17);
+    gamma_rates(mode, n, shape + h, buf);
+    gamma_rates(mode, n, shape - h, buf + n);
+    gamma_rates(mode, n, shape + h / 2, buf + 2 * n);
+    gamma_rates(mode, n, shape - h / 2, buf + 3 * n);
+    for (int j = 0; j < n; j++) {
+        const ld d1 = (buf[j] - buf[n + j]) / (2 * h), d2 = (buf[2 * n + j] - buf[3 * n + j]) / h;
+        dg[j] = (4 * d2 - d1) / 3;
+    }
+    free(buf);
+    return 0;
+}
+
+int plk_mixture_chain(int mode, int n, const double *rates, const double *prior, double gamma_shape, double invariable_prior,
+                      int divisor_mode, const double *prior_sens, const double *rate_sens,
+                      double *drates_out, double *dprior_out, double *dshape_out, double *dinvariable_out,
+                      int *has_invariable_out, char *err, size_t errlen)
+{
+    if (err && errlen) err[0] = 0;
+    if (has_invariable_out) *has_invariable_out = 0;
+    if (mode == K0_MIX_NONE) return mix_fail(err, errlen, "plk_mixture_chain: the model has no rate mixture, there is nothing to differentiate");
+    if (mode != K0_MIX_CUSTOM && mode != K0_MIX_UNIFORM && mode != K0_MIX_GAMMA && mode != K0_MIX_GAMMA_MEDIAN)
+        return mix_fail(err, errlen, "plk_mixture_chain: bad rate mixture mode");
+    if (n < 1 || !prior_sens || !rate_sens) return mix_fail(err, errlen, "plk_mixture_chain: bad arguments");
+    if (divisor_mode != PLK_DIVISOR_NUMBER && divisor_mode != PLK_DIVISOR_EXIT_RATE) return mix_fail(err, errlen, "plk_mixture_chain: bad divisor form");
+#define SENS(a, c) ((ld)(a)[2 * (c)] + (ld)(a)[2 * (c) + 1])
+    if (mode == K0_MIX_CUSTOM || mode == K0_MIX_UNIFORM) {
+        if (!rates || !drates_out || (mode == K0_MIX_CUSTOM && (!prior || !dprior_out))) return mix_fail(err, errlen, "plk_mixture_chain: bad arguments");
+        /* the divisor of the exit-rate form carries expect = sum_c r_c p_c: f(Qn / expect), and df/d(scale of Qn) = T */
+        ld expect = 0, T = 0;
+        for (int c = 0; c < n; c++) {
+            const ld p = mode == K0_MIX_CUSTOM ? (ld)prior[c] : 1.0Q / (ld)n;
+            expect += (ld)rates[c] * p;
+            T += (ld)rates[c] * SENS(rate_sens, c);
+        }
+        const int exitr = divisor_mode == PLK_DIVISOR_EXIT_RATE;
+        if (exitr && !(expect != 0 && finiteq(expect))) return mix_fail(err, errlen, "plk_mixture_chain: the expected rate of the mixture is zero, the exit-rate divisor is undefined");
+        for (int c = 0; c < n; c++) {
+            const ld p = mode == K0_MIX_CUSTOM ? (ld)prior[c] : 1.0Q / (ld)n;
+            drates_out[c] = (double)(SENS(rate_sens, c) - (exitr ? p * T / expect : 0));
+            if (mode == K0_MIX_CUSTOM) dprior_out[c] = (double)(SENS(prior_sens, c) - (exitr ? (ld)rates[c] * T / expect : 0));
+        }
+        return PLK_OK;
+    }
+    if (!dshape_out) return mix_fail(err, errlen, "plk_mixture_chain: bad arguments");
+    if (!(gamma_shape > 0) || !isfinite(gamma_shape)) return mix_fail(err, errlen, "plk_mixture_chain: gamma_shape must be positive");
+    if (!(invariable_prior >= 0 && invariable_prior < 1)) return mix_fail(err, errlen, "plk_mixture_chain: invariable_prior must be in [0, 1)");
+    const int inv = invariable_prior != 0;
+    if (inv && !dinvariable_out) return mix_fail(err, errlen, "plk_mixture_chain: bad arguments");
+    ld *g = calloc((size_t)2 * n, sizeof(ld));
+    if (!g) return PLK_E_NOMEM;
+    ld *dg = g + n;
+    gamma_rates(mode, n, (ld)gamma_shape, g);
+    if (gamma_rates_deriv(mode, n, (ld)gamma_shape, dg)) { free(g); return PLK_E_NOMEM; }
+    const ld q = 1 - (ld)invariable_prior;
+    ld dshape = 0, dpi = 0;
+    for (int j = 0; j < n; j++) {
+        dshape += SENS(rate_sens, j) * dg[j] / q;
+        dpi += SENS(rate_sens, j) * (g[j] / q) / q - SENS(prior_sens, j) / (ld)n;
+    }
+    *dshape_out = (double)dshape;
+    if (inv) {
+        *dinvariable_out = (double)(dpi + SENS(prior_sens, n));
+        if (has_invariable_out) *has_invariable_out = 1;
+    }
+#undef SENS
+    free(g);
+    return PLK_OK;
 }

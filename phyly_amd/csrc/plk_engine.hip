@@ -160,6 +160,8 @@ struct plk_engine {
     void *comm = nullptr;                /* ncclComm_t of the one-process-per-GPU reduction step */
     int comm_ranks = 0;
     long info_pair_sums_kernel = 0, info_query_ns = 0;
+    double *d_mixD = nullptr; size_t mixd_cap = 0;   /* plk_mixture_sens: its direction matrices t_e Qn P[c][e] (the query's own; d_dP is not touched) */
+    long info_mixture_sens_kernel = 0;
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
     long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
@@ -1299,6 +1301,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_up(UpArgs a)
 }
 
 #include "plk_pairsums.h"
+#include "plk_mixsens.h"
 
 /* padded edge-indexed matrix streams for the up/down kernels:
  * mode 0: out[j*K+i] = M[i][j] (transposed), mode 1: out[i*K+j] = M[i][j] */
@@ -1395,7 +1398,7 @@ extern "C" void plk_destroy(plk_engine *h)
                     h->d_defs, h->d_B, h->d_w, h->d_ops, h->d_fops, h->d_words, h->d_mat_edge, h->d_edge_slot, h->d_op_edge, h->d_tip_edge, h->d_obs_nodes,
                     h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
                     h->d_cp_fops, h->d_cp_ops, h->d_cp_mat_edge, h->d_cp_tip_edge, h->d_cp_obs_nodes, h->d_cp_op_edge, h->d_cp_expo, h->d_cp_flag,
-                    h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial};
+                    h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial, h->d_mixD};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1467,6 +1470,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LAST_CAT_POSTERIOR_NS: *out = h->info_cat_posterior_ns; return PLK_OK;
     case PLK_INFO_PAIR_SUMS_KERNEL: *out = h->info_pair_sums_kernel; return PLK_OK;
     case PLK_INFO_LAST_QUERY_NS: *out = h->info_query_ns; return PLK_OK;
+    case PLK_INFO_MIXTURE_SENS_KERNEL: *out = h->info_mixture_sens_kernel; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && ((h->fmt_pt && h->fmt_kind == 1) || (h->vec_pt && h->fmt_kind == 4)) ? h->fpt.npairs : 0; return PLK_OK;
@@ -2328,6 +2332,14 @@ static void launch_pairsums(plk_engine *h, const UpArgs &a, const PairSumOut &o,
     hipLaunchKernelGGL(k_up_pairsums<K>, dim3(pgrid), dim3(GEN_BLOCK), 0, h->stream, a, o, (int)grid);
 }
 
+/* ... and the mixture-gradient up pass on the same grid (plk_mixsens.h) */
+template <int K>
+static void launch_mixsens(plk_engine *h, const UpArgs &a, const MixSensOut &o, unsigned grid, unsigned pgrid)
+{
+    hipLaunchKernelGGL(k_down_store<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a);
+    hipLaunchKernelGGL(k_up_mixsens<K>, dim3(pgrid), dim3(GEN_BLOCK), 0, h->stream, a, o, (int)grid);
+}
+
 /* rows x n weighted sums of X (row stride n) accumulated into acc[rows] (long double pairs) */
 static int wsum_rows(plk_engine *h, int rows, long n, const double *X, const double *w, long double *acc)
 {
@@ -2568,6 +2580,10 @@ struct PairSumReq {
     std::vector<long double> acc;
     bool want_root = false;
     bool zero_lh = false;        /* a site of likelihood 0 with a non-zero weight was met */
+    /* plk_mixture_sens: the same drivers run the mixture-gradient pass (plk_mixsens.h) when mix_D is set: [C][E][k][k]
+     * direction matrices on the device; acc then receives the rows that pass writes (the k = 4 kernel: 2 MIX4_MAX_C rows,
+     * prior c at c, rate c at MIX4_MAX_C + c; the generic kernel: C prior rows, then C rate rows) */
+    const double *mix_D = nullptr;
 };
 /* workgroups of the pair-sum passes: fixed by the device, so the partial sums never grow with S */
 static unsigned pair_sums_grid(const plk_engine *h, long nbatch) { return (unsigned)std::min<long>(nbatch, 4L * h->num_cus); }
@@ -2744,7 +2760,7 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     if (chunk < 1) { cleanup(); h->err = "plk_deriv/plk_marginal: not enough device memory for one site"; return PLK_E_NOMEM; }
     if (chunk < S) chunk = std::max<long>(UD4_BLOCK, chunk / UD4_BLOCK * UD4_BLOCK);
     const size_t mvs_doubles = msum_only ? (size_t)N * 4 * (size_t)((chunk + UD4_BLOCK - 1) / UD4_BLOCK) * (UD4_BLOCK / 64) : 0;   /* per-wave marginal sums */
-    const size_t ps_rows = ps ? (size_t)C * E * 16 + (size_t)C * 4 : 0;
+    const size_t ps_rows = ps ? (ps->mix_D ? (size_t)2 * MIX4_MAX_C : (size_t)C * E * 16 + (size_t)C * 4) : 0;
     const size_t ps_doubles = ps ? ps_rows * pair_sums_grid(h, (chunk + PS4_BLOCK - 1) / PS4_BLOCK) : 0;
     if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles + ps_doubles))) { cleanup(); return rc; }
     if (ps) {
@@ -2789,6 +2805,14 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
         if (ps) {
             const long nbatch = (n + PS4_BLOCK - 1) / PS4_BLOCK;
             const unsigned pgrid = pair_sums_grid(h, nbatch);
+            if (ps->mix_D) {
+                MixSensOut mo;
+                mo.part = p; mo.flag = d_psflag; mo.wsite = h->d_w ? h->d_w + s0 : nullptr; mo.D = ps->mix_D;
+                hipLaunchKernelGGL(k_up4_mixsens, dim3(pgrid), dim3(PS4_BLOCK), 0, h->stream, a, mo, (int)nbatch);   /* every row of part is written */
+                if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_mixture_sens: kernel launch failed"; return PLK_E_DEVICE; }
+                if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, mo.part, d_psflag))) { cleanup(); return rc; }
+                continue;
+            }
             PairSumOut o;
             o.part = p; o.flag = d_psflag; o.wsite = h->d_w ? h->d_w + s0 : nullptr; o.want_root = ps->want_root ? 1 : 0;
             HIPCHK(h, hipMemsetAsync(o.part, 0, ps_rows * pgrid * sizeof(double), h->stream));     /* masked edges: exactly 0 */
@@ -2997,8 +3021,9 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     const double *d_M = d_M_in ? d_M_in : h->d_dP;
     if (ps) {
         /* the k = 4 kernel takes compact codes and at most four categories; everything else the generic kernel below */
-        if (use_updown4(h) && h->C <= 4) { h->info_pair_sums_kernel = 1; return run_updown4(h, false, false, edge_mask, nullptr, nullptr, nullptr, nullptr, 0, 0, ps); }
-        h->info_pair_sums_kernel = 2;
+        long &info = ps->mix_D ? h->info_mixture_sens_kernel : h->info_pair_sums_kernel;
+        if (use_updown4(h) && h->C <= 4) { info = 1; return run_updown4(h, false, false, edge_mask, nullptr, nullptr, nullptr, nullptr, 0, 0, ps); }
+        info = 2;
     } else
     if (use_updown_vec(h) && nM == 1) { h->info_updown_kernel = 4; return run_updown_vec(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
     else if (use_mfma(h)) { h->info_updown_kernel = 3; return run_updown_mfma(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
@@ -3026,7 +3051,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     const int bt = K * K >= 256 ? 256 : 64;
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, h->d_P, d_PT);
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 1, h->d_P, d_PN);
-    if (!ps) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, d_M, d_DT);
+    if (!ps || ps->mix_D) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
     if (edge_mask && (rc = dev_upload(h, &d_emask, edge_mask, (size_t)E))) { cleanup(); return rc; }
     if (node_mask && (rc = dev_upload(h, &d_nmask, node_mask, (size_t)N))) { cleanup(); return rc; }
     if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
@@ -3047,7 +3072,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
     if (chunk < 1) { cleanup(); h->err = "plk_deriv/plk_marginal: not enough device memory for one site"; return PLK_E_NOMEM; }
     if (chunk < S) chunk = std::max<long>(GEN_BLOCK, chunk / GEN_BLOCK * GEN_BLOCK);
-    const size_t ps_rows = ps ? (size_t)C * E * k * k + (size_t)C * k : 0;
+    const size_t ps_rows = ps ? (ps->mix_D ? (size_t)2 * C : (size_t)C * E * k * k + (size_t)C * k) : 0;
     const size_t ps_doubles = ps ? ps_rows * pair_sums_grid(h, (chunk + GEN_BLOCK - 1) / GEN_BLOCK) : 0;
     if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + ps_doubles))) { cleanup(); return rc; }
     if (ps) {
@@ -3083,6 +3108,23 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
         const unsigned grid = (unsigned)((n + GEN_BLOCK - 1) / GEN_BLOCK);
         if (ps) {
             const unsigned pgrid = pair_sums_grid(h, (long)grid);
+            if (ps->mix_D) {
+                MixSensOut mo;
+                mo.part = p; mo.flag = d_psflag; mo.wsite = h->d_w ? h->d_w + s0 : nullptr; mo.D = nullptr;
+                switch (K) {
+                case 2: launch_mixsens<2>(h, a, mo, grid, pgrid); break;
+                case 4: launch_mixsens<4>(h, a, mo, grid, pgrid); break;
+                case 8: launch_mixsens<8>(h, a, mo, grid, pgrid); break;
+                case 16: launch_mixsens<16>(h, a, mo, grid, pgrid); break;
+                case 20: launch_mixsens<20>(h, a, mo, grid, pgrid); break;
+                case 32: launch_mixsens<32>(h, a, mo, grid, pgrid); break;
+                case 61: launch_mixsens<61>(h, a, mo, grid, pgrid); break;
+                default: launch_mixsens<64>(h, a, mo, grid, pgrid); break;
+                }
+                if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_mixture_sens: kernel launch failed"; return PLK_E_DEVICE; }
+                if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, mo.part, d_psflag))) { cleanup(); return rc; }
+                continue;
+            }
             PairSumOut o;
             o.part = p; o.flag = d_psflag; o.wsite = h->d_w ? h->d_w + s0 : nullptr; o.want_root = ps->want_root ? 1 : 0;
             HIPCHKC(h, hipMemsetAsync(o.part, 0, ps_rows * pgrid * sizeof(double), h->stream));     /* masked edges: exactly 0 */
@@ -3427,6 +3469,43 @@ extern "C" int plk_rate_matrix_sens(plk_engine *h, double *G_out, double *root_o
             for (int c = 0; c < C; c++) acc += ps.acc[nW + (size_t)c * k + i];
             put_dd(root_out + 2 * i, acc);
         }
+    }
+    return PLK_OK;
+}
+
+/*
+ * Gradient of sum_s w_s ll_s in the priors and rates of the rate mixture (plk_mixsens.h).  The direction matrices
+ * D[c][e] = t_e Qn P[c][e] live in a buffer of the query's own and are rebuilt on every call from the stored
+ * double-double P (C E small products), so nothing another query caches is read stale or overwritten.
+ */
+extern "C" int plk_mixture_sens(plk_engine *h, double *prior_out, double *rate_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    if (!prior_out || !rate_out) { h->err = "plk_mixture_sens: no output buffer"; return PLK_E_ARG; }
+    if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_mixture_sens: tree, model and patterns must be set"; return PLK_E_ARG; }
+    if (h->E == 0) { h->err = "plk_mixture_sens: the tree has no edge"; return PLK_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    QueryTimer qt(h);
+    int rc;
+    if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
+    const int k = h->k, C = h->C, E = h->E;
+    const size_t kk = (size_t)k * k;
+    if ((rc = dev_reserve(h, &h->d_mixD, &h->mixd_cap, (size_t)C * E * kk))) return rc;
+    {
+        const int threads = kk >= 1024 ? 1024 : (kk >= 256 ? 256 : 64);
+        int use_lds;
+        const size_t strip_bytes = expm_lds_bytes((size_t)k, threads, &use_lds);
+        hipLaunchKernelGGL(k_mix_dir, dim3(C * E), dim3(threads), use_lds ? 0 : strip_bytes, h->stream,
+                           k, E, h->d_Qn, h->d_edge_rates, h->d_Pdd, h->d_mixD, use_lds ? 0 : 1);
+        if (hipGetLastError() != hipSuccess) { h->err = "plk_mixture_sens: direction matrix kernel launch failed"; return PLK_E_DEVICE; }
+    }
+    PairSumReq ps;
+    ps.mix_D = h->d_mixD;
+    if ((rc = pair_sums_run(h, nullptr, ps, "plk_mixture_sens"))) return rc;
+    const size_t rate_row0 = h->info_mixture_sens_kernel == 1 ? (size_t)MIX4_MAX_C : (size_t)C;
+    for (int c = 0; c < C; c++) {
+        put_dd(prior_out + 2 * c, ps.acc[c]);
+        put_dd(rate_out + 2 * c, ps.acc[rate_row0 + c]);
     }
     return PLK_OK;
 }

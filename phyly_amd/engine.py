@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("PHYLY_AMD_LIB") or os.path.join(_HERE, "csrc", "libar
 HOST, DEVICE = 0, 1
 ROOT_NONE, ROOT_CUSTOM, ROOT_UNIFORM, ROOT_EQUILIBRIUM = 1, 2, 3, 4
 INFO_LL_KERNEL, INFO_STACK_SLOTS, INFO_PROGRAM_OPS, INFO_LL_KERNEL_NS, INFO_LL_TOTAL_NS, INFO_LL_KERNEL_NS_SUM, INFO_LL_KERNEL_COUNT, INFO_LL_VARIANT, INFO_PAIR_TABLES, INFO_LL_EXEC_FLOPS, \
-    INFO_UPDOWN_KERNEL, INFO_CAT_POSTERIOR_KERNEL, INFO_CATEGORIES, INFO_CAT_POSTERIOR_NS, INFO_PAIR_SUMS_KERNEL, INFO_QUERY_NS = range(16)
+    INFO_UPDOWN_KERNEL, INFO_CAT_POSTERIOR_KERNEL, INFO_CATEGORIES, INFO_CAT_POSTERIOR_NS, INFO_PAIR_SUMS_KERNEL, INFO_QUERY_NS, INFO_MIXTURE_SENS_KERNEL = range(17)
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 COEF_PRIOR, COEF_PRIOR_RATE_EDGE, COEF_PRIOR_RATE = 0, 1, 2
 FIT_EM, FIT_LBFGS = 0, 1
@@ -71,6 +71,9 @@ def load_library():
     lib.plk_edge_pair_sums.argtypes = [vp, vp, vp, vp]
     lib.plk_rate_matrix_sens.argtypes = [vp, vp, vp]
     lib.plk_rate_matrix_chain.argtypes = [ci, vp, ci, ctypes.c_double, ci, vp, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
+    lib.plk_mixture_sens.argtypes = [vp, vp, vp]
+    lib.plk_mixture_chain.argtypes = [ci, ci, vp, vp, ctypes.c_double, ctypes.c_double, ci, vp, vp, vp, vp, vp, vp,
+                                      ctypes.POINTER(ci), ctypes.c_char_p, ctypes.c_size_t]
     lib.plk_get_transition_matrices.argtypes = [vp, vp]
     lib.plk_get_info.argtypes = [vp, ci, ctypes.POINTER(cl)]
     lib.plk_set_option.argtypes = [vp, ci, cl]
@@ -298,6 +301,14 @@ class Engine:
         root = np.zeros((self.k, 2)) if want_root else None
         self._check(self._lib.plk_rate_matrix_sens(self._h, _ptr(G), _ptr(root)))
         return G, root
+
+    def mixture_sens(self):
+        """gradient of the weighted log likelihood in the category priors and rates, taken as independent
+        (include/plk.h:plk_mixture_sens) -> (prior [C][2], rate [C][2]), double-double entries"""
+        prior = np.zeros((self.C, 2))
+        rate = np.zeros((self.C, 2))
+        self._check(self._lib.plk_mixture_sens(self._h, _ptr(prior), _ptr(rate)))
+        return prior, rate
 
     def transition_matrices(self):
         P = np.empty((self.C, self.E, self.k, self.k))
