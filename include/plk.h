@@ -107,13 +107,18 @@ int plk_set_patterns_codes(plk_engine *h, long S, const uint8_t *codes, int wher
 int plk_set_patterns_dense(plk_engine *h, long S, const double *B, int where);
 
 /* Optional per-site weights for the aggregated outputs (NULL = all 1).
- * A weight of exactly 0 still evaluates the site; selection is the caller's. */
+ * A weight of exactly 0 still evaluates the site; selection is the caller's.  In the sums of plk_ll, plk_deriv and
+ * plk_marginal a weight of exactly 0 drops the site's term whatever the term is: a site of likelihood 0 (ll -inf,
+ * derivatives and marginals inf or NaN) under weight 0 leaves those sums equal to the sums of the alignment without the
+ * site.  plk_edge_expect(_multi), plk_hess and plk_second_order make no such promise: where one of their sums
+ * multiplies the weight into a term that is not finite, that sum is NaN whatever the weight. */
 int plk_set_site_weights(plk_engine *h, const double *w, int where);
 
 /*
  * Log likelihoods.  site_ll_out: NULL or S doubles (host/device per `where`).
  * sum_out: NULL or 2 doubles {hi, lo}: sum_s w_s * ll_s as an unevaluated
- * double-double (hi + lo), summed in a fixed order (deterministic).
+ * double-double (hi + lo), summed in a fixed order (deterministic).  A site of weight exactly 0 adds nothing to the
+ * sum, also where its ll is -inf (likelihood 0).
  */
 int plk_ll(plk_engine *h, double *site_ll_out, int where, double *sum_out);
 
@@ -132,7 +137,8 @@ int plk_set_stream(plk_engine *h, void *hip_stream);
  * Edge-rate derivatives d ll_s / d edge_rate_coefficient_e (CSR edge order).
  * edge_mask: NULL (all) or E ints, nonzero = requested.
  * site_edge_out: NULL or [S][E] doubles, host; unrequested edges get 0.
- * edge_sums_out: NULL or [E][2] double-double sums of w_s * d_{s,e}.
+ * edge_sums_out: NULL or [E][2] double-double sums of w_s * d_{s,e}; a site of weight exactly 0 adds nothing, also
+ * where its derivatives are not finite (likelihood 0).
  */
 int plk_deriv(plk_engine *h, const int *edge_mask,
               double *site_edge_out, double *edge_sums_out);
@@ -140,7 +146,8 @@ int plk_deriv(plk_engine *h, const int *edge_mask,
 /*
  * Marginal state distributions.  node_mask: NULL (all) or N ints.
  * site_out: NULL or [S][N][k] doubles, host (unrequested nodes get 0).
- * sums_out: NULL or [N][k][2] double-double sums over sites of w_s * m_{s,a,i}.
+ * sums_out: NULL or [N][k][2] double-double sums over sites of w_s * m_{s,a,i}; a site of weight exactly 0 adds
+ * nothing, also where its marginals are not finite (likelihood 0), whether or not site_out is asked for.
  */
 int plk_marginal(plk_engine *h, const int *node_mask,
                  double *site_out, double *sums_out);
@@ -360,8 +367,13 @@ enum {
                                        plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens or plk_mixture_sens
                                        (0 when it could not be taken); for tools/time_rate_matrix_deriv.py and
                                        tools/time_mixture_deriv.py */
-    PLK_INFO_MIXTURE_SENS_KERNEL = 16 /* up pass of the last plk_mixture_sens: 0 = none yet, 1 = the k = 4 kernel (compact
+    PLK_INFO_MIXTURE_SENS_KERNEL = 16, /* up pass of the last plk_mixture_sens: 0 = none yet, 1 = the k = 4 kernel (compact
                                        codes, at most 4 categories), 2 = generic */
+    PLK_INFO_UP4_PATH = 17          /* k = 4 up pass of the last deriv, marginal or expectation query, a bit mask: 1 = node-visit
+                                       pass (k_up4_nodes; otherwise k_up4), 2 = with pair messages (at least one two-leaf node
+                                       read from a table), 4 = with rebuilt tables (at least one node whose vector is the
+                                       product of two table rows), 8 = two-leaf nodes finished inside their parent's visit
+                                       (one rate category); 0 when another kernel family ran */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused

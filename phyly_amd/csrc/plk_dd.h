@@ -65,6 +65,16 @@ __host__ __device__ static inline dd dd_mul_d(dd x, double y)
     return dd_quick_two_sum(p.hi, p.lo);
 }
 
+/* term of a weighted site sum: w[s] * x, or x without weights.  A site of weight 0 contributes exactly 0 whatever x
+ * is: the log likelihood of a site of likelihood 0 is -inf and its derivatives and marginals are inf or NaN, and a zero
+ * weight takes the site out of the sum as if the alignment did not hold it */
+__host__ __device__ static inline dd dd_weighted(const double *w, long s, double x)
+{
+    if (!w) return dd_make(x, 0.0);
+    const double ws = w[s];
+    return ws == 0.0 ? dd_make(0.0, 0.0) : dd_two_prod(ws, x);
+}
+
 /* x * 2^e, exact */
 __host__ __device__ static inline dd dd_ldexp(dd x, int e)
 {

@@ -162,6 +162,7 @@ struct plk_engine {
     long info_pair_sums_kernel = 0, info_query_ns = 0;
     double *d_mixD = nullptr; size_t mixd_cap = 0;   /* plk_mixture_sens: its direction matrices t_e Qn P[c][e] (the query's own; d_dP is not touched) */
     long info_mixture_sens_kernel = 0;
+    long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
     long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
@@ -780,7 +781,7 @@ __global__ void k_wsum_rows(long S, long row_stride, const double *__restrict__ 
     dd acc = dd_make(0.0, 0.0);
     for (long s = lo + threadIdx.x; s < hi; s += blockDim.x) {
         double x = X[(size_t)row * row_stride + s];
-        dd t = w ? dd_two_prod(w[s], x) : dd_make(x, 0.0);
+        dd t = dd_weighted(w, s, x);
         acc = dd_add(acc, t);
     }
     dd r = dd_block_sum(acc);
@@ -952,7 +953,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_ll_generic(GenArgs a)
     if (valid && a.site_ll) a.site_ll[s] = ll;
     if (a.partial) {
         dd v = dd_make(0.0, 0.0);
-        if (valid) v = a.w ? dd_two_prod(a.w[s], ll) : dd_make(ll, 0.0);
+        if (valid) v = dd_weighted(a.w, s, ll);
         dd r = dd_block_sum(v);
         if (tid == 0) a.partial[blockIdx.x] = r;
     }
@@ -1471,6 +1472,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_PAIR_SUMS_KERNEL: *out = h->info_pair_sums_kernel; return PLK_OK;
     case PLK_INFO_LAST_QUERY_NS: *out = h->info_query_ns; return PLK_OK;
     case PLK_INFO_MIXTURE_SENS_KERNEL: *out = h->info_mixture_sens_kernel; return PLK_OK;
+    case PLK_INFO_UP4_PATH: *out = h->info_up4_path; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && ((h->fmt_pt && h->fmt_kind == 1) || (h->vec_pt && h->fmt_kind == 4)) ? h->fpt.npairs : 0; return PLK_OK;
@@ -2693,15 +2695,17 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     const std::vector<plk_op4> &ops2 = ch2.ops;
     const int first_slot2 = ch2.first_slot, first_row2 = ch2.first_row;
     PlkUpNodes un4;
+    const bool inline4 = npairs4 > 0 && C == 1 && !(h->opt_up_nodes & 8);      /* two-leaf nodes finish inside their parent's visit */
     if (nodes4) {
         if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
         plk_up_nodes_build(N, h->indptr.data(), h->indices.data(), h->preorder.data(), h->node_has_data.data(), edge_tip.data(),
                            node_int.data(), node_scale.data(), edge_mask, un4, npairs4 ? pair_of.data() : nullptr,
-                           any_rebuild ? rebuild_n.data() : nullptr, npairs4 > 0 && C == 1 && !(h->opt_up_nodes & 8));
+                           any_rebuild ? rebuild_n.data() : nullptr, inline4);
         const std::string bad = plk_up_nodes_check(N, E, h->indptr.data(), h->indices.data(), un4, nin, ntips, nsc, npairs4, edge_tip.data(),
                                                    any_rebuild ? rebuild_tab.data() : nullptr, pair_of.data());
         if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
     }
+    if (!ps) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
     const int *d_vis4 = nullptr, *d_ptabs = nullptr, *d_rebuild = nullptr;
     double *d_tip4 = nullptr, *d_dtip4 = nullptr, *d_ptab4 = nullptr;
     size_t nptab = 0;
@@ -3019,6 +3023,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
     if (!d_M_in && !ps && (rc = ensure_dP(h))) return rc;
     const double *d_M = d_M_in ? d_M_in : h->d_dP;
+    if (!ps) h->info_up4_path = 0;
     if (ps) {
         /* the k = 4 kernel takes compact codes and at most four categories; everything else the generic kernel below */
         long &info = ps->mix_D ? h->info_mixture_sens_kernel : h->info_pair_sums_kernel;

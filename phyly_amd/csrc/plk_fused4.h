@@ -259,7 +259,7 @@ __global__ __launch_bounds__(PLK_TILE) void k_ll_fused4(FusedArgs a)
         const double ll = have[j] ? log(sum[j]) + (double)Eexp[j] * 0.6931471805599453094 : -INFINITY;
         if (s < a.S) {
             if (a.site_ll) a.site_ll[s] = ll;
-            v = dd_add(v, a.w ? dd_two_prod(a.w[s], ll) : dd_make(ll, 0.0));
+            v = dd_add(v, dd_weighted(a.w, s, ll));
         }
     }
     if (a.partial) {

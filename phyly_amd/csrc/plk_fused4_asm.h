@@ -507,7 +507,7 @@ __global__ __launch_bounds__(PLK_TILE) void k_ll_fused4_asm(FusedAsmArgs aa)
     dd v = dd_make(0.0, 0.0);
     if (s < a.S) {
         if (a.site_ll) a.site_ll[s] = ll;
-        v = a.w ? dd_two_prod(a.w[s], ll) : dd_make(ll, 0.0);
+        v = dd_weighted(a.w, s, ll);
     }
     if (a.partial) {
         dd r = dd_block_sum(v);
@@ -674,7 +674,7 @@ __global__ __launch_bounds__(TILE) void k_ll_fused4_asm_pt(FusedPTArgs aa)
         dd v = dd_make(0.0, 0.0);
         if (s < a.S) {
             if (a.site_ll) a.site_ll[s] = ll;
-            v = a.w ? dd_two_prod(a.w[s], ll) : dd_make(ll, 0.0);
+            v = dd_weighted(a.w, s, ll);
         }
         if (a.partial) {
             dd r = dd_block_sum(v);

@@ -223,7 +223,7 @@ __device__ __forceinline__ void ll_mfma_body(const MfmaArgs &a)
     dd v = dd_make(0.0, 0.0);
     if (valid && g == 0) {
         if (a.site_ll) a.site_ll[site] = ll;
-        v = a.w ? dd_two_prod(a.w[site], ll) : dd_make(ll, 0.0);
+        v = dd_weighted(a.w, site, ll);
     }
     if (a.partial) {
         dd r = dd_block_sum(v);
@@ -371,7 +371,7 @@ __device__ __forceinline__ void ll_mfma_body2(const MfmaArgs &a)
         const double ll = have[j] ? log(sum[j]) + (double)Eexp[j] * 0.6931471805599453094 : -INFINITY;
         if (site[j] < a.S && g == 0) {
             if (a.site_ll) a.site_ll[site[j]] = ll;
-            v = dd_add(v, a.w ? dd_two_prod(a.w[site[j]], ll) : dd_make(ll, 0.0));
+            v = dd_add(v, dd_weighted(a.w, site[j], ll));
         }
     }
     if (a.partial) {

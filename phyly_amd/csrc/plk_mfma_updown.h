@@ -375,7 +375,7 @@ __global__ __launch_bounds__(MF_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
  * row of 16 lanes; lane 15 of row g stores the states g + 4r.  All lanes take part. */
 #define MF_OUT_M(NODE, MACC)                                                                              \
     do { if (a.MVS) {                                                                                      \
-             const double ws_ = valid ? (a.wsite ? a.wsite[sl] : 1.0) * inv : 0.0;                        \
+             const double ws_ = valid && !(a.wsite && a.wsite[sl] == 0.0) ? (a.wsite ? a.wsite[sl] : 1.0) * inv : 0.0;                        \
              const size_t nwv_ = (size_t)gridDim.x * (MF_BLOCK / 64), wv_ = (size_t)blockIdx.x * (MF_BLOCK / 64) + wave; \
              _Pragma("unroll") for (int r = 0; r < R; r++) {                                               \
                  const double t_ = row16_sum(MACC[r] * ws_);                                               \

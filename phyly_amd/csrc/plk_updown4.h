@@ -382,7 +382,7 @@ __device__ static inline void ud4_pre_step(const Up4Args &a, int c, const double
 __device__ static inline void ud4_out_m(const Up4Args &a, size_t n, long sl, bool valid, int node, const v4 &m, double inv)
 {
     if (a.MVS) {
-        const double ws = valid ? (a.wsite ? a.wsite[sl] : 1.0) * inv : 0.0;
+        const double ws = valid && !(a.wsite && a.wsite[sl] == 0.0) ? (a.wsite ? a.wsite[sl] : 1.0) * inv : 0.0;
         const double s0 = wave64_sum_lane63(m.a * ws), s1 = wave64_sum_lane63(m.b * ws);
         const double s2 = wave64_sum_lane63(m.c * ws), s3 = wave64_sum_lane63(m.d * ws);
         if ((threadIdx.x & 63) == 63) {

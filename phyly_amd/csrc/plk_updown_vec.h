@@ -320,7 +320,7 @@ __global__ __launch_bounds__(UDV_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
         }
         if (MARG && vis[6]) {
             if (a.MVS) {
-                const double ws = valid ? (a.wsite ? a.wsite[sl] : 1.0) * inv : 0.0;
+                const double ws = valid && !(a.wsite && a.wsite[sl] == 0.0) ? (a.wsite ? a.wsite[sl] : 1.0) * inv : 0.0;
 #pragma unroll
                 for (int i = 0; i < K; i++) {
                     const double t_ = wave64_sum_lane63(macc[i] * ws);
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(UDV_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
                  const double t_ = (VAL); *dp_ = (first_cat ? t_ : *dp_ + t_) * (last_cat ? inv : 1.0); } } while (0)
 #define UDV_OUT_M(NODE, FB, LB)                                                                           \
             do { if (a.MVS) {      /* site sums only: the wave's weighted sum of this category's term, accumulated per wave */ \
-                     const double wi_ = valid ? (a.wsite ? a.wsite[sl] : 1.0) * inv * pc : 0.0;          \
+                     const double wi_ = valid && !(a.wsite && a.wsite[sl] == 0.0) ? (a.wsite ? a.wsite[sl] : 1.0) * inv * pc : 0.0;          \
                      double v_[K];                                                                        \
                      _Pragma("unroll") for (int i = 0; i < K; i++) v_[i] = wi_ * FB[i] * LB[i];           \
                      const double t_ = udv_state_sums<K>(v_, strip, threadIdx.x & 63);                   \
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(UDV_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4)
             /* marginal of a leaf that observes state ST_ at this site: one non-zero entry FS_ = F(ST_) (B = 1 there) */
 #define UDV_OUT_M1(NODE, ST_, FS_)                                                                        \
             do { if (a.MVS) {                                                                             \
-                     const double x_ = (valid ? (a.wsite ? a.wsite[sl] : 1.0) * inv * pc : 0.0) * (FS_);  \
+                     const double x_ = (valid && !(a.wsite && a.wsite[sl] == 0.0) ? (a.wsite ? a.wsite[sl] : 1.0) * inv * pc : 0.0) * (FS_);  \
                      double v_[K];                                                                        \
                      _Pragma("unroll") for (int i = 0; i < K; i++) v_[i] = (ST_) == i ? x_ : 0.0;         \
                      const double t_ = udv_state_sums<K>(v_, strip, threadIdx.x & 63);                   \

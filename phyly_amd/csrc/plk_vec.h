@@ -215,7 +215,7 @@ __device__ __forceinline__ void k_ll_vec_body(const VecArgs &a)
     if (valid && a.site_ll) a.site_ll[s] = ll;
     if (a.partial) {
         dd v = dd_make(0.0, 0.0);
-        if (valid) v = a.w ? dd_two_prod(a.w[s], ll) : dd_make(ll, 0.0);
+        if (valid) v = dd_weighted(a.w, s, ll);
         dd r = dd_block_sum(v);
         if (tid == 0) a.partial[blockIdx.x] = r;
     }

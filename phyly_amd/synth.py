@@ -155,13 +155,21 @@ class _K0Mixture(ctypes.Structure):
 
 
 def k0_prepare(Q, mixture, use_eq_divisor=True, divisor=1.0, need_pi=True):
-    """Product host K0 (phyly_amd/csrc/host_k0.c) through ctypes."""
+    """Product host K0 (phyly_amd/csrc/host_k0.c) through ctypes.  mixture: None, a gamma dict (gamma_categories,
+    gamma_shape, invariable_prior) or an explicit dict(rates, prior): the custom mixture of host_k0.h."""
     lib = _engine.load_library()
     Q = np.ascontiguousarray(Q, dtype=np.float64)
     k = Q.shape[0]
+    dp = ctypes.POINTER(ctypes.c_double)
     mix = _K0Mixture()
     if mixture is None:
         mix.mode, mix.n = 1, 1
+    elif "rates" in mixture:
+        r_in, p_in = np.array(mixture["rates"], dtype=np.float64), np.array(mixture["prior"], dtype=np.float64)
+        if r_in.shape != p_in.shape or r_in.ndim != 1:
+            raise ValueError("one prior per rate")
+        mix.mode, mix.n = 2, len(r_in)
+        mix.rates, mix.prior = r_in.ctypes.data_as(dp), p_in.ctypes.data_as(dp)      # r_in, p_in live until the call below
     else:
         mix.mode = 4
         mix.n = int(mixture["gamma_categories"])
@@ -174,7 +182,6 @@ def k0_prepare(Q, mixture, use_eq_divisor=True, divisor=1.0, need_pi=True):
     pi = np.zeros(k)
     Qn = np.zeros((k, k))
     Qn_lo = np.zeros((k, k))
-    dp = ctypes.POINTER(ctypes.c_double)
     lib.arbplf_k0_prepare.argtypes = [ctypes.c_int, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                       ctypes.POINTER(_K0Mixture), dp, dp, dp, dp, dp]
     rc = lib.arbplf_k0_prepare(k, Q.ctypes.data_as(dp), int(use_eq_divisor), float(divisor), int(need_pi),

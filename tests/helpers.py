@@ -60,6 +60,13 @@ class CustomWorkload(synth.Workload):
             return _E.ROOT_CUSTOM, self.root_custom
         return (_E.ROOT_UNIFORM if self.root == "uniform" else _E.ROOT_NONE), None
 
+    def prepare(self):
+        """K0 through the product host layer; an explicit rate_mixture (rates and prior as given) goes in as the custom
+        mixture of host_k0.h"""
+        if self.k0 is None and getattr(self, "rate_mixture", None) is not None:
+            self.k0 = synth.k0_prepare(self.Q, self.rate_mixture, True, 1.0, True)
+        return synth.Workload.prepare(self)
+
     def setup_engine(self, eng):
         k0 = self.prepare()
         mode, rw = self.root_engine()
@@ -68,6 +75,8 @@ class CustomWorkload(synth.Workload):
 
     def json_model(self, codes_host):
         md = synth.Workload.json_model(self, codes_host)
+        if getattr(self, "rate_mixture", None) is not None:
+            md["rate_mixture"] = dict(rates=list(self.rate_mixture["rates"]), prior=list(self.rate_mixture["prior"]))
         if self.root == "none":
             del md["root_prior"]
         elif self.root == "uniform":
@@ -78,7 +87,8 @@ class CustomWorkload(synth.Workload):
 
     def _observe(self, codes, salt):
         extra = self.nchar - self.k - 1
-        if not extra and not self.internal_data:
+        data_nodes = getattr(self, "data_nodes", None)
+        if not extra and not self.internal_data and not data_nodes:
             return codes
         rng = np.random.default_rng([self.seed, salt, codes.shape[1]])
         codes = codes.copy()
@@ -89,6 +99,8 @@ class CustomWorkload(synth.Workload):
         if self.internal_data:
             inner = np.flatnonzero(~leaf)[::3]
             codes[inner] = rng.integers(0, self.nchar, (len(inner), codes.shape[1]))
+        if data_nodes:
+            codes[list(data_nodes)] = rng.integers(0, self.nchar, (len(data_nodes), codes.shape[1]))
         return codes
 
     def simulate(self, S, site0=0, device=None):
@@ -131,10 +143,109 @@ def custom_workload(k, T, *, C, root, seed, tree="yule", invariable=0.0, ambigui
     return wl
 
 
+def tree_workload(k, edges, edge_rates, *, root, seed, rate_mixture=None, gamma=None, nchar=None, data_nodes=(), name=None):
+    """custom_workload on an explicit tree: `edges` [[parent, child], ...] of any shape (unary nodes, multifurcations),
+    one rate per edge (0 allowed), either an explicit `rate_mixture` dict(rates, prior) (unequal priors, rate-0
+    categories), a `gamma` dict as in synth.Workload.mixture, or neither (one category); `nchar` character definitions
+    (identity, the missing row, then rows with fractional entries); `data_nodes` are the internal nodes that carry a
+    code at every site.  Q is nonreversible_rates(k)."""
+    if root not in ROOTS:
+        raise ValueError(root)
+    if rate_mixture is not None and gamma is not None:
+        raise ValueError("one mixture form at most")
+    nchar = k + 1 if nchar is None else nchar
+    rng = np.random.default_rng(seed)
+    wl = CustomWorkload(T=2, k=k, tree="balanced", model="aa20", seed=seed)       # a shell; tree and model replaced below
+    wl.name = name or "tree k=%d E=%d root=%s" % (k, len(edges), root)
+    wl.edges = [list(map(int, e)) for e in edges]
+    wl.E, wl.N = len(edges), len(edges) + 1
+    wl.edge_rates = [float(r) for r in edge_rates]
+    if len(wl.edge_rates) != wl.E:
+        raise ValueError("one rate per edge")
+    wl.indptr, wl.indices, wl.preorder, wl.order = synth.csr_from_edges(wl.edges)
+    wl.T = int(np.sum(wl.indptr[1:] == wl.indptr[:-1]))
+    wl.edge_rates_csr = np.zeros(wl.E)
+    wl.edge_rates_csr[wl.order] = wl.edge_rates
+    wl.Q = nonreversible_rates(k, rng).tolist()
+    wl.mixture = dict(gamma) if gamma is not None else None
+    wl.rate_mixture = rate_mixture
+    amb = rng.choice([0.0, 0.25, 0.5, 1.0], size=(nchar - k - 1, k))
+    amb[np.arange(nchar - k - 1), rng.integers(0, k, nchar - k - 1)] = 0.75            # never an all-zero row
+    wl.defs = np.vstack([np.eye(k), np.ones((1, k)), amb])
+    wl.nchar = nchar
+    wl.root = root
+    wl.root_custom = rng.uniform(0.05, 1.0, k) if root == "custom" else None
+    wl.internal_data = False
+    wl.data_nodes = tuple(data_nodes)
+    if any(wl.indptr[a + 1] == wl.indptr[a] for a in wl.data_nodes):
+        raise ValueError("data_nodes are internal nodes")
+    wl.k0 = None
+    wl._cum = None
+    return wl
+
+
+# The irregular tree of K4_MODELS "irregular" and "wide": 13 leaves (0..12), root 13 with three children (14, 15, leaf 12);
+# 14 has three children (16, leaves 4 and 5); 15 is unary (child 19); two cherry parents, 23 (leaves 0, 1; no data; edge
+# rates 0.04 and 0.3) and 18 (leaves 2, 3; data of its own); 17 carries data too; the edge 20 -> 21 has rate 0.
+IRREGULAR_EDGES = [[13, 14], [13, 15], [13, 12], [14, 16], [14, 4], [14, 5], [16, 6], [16, 17], [17, 7], [17, 18], [18, 2], [18, 3],
+                   [15, 19], [19, 8], [19, 20], [20, 9], [20, 21], [21, 10], [21, 22], [22, 11], [22, 23], [23, 0], [23, 1]]
+IRREGULAR_RATES = [0.11, 0.07, 0.23, 0.05, 0.31, 0.02, 0.17, 0.09, 0.13, 0.06, 0.21, 0.08,
+                   0.12, 0.27, 0.03, 0.19, 0.0, 0.14, 0.1, 0.16, 0.22, 0.04, 0.3]
+IRREGULAR_CHERRY = (0, 1)            # leaves of the data-free cherry whose edge rates differ 7.5 x
+IRREGULAR_DATA_NODES = (18, 17)
+
+# k = 4 models for tests/test_gpu_k4_variants.py (and the CPU check in tests/test_kernel_family_models.py): what
+# the engine-level k = 4 tests on synth.Workload gtr_g4 / hky85 cannot see.  See DESIGN.md section 2.
+K4_MODELS = ("irregular", "balanced32", "balanced64", "wide")
+
+
+def k4_workload(name):
+    """irregular:  the irregular tree, rate_mixture rates [0, 0.4, 1.1, 2.7] with prior [0.15, 0.4, 0.05, 0.4], custom
+                   root prior, 7 character definitions (identity, missing, two fractional rows)
+    balanced32: make_tree(32, "balanced") (stack need 4, the pair-table limit), one rate category, no root prior
+    balanced64: make_tree(64, "balanced") (stack need 5: no pair tables), gamma 4 + invariable (C = 5), uniform root prior
+    wide:       the irregular tree with 17 definitions (8-bit staged codes, no pair tables or pair messages), two
+                categories with prior [0.3, 0.7], equilibrium root prior"""
+    if name == "irregular":
+        return tree_workload(4, IRREGULAR_EDGES, IRREGULAR_RATES, root="custom", seed=4401, nchar=7, data_nodes=IRREGULAR_DATA_NODES,
+                             rate_mixture=dict(rates=[0.0, 0.4, 1.1, 2.7], prior=[0.15, 0.4, 0.05, 0.4]), name="k4 irregular")
+    if name == "wide":
+        return tree_workload(4, IRREGULAR_EDGES, IRREGULAR_RATES, root="equilibrium", seed=4404, nchar=17, data_nodes=IRREGULAR_DATA_NODES,
+                             rate_mixture=dict(rates=[0.5, 1.6], prior=[0.3, 0.7]), name="k4 wide")
+    if name in ("balanced32", "balanced64"):
+        T = int(name[8:])
+        shell = synth.Workload(T=T, k=4, tree="balanced", model="hky85", seed=4400 + T)
+        gamma = dict(gamma_shape=0.8, gamma_categories=4, invariable_prior=0.1) if T == 64 else None     # priors 4 x 0.225, 0.1
+        return tree_workload(4, shell.edges, shell.edge_rates, root="none" if T == 32 else "uniform", seed=4400 + T, gamma=gamma,
+                             name="k4 " + name)
+    raise ValueError(name)
+
+
+def cherry_with_unequal_edges(wl, min_ratio=2.0):
+    """(leaf b, leaf c) of the data-free cherry of wl whose two edge rates differ most, by at least min_ratio"""
+    best = None
+    for a in range(wl.N):
+        e0, e1 = wl.indptr[a], wl.indptr[a + 1]
+        if e1 - e0 != 2 or a in getattr(wl, "data_nodes", ()):
+            continue
+        b, c = int(wl.indices[e0]), int(wl.indices[e0 + 1])
+        if wl.indptr[b + 1] != wl.indptr[b] or wl.indptr[c + 1] != wl.indptr[c]:
+            continue
+        r0, r1 = wl.edge_rates_csr[e0], wl.edge_rates_csr[e0 + 1]
+        ratio = max(r0, r1) / min(r0, r1)
+        if best is None or ratio > best[0]:
+            best = (ratio, b, c)
+    assert best is not None and best[0] >= min_ratio, best
+    return best[1], best[2]
+
+
 # One model per state count for tests/test_gpu_kernel_families.py (and the CPU check that these models can tell a wrong
 # kernel from a right one, tests/test_kernel_family_models.py): every k names the padded width or row-tile count it
 # exercises.  C * E * k^3 stays small at large k: the oracle's binary128 exponentials dominate the cost.
 FAMILY_MODELS = {
+    2: dict(T=10, C=3, invariable=0.2, root="none", ambiguity_rows=1, seed=4112),                   # generic <2>; the seed: a
+                                                                                                  # pi with max / min = 2.6 (4102: 1.25)
+    3: dict(T=10, C=3, invariable=0.15, root="custom", ambiguity_rows=2, internal_data=True),       # generic <4>
     5: dict(T=14, C=4, invariable=0.2, root="custom", ambiguity_rows=2, internal_data=True),      # generic <8>
     8: dict(T=12, C=3, root="none"),
     9: dict(T=12, C=3, invariable=0.15, root="uniform"),                                          # vec K = 16 / MFMA T = 1
@@ -155,4 +266,4 @@ FAMILY_MODELS = {
 
 def family_workload(k):
     spec = dict(FAMILY_MODELS[k])
-    return custom_workload(k, spec.pop("T"), C=spec.pop("C"), root=spec.pop("root"), seed=4100 + k, **spec)
+    return custom_workload(k, spec.pop("T"), C=spec.pop("C"), root=spec.pop("root"), seed=spec.pop("seed", 4100 + k), **spec)
