@@ -369,11 +369,15 @@ enum {
                                        tools/time_mixture_deriv.py */
     PLK_INFO_MIXTURE_SENS_KERNEL = 16, /* up pass of the last plk_mixture_sens: 0 = none yet, 1 = the k = 4 kernel (compact
                                        codes, at most 4 categories), 2 = generic */
-    PLK_INFO_UP4_PATH = 17          /* k = 4 up pass of the last deriv, marginal or expectation query, a bit mask: 1 = node-visit
+    PLK_INFO_UP4_PATH = 17,         /* k = 4 up pass of the last deriv, marginal or expectation query, a bit mask: 1 = node-visit
                                        pass (k_up4_nodes; otherwise k_up4), 2 = with pair messages (at least one two-leaf node
                                        read from a table), 4 = with rebuilt tables (at least one node whose vector is the
                                        product of two table rows), 8 = two-leaf nodes finished inside their parent's visit
                                        (one rate category); 0 when another kernel family ran */
+    PLK_INFO_DOWN4_KERNEL = 18      /* k = 4 down pass of the last query that ran on the k = 4 up/down kernels (deriv, marginal,
+                                       expectations, and the pair-sum and mixture-gradient passes): 4, 8 or 16 = k_down_fused4<D>
+                                       with a register stack of that depth, 0 = k_down_store4 (the staged code rows do not fit
+                                       the LDS, or the tree needs more than 16 slots) or no such query yet */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused

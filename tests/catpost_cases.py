@@ -108,6 +108,54 @@ def oracle_for(oracle, wl, codes, precise=2, nthreads=0):
     return m, w, post, rate, sll
 
 
+# ---------------------------------------------------------------- the engine against these values (GPU tests)
+def _sum_ld(hl):
+    return np.longdouble(hl[0]) + np.longdouble(hl[1])
+
+
+def compare(tag, got_post, got_rate, post, rate, tol):
+    """every entry against the bound; prints the largest error in units of the bound before asserting"""
+    e_post = np.abs(got_post.astype(np.longdouble) - post) - 1e-300
+    e_rate = np.abs(got_rate.astype(np.longdouble) - rate)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r_post = float(np.max(np.where(post > 0, e_post / post, np.where(got_post == 0, 0.0, np.inf))))
+    r_rate = float(np.max(e_rate / rate))
+    print("%s: max rel err post %.3g rate %.3g (bound %.3g)" % (tag, r_post, r_rate, tol))
+    assert r_post <= tol and r_rate <= tol
+    C = post.shape[1]
+    assert np.max(np.abs(got_post.sum(axis=1) - 1)) <= (C + 2) * 2.0 ** -52
+    return max(r_post, r_rate)
+
+
+def check_engine(eng, oracle, wl, codes, tag, kernel, precise=2, extra_tol=0.0, weights=(False, True), ref=None, site_weights=None):
+    """plk_cat_posterior (with its log-likelihood by-product) on the patterns the engine holds against oracle_for: every
+    entry, the row sums, the weighted sums.  ref: (m, w, post, rate, sll) built earlier for these codes; site_weights: the
+    weights of the weighted pass (default: uniform(0.25, 3))"""
+    m, w, post, rate, sll = ref if ref is not None else oracle_for(oracle, wl, codes, precise=precise)
+    C, S = int(w["C"]), codes.shape[1]
+    tol = rtol(wl.E, wl.k, C) + extra_tol
+    assert np.array_equal(np.asarray(w["cat_prior"]) == 0, wl.prepare()["cat_prior"] == 0)
+    for weighted in weights:
+        ws = (site_weights if site_weights is not None else np.random.default_rng(S + C).uniform(0.25, 3.0, S)) if weighted else None
+        eng.set_site_weights(ws)
+        gp, gr, psum, rsum, gll, lsum = eng.cat_posterior(want_ll=True)
+        assert eng.info(_E.INFO_CAT_POSTERIOR_KERNEL) == kernel
+        compare("%s weighted=%s" % (tag, weighted), gp, gr, post, rate, tol)
+        assert np.all(gp[:, np.asarray(w["cat_prior"]) == 0] == 0)
+        wl_ = np.ones(S, dtype=np.longdouble) if ws is None else ws.astype(np.longdouble)
+        for c in range(C):
+            want = np.sum(wl_ * post[:, c])
+            assert abs(_sum_ld(psum[c]) - want) <= tol * want + 1e-300
+        want = np.sum(wl_ * rate)
+        assert abs(_sum_ld(rsum) - want) <= tol * want
+        # log likelihood: the relative bound of L is an absolute one of log L, plus the rounding of the logarithm itself
+        ll_bound = tol + 2.0 ** -52 * np.abs(sll)
+        assert np.all(np.abs(gll.astype(np.longdouble) - sll) <= ll_bound)
+        assert abs(_sum_ld(lsum) - np.sum(wl_ * sll)) <= np.sum(wl_ * ll_bound)
+    eng.set_site_weights(None)
+    return gp, gr, post, rate
+
+
 def document_table(oracle, doc, what):
     """the table arbplf-cat-posterior ("cat_posterior") or arbplf-site-rate ("site_rate") must print for a document"""
     m = oracle.parse_model(doc["model_and_data"])

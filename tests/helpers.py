@@ -221,6 +221,44 @@ def k4_workload(name):
     raise ValueError(name)
 
 
+# Models for tests/test_gpu_query_variants.py beyond K4_MODELS (which other tests enumerate and which stays as it is)
+QUERY_MODEL = "balanced64g3"
+
+
+def query_workload(name):
+    """the models of tests/test_gpu_query_variants.py: K4_MODELS and
+    balanced64g3: the balanced64 tree (stack need 5) with a 3-category gamma mixture and the uniform root prior: at most 4
+                  categories, so the k = 4 pair-sum and mixture-gradient kernels take it, after k_down_fused4<8>"""
+    if name == QUERY_MODEL:
+        shell = synth.Workload(T=64, k=4, tree="balanced", model="hky85", seed=4464)
+        return tree_workload(4, shell.edges, shell.edge_rates, root="uniform", seed=4467, gamma=dict(gamma_shape=0.6, gamma_categories=3),
+                             name="k4 " + name)
+    return k4_workload(name)
+
+
+def numeric_divisor_doc(wl, codes_host):
+    """wl.json_model with the rate divisor replaced by a fixed number near the mean exit rate of Q (three decimals): the
+    one-category models of mixsens_cases.expectations need a divisor that does not depend on the mixture"""
+    md = wl.json_model(codes_host)
+    Q = np.array(wl.Q, dtype=float)
+    np.fill_diagonal(Q, 0.0)
+    md["rate_divisor"] = round(float(np.sum(Q)) / wl.k, 3)
+    return md
+
+
+def deep_workload(rate_mixture=None):
+    """the smallest input that reaches the 16-slot k = 4 instantiations: the full binary tree over
+    512 unary nodes with one leaf each (N = 1535, stack need 9) and ONE character definition, the all-ones row.  Nodes
+    0..510 are the binary tree in heap order, 511..1022 the unary nodes, 1023..1534 the leaves."""
+    edges = [[(i - 1) // 2, i] for i in range(1, 1023)] + [[511 + i, 1023 + i] for i in range(512)]
+    rng = np.random.default_rng(4416)
+    rates = rng.uniform(0.01, 0.3, len(edges))
+    rates[rng.choice(len(edges), 20, replace=False)] = 0.0
+    wl = tree_workload(4, edges, rates, root="custom", seed=4416, rate_mixture=rate_mixture, name="k4 deep")
+    wl.defs, wl.nchar = np.ones((1, 4)), 1
+    return wl
+
+
 def cherry_with_unequal_edges(wl, min_ratio=2.0):
     """(leaf b, leaf c) of the data-free cherry of wl whose two edge rates differ most, by at least min_ratio"""
     best = None

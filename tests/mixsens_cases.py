@@ -139,24 +139,29 @@ def one_category(md, r):
     return md1
 
 
-def _site_ll(oracle, md):
+def _site_ll(oracle, md, cache=None, key=None):
+    if cache is not None and key in cache:
+        return cache[key]
     m = oracle.parse_model(md)
     ll, _ = oracle.site_ll(m, oracle.prepare(m), B=m.B, precise=2)
-    return np.asarray(ll, dtype=LD)
+    ll = np.asarray(ll, dtype=LD)
+    if cache is not None:
+        cache[key] = ll
+    return ll
 
 
 def _fd4(f0, f1, f2, f3, h):
     return (-11 * f0 + 18 * f1 - 9 * f2 + 2 * f3) / (6 * LD(h))
 
 
-def zero_rate_term(oracle, md, ll_s, wt_p, h0=FD_H):
+def zero_rate_term(oracle, md, ll_s, wt_p, h0=FD_H, cache=None):
     """sum_s wt_p[s] d/dr exp(ll_{s,c}(r) - ll_s) at r = 0 by one-sided 4-point differences at steps h and h / 2
     -> (value at h / 2, |value at h / 2 - value at h|, h).  Truncation falls as h^3 and the rounding of the oracle's
     double ll output rises as 1 / h, so the disagreement of the two steps has a minimum over h: starting at h0, h is
     divided by 4 while the disagreement shrinks, and the step of the smallest disagreement is taken."""
     def g(r):
         with np.errstate(over="ignore"):
-            return np.sum(wt_p * np.where(wt_p != 0, np.exp(_site_ll(oracle, one_category(md, r)) - ll_s), 0))
+            return np.sum(wt_p * np.where(wt_p != 0, np.exp(_site_ll(oracle, one_category(md, r), cache, ("ll", float(r))) - ll_s), 0))
     g0 = g(0.0)
     best = None
     h = h0
@@ -170,8 +175,10 @@ def zero_rate_term(oracle, md, ll_s, wt_p, h0=FD_H):
     return best
 
 
-def expectations(oracle, md, weights):
+def expectations(oracle, md, weights, cache=None):
     """(prior_out [C], rate_out [C], rate_tol [C]) of plk_mixture_sens from the oracle alone, in long double.
+    cache: a dict the caller keeps for ONE document; the per-site oracle values, which do not depend on the weights, are
+    kept there, so that a second weight vector costs no oracle call.
     rate_tol[c] is the accuracy of the expected rate_out[c] relative to max_c |rate_out|: 0 where the value comes from
     binary128 derivatives, and for a category of rate 0 the larger of 1e-9 and ten times the disagreement of the two
     difference steps (asserted below 1e-8, so that a test cannot hide behind it)."""
@@ -180,7 +187,7 @@ def expectations(oracle, md, weights):
     w = oracle.prepare(m)
     C = int(w["C"])
     wt = np.asarray(weights, dtype=LD)
-    ll_s = _site_ll(oracle, md)
+    ll_s = _site_ll(oracle, md, cache, "mixture")
     assert np.all(np.isfinite(ll_s[np.asarray(weights) != 0]))
     t = np.asarray(m.edge_rates_csr, dtype=LD)
     prior_out, rate_out, fd_gap = np.zeros(C, dtype=LD), np.zeros(C, dtype=LD), np.zeros(C, dtype=LD)
@@ -188,17 +195,22 @@ def expectations(oracle, md, weights):
     for c in range(C):
         r, p = float(w["cat_rates"][c]), LD(w["cat_prior"][c])
         md1 = one_category(md, r)
-        ll_c = _site_ll(oracle, md1)
+        ll_c = _site_ll(oracle, md1, cache, ("ll", r))
         with np.errstate(over="ignore"):
             ratio = np.where(live, np.exp(ll_c - ll_s), 0)
         prior_out[c] = np.sum(wt * ratio)
         if r > 0:
-            m1 = oracle.parse_model(md1)
-            d = np.asarray(oracle.site_deriv(m1, oracle.prepare(m1), m1.B, precise=2), dtype=LD)
+            if cache is None or ("deriv", r) not in cache:
+                m1 = oracle.parse_model(md1)
+                d = np.asarray(oracle.site_deriv(m1, oracle.prepare(m1), m1.B, precise=2), dtype=LD)
+                if cache is not None:
+                    cache["deriv", r] = d
+            else:
+                d = cache["deriv", r]
             per_site = np.where(live, ratio * (d @ (t / LD(r))), 0)
             rate_out[c] = p * np.sum(wt * per_site)
         else:
-            rate_out[c], fd_gap[c], _ = zero_rate_term(oracle, md, ll_s, wt * p)
+            rate_out[c], fd_gap[c], _ = zero_rate_term(oracle, md, ll_s, wt * p, cache=cache)
     scale = np.max(np.abs(rate_out))
     gap = fd_gap / scale if scale > 0 else fd_gap
     assert np.all(gap < 1e-8), "forward difference at r = 0: steps h and h/2 disagree by %s of max|rate_out|" % gap

@@ -116,60 +116,66 @@ def _wsum(vals, weights):
 
 def oracle_W(oracle, m, w, weights, nthreads=0, cats=None):
     """W[c][e][i][j] by the issue's definition: the weighted site sum of site_edge_expect with F zero except a 1 at
-    (c, i, j) on every edge, coef_mode 0 -> [C][E][k][k] long double (categories not in `cats` stay 0)"""
+    (c, i, j) on every edge, coef_mode 0 -> [C][E][k][k] long double (categories not in `cats` stay 0).
+    weights None: the per-site terms [S][C][E][k][k], for callers that sum them under several weight vectors."""
     C, E, k = int(w["C"]), m.E, m.k
-    W = np.zeros((C, E, k, k), dtype=LD)
+    W = np.zeros((m.S, C, E, k, k), dtype=LD)
     for c in (range(C) if cats is None else cats):
         for i in range(k):
             for j in range(k):
                 F = np.zeros((C, E, k, k))
                 F[c, :, i, j] = 1.0
-                x = oracle.site_edge_expect(m, w, m.B, q128(F), 0, nthreads=nthreads)
-                W[c, :, i, j] = _wsum(x, weights)
-    return W
+                W[:, c, :, i, j] = oracle.site_edge_expect(m, w, m.B, q128(F), 0, nthreads=nthreads)
+    return W if weights is None else _wsum(W, weights)
 
 
-def oracle_W_factored(oracle, m, w, weights, nthreads=0):
+def oracle_W_factored(oracle, m, w, weights, nthreads=0, precise=2, sites=None):
     """The same W from 2k + 1 oracle calls per category instead of k^2, for state counts where k^2 binary128 up passes
     are out of reach of a test: per site and edge, with F nonzero in category c only,
         x(e_i 1^T) = a_i = p fe[i] (1 . L) / f,   x(1 e_j^T) = b_j = p (fe . 1) L[j] / f,   x(1 1^T) = t = p (fe . 1)(1 . L) / f
     so p fe[i] L[j] / f = a_i b_j / t exactly; the three factors are correctly rounded doubles of binary128 values and
-    every term is non-negative, which puts the relative error of each W entry below 4 ulp.  Checked against oracle_W."""
+    every term is non-negative, which puts the relative error of each W entry below 4 ulp.  Checked against oracle_W.
+    weights None: the per-site terms, as in oracle_W.  precise = 1: the oracle's long-double pass on double P (for state
+    counts whose binary128 pass is too slow for a test; the caller holds it against precise = 2 on a few sites);
+    sites: a slice of the sites of m."""
     C, E, k = int(w["C"]), m.E, m.k
-    W = np.zeros((C, E, k, k), dtype=LD)
-    wt = np.asarray(weights, dtype=LD)
+    B = m.B if sites is None else np.ascontiguousarray(m.B[sites])
+    W = np.zeros((B.shape[0], C, E, k, k), dtype=LD)
     for c in range(C):
         def run(F1):
             F = np.zeros((C, E, k, k))
             F[c] = F1
-            return np.asarray(oracle.site_edge_expect(m, w, m.B, q128(F), 0, nthreads=nthreads), dtype=LD)
+            return np.asarray(oracle.site_edge_expect(m, w, B, q128(F) if precise == 2 else F, 0, nthreads=nthreads, precise=precise), dtype=LD)
         t = run(np.ones((k, k)))
         a = np.stack([run(np.outer(np.eye(k)[i], np.ones(k))) for i in range(k)], axis=2)      # [S][E][k]
         b = np.stack([run(np.outer(np.ones(k), np.eye(k)[j])) for j in range(k)], axis=2)
         with np.errstate(divide="ignore", invalid="ignore"):
             term = np.where(t[:, :, None, None] > 0, a[:, :, :, None] * b[:, :, None, :] / t[:, :, None, None], 0)
-        W[c] = np.tensordot(wt, term, axes=(0, 0))
-    return W
+        W[:, c] = term
+    return W if weights is None else _wsum(W, weights)
 
 
 def oracle_root(oracle, m, w, weights, per_category=False):
     """root[i] = d/droot_w[i] = sum_s w_s L_i(s) / lhood_s with L_i the site likelihood under the one-hot custom root
-    prior e_i -> [k], or per category [C][k] (the workspace cut down to one category, times its prior)"""
+    prior e_i -> [k], or per category [C][k] (the workspace cut down to one category, times its prior).
+    weights None: the per-site terms [S][C][k] (per_category) or [S][k]."""
     k, C = m.k, int(w["C"])
     ll, _ = oracle.site_ll(m, w, B=m.B, precise=2)
     ll = np.asarray(ll, dtype=LD)
     m1 = copy.copy(m)
     m1.root_mode = 2
     Pq = np.asarray(w["Pq"]).reshape(C, -1)
-    out = np.zeros((C, k), dtype=LD)
+    out = np.zeros((m.S, C, k), dtype=LD)
     for c in range(C) if per_category else [None]:
         wc = w if c is None else dict(w, C=1, P=np.ascontiguousarray(w["P"][c:c + 1]), Pq=np.ascontiguousarray(Pq[c]), cat_prior=np.ones(1))
         for i in range(k):
             li, _ = oracle.site_ll(m1, dict(wc, root_w=np.eye(k)[i].copy()), B=m.B, precise=2)
             with np.errstate(over="ignore"):
                 r = np.exp(np.asarray(li, dtype=LD) - ll)
-            out[0 if c is None else c, i] = _wsum(r, weights) * (1 if c is None else LD(w["cat_prior"][c]))
-    return out if per_category else out[0]
+            out[:, 0 if c is None else c, i] = r * (1 if c is None else LD(w["cat_prior"][c]))
+    if weights is not None:
+        out = _wsum(out, weights)
+    return out if per_category else out[..., 0, :]
 
 
 def oracle_G(oracle, m, w, weights, nthreads=0):

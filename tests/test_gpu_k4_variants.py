@@ -19,8 +19,8 @@ Tolerances and weights are those of tests/test_gpu_kernel_families.py."""
 import numpy as np
 import pytest
 
-from helpers import (IRREGULAR_CHERRY, IRREGULAR_EDGES, IRREGULAR_RATES, K4_MODELS, cherry_with_unequal_edges, family_workload, k4_workload,
-                     oracle_model, rel_err, tree_workload)
+from helpers import (IRREGULAR_CHERRY, IRREGULAR_EDGES, IRREGULAR_RATES, K4_MODELS, cherry_with_unequal_edges, deep_workload, family_workload,
+                     k4_workload, oracle_model, rel_err, tree_workload)
 from test_gpu_kernel_families import MFMA, PROB_ULP, SUM_TOL, TOL, VEC, _row_err, _wsum
 
 gpu = pytest.mark.gpu                # every test but the one on the tables of expected paths, which needs no GPU
@@ -487,19 +487,6 @@ def test_zero_likelihood_site_under_zero_weight(eng, k, case):
 
 
 # ------------------------------------------------------------------ the 16-slot C++ interpreter
-def _deep_workload():
-    """the smallest input that reaches launch_fused<16, 1>: the full binary tree over 512 unary
-    nodes with one leaf each (N = 1535, stack need 9) and ONE character definition, the all-ones row.  Nodes 0..510 are
-    the binary tree in heap order, 511..1022 the unary nodes, 1023..1534 the leaves."""
-    edges = [[(i - 1) // 2, i] for i in range(1, 1023)] + [[511 + i, 1023 + i] for i in range(512)]
-    rng = np.random.default_rng(4416)
-    rates = rng.uniform(0.01, 0.3, len(edges))
-    rates[rng.choice(len(edges), 20, replace=False)] = 0.0
-    wl = tree_workload(4, edges, rates, root="custom", seed=4416, name="k4 deep")
-    wl.defs, wl.nchar = np.ones((1, 4)), 1
-    return wl
-
-
 @gpu
 def test_ll_sixteen_slot_interpreter(eng, oracle):
     """k_ll_fused4<16, 1> on the only kind of input that reaches it.  Its LDS image fits with one character definition
@@ -510,7 +497,7 @@ def test_ll_sixteen_slot_interpreter(eng, oracle):
     instantiation (kernel 1, variant 3, 9 slots), that it launches with 144 KiB of LDS and 16 parked vectors in two tiles,
     and that the scalings on the way up and the custom root prior end in the right number."""
     from phyly_amd import engine as E
-    wl = _deep_workload()
+    wl = deep_workload()
     wl.setup_engine(eng)
     try:
         _set_options(eng, {})
