@@ -74,7 +74,11 @@ char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode
  * reductions) exactly as the corresponding query would perform it, without
  * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
  * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate" | "rate_matrix_deriv" |
- * "mixture_deriv".  0 = accepted. */
+ * "mixture_deriv".  0 = accepted.  Where the document selects at least one site this includes the preparation of the
+ * model on the host (normalised rate matrix, category rates and priors) and the check of its values that every query
+ * makes before any device work (plk_check_model_values in plk.h: non-finite or negative values, rate x length x |Qn|
+ * beyond 2^40); the diagnostic names the edge in the order of the document's `edges`.  A document that selects no site
+ * is accepted without it, as the query answers it without preparing the model. */
 int arbplf_validate_string(const char *what, const char *s_in);
 
 /* stdin -> stdout filter used by the CLI mains (run_string_script,

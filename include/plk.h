@@ -97,6 +97,24 @@ int plk_set_model(plk_engine *h, int k, int C, const double *Qn, const double *Q
 /* Recompute P for new edge rates only (branch-length optimisation loops). */
 int plk_update_edge_rates(plk_engine *h, const double *edge_rates_csr);
 
+/*
+ * What plk_set_model and plk_update_edge_rates accept, on its own: host only, no engine and no GPU involved
+ * (phyly_amd/csrc/plk_k1_check.h; E edge rates, otherwise the arguments of plk_set_model).  PLK_E_ARG for
+ *   - any value that is not finite: Qn, Qn_lo, edge rates, category rates and priors, root_w where the root mode reads it;
+ *   - a negative edge rate, category rate or category prior (-0.0 counts as zero);
+ *   - any pair (c, e) with cat_rates[c] * edge_rates[e] * |Qn|_inf not finite or above 2^40 (|Qn|_inf: the largest
+ *     absolute row sum).  The transition matrix kernel squares once per doubling of that number; each squaring can
+ *     double the drift of the row sums, at most k 2^sq 2^-104, and 2^40 keeps it below 2^-53 at k = 64 (DESIGN.md
+ *     section 6).  The reference, working in Arb, accepts such inputs; here about 1e12 expected substitutions on one
+ *     edge is the documented limit.
+ * plk_set_model, plk_update_edge_rates and every call that recomputes the transition matrices return PLK_E_ARG on the
+ * same terms, the diagnostic (plk_last_error) naming the edge and the category; the engine then keeps its previous model
+ * and rates and stays usable.  plk_get_frechet_matrices, plk_edge_expect(_multi) and their group forms return PLK_E_ARG
+ * for a direction matrix with an entry that is not finite; plk_rate_matrix_sens for pair sums that are not finite.
+ */
+int plk_check_model_values(int k, int C, int E, const double *Qn, const double *Qn_lo, const double *edge_rates,
+                           const double *cat_rates, const double *cat_prior, int root_mode, const double *root_w);
+
 /* Observations, compact form: codes[N][S] (site index fastest, one byte per
  * node per site) + definitions defs[nchar][k] (host).  `where` says whether
  * `codes` is a host or a device pointer; the engine copies it either way. */

@@ -71,10 +71,18 @@ static void q_expm(int k, const q128 *A, q128 *out)
     for (size_t i = 0; i < n; i++) out[i] = 0;
     for (int i = 0; i < k; i++) out[i * k + i] = 1;
     memcpy(T, X, n * sizeof(q128));
+    /* stop when the term moved no entry by more than 2^-120 of the entry itself: an absolute bound on the term would cut
+     * off the entries m steps from the diagonal, of order |A|^m, on a very short branch.  An entry that first appears
+     * in this term equals it, so the loop cannot end before every reachable entry has appeared: the entry (i, j) first
+     * appears in the term whose number is the length of the shortest path from i to j in the graph of A, a shortest path
+     * of length d passes nodes at every distance below d, so every term up to the largest distance brings a new entry
+     * and keeps the loop running.  Nor can a first appearance cancel to exactly 0: the term of number d holds at (i, j)
+     * the sum over the walks of d steps, a walk through a diagonal entry would reach j in fewer real steps, so only the
+     * shortest paths contribute, and their products of off-diagonal rates are all positive in a rate matrix. */
     for (int term = 1; term < 200; term++) {
-        q128 tn = 0;
-        for (size_t i = 0; i < n; i++) { out[i] += T[i]; q128 a = fabsq(T[i]); if (a > tn) tn = a; }
-        if (tn < 1e-45Q) break;
+        int done = 1;
+        for (size_t i = 0; i < n; i++) { out[i] += T[i]; if (fabsq(T[i]) > 0x1p-120Q * fabsq(out[i])) done = 0; }
+        if (done) break;
         q_matmul(k, T, X, W);
         q128 inv = 1.0Q / (q128)(term + 1);
         for (size_t i = 0; i < n; i++) T[i] = W[i] * inv;

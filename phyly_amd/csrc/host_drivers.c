@@ -20,6 +20,7 @@
 #include "host_json.h"
 #include "host_k0.h"
 #include "host_model.h"
+#include "plk_k1_check.h"
 
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
 static plk_group *g_grp = NULL;
@@ -101,6 +102,41 @@ static void query_clear(query *q)
 
 #define ENG(q, call) do { if (call) { fprintf(stderr, "error: %s\n", plk_group_last_error((q)->eng)); return -1; } } while (0)
 
+/* K0: the prepared model (host, long double) and the check of its values against what the transition matrix kernel
+ * accepts (plk_k1_check.h), before any device work; returns 0 / -1 with one diagnostic line */
+static int query_k0(query *q)
+{
+    host_model *m = &q->m;
+    const int k = m->k;
+    const int need_pi = (m->root_mode == HM_ROOT_EQUILIBRIUM) || m->use_equilibrium_divisor;
+    q->C = arbplf_k0_category_count(&m->mix);
+    q->cat_rates = malloc(q->C * sizeof(double));
+    q->cat_prior = malloc(q->C * sizeof(double));
+    q->pi = calloc(k, sizeof(double));
+    q->Qn = malloc((size_t)k * k * sizeof(double));
+    q->Qn_lo = malloc((size_t)k * k * sizeof(double));
+    if (!q->cat_rates || !q->cat_prior || !q->pi || !q->Qn || !q->Qn_lo) return -1;
+    if (arbplf_k0_prepare(k, m->rate_matrix, m->use_equilibrium_divisor, m->rate_divisor, need_pi, &m->mix,
+                          q->cat_rates, q->cat_prior, q->pi, q->Qn, q->Qn_lo) != q->C) {
+        fprintf(stderr, "error: model preparation failed\n");
+        return -1;
+    }
+    for (int i = 0; i < k * k; i++)
+        if (!isfinite(q->Qn[i])) { fprintf(stderr, "error: the normalised rate matrix is not finite (zero rate divisor or singular equilibrium system)\n"); return -1; }
+    char msg[320];
+    const double *root_w = m->root_mode == HM_ROOT_CUSTOM ? m->root_custom : (m->root_mode == HM_ROOT_EQUILIBRIUM ? q->pi : NULL);
+    /* the check numbers the edges as its array does: give it the rates in the order of the user's `edges`, so that this
+     * line names the edge as the document does.  A later refusal by the engine (the rates of a fit or Newton step)
+     * comes through ENG() in the engine's words, which say that they count in CSR order. */
+    double *er_user = malloc((size_t)(m->E + 1) * sizeof(double));
+    if (!er_user) return -1;
+    for (int e = 0; e < m->E; e++) er_user[m->csr_to_user[e]] = m->edge_rates_csr[e];
+    const int bad = plk_k1_check_values(k, q->C, m->E, q->Qn, q->Qn_lo, er_user, q->cat_rates, q->cat_prior, m->root_mode, root_w, msg, sizeof msg);
+    free(er_user);
+    if (bad) { fprintf(stderr, "error: %s\n", msg); return -1; }
+    return 0;
+}
+
 /* K0 + engine set-up + upload of the selected sites; returns 0 / -1 */
 static int query_prepare(query *q)
 {
@@ -150,22 +186,7 @@ static int query_prepare(query *q)
     if (q->r_site.agg_mode != AGG_NONE) host_reduction_weights(&q->r_site, q->w_site, &q->div_site);
     if (q->U == 0) return 0;
 
-    /* K0 (host, long double) */
-    const int need_pi = (m->root_mode == HM_ROOT_EQUILIBRIUM) || m->use_equilibrium_divisor;
-    q->C = arbplf_k0_category_count(&m->mix);
-    q->cat_rates = malloc(q->C * sizeof(double));
-    q->cat_prior = malloc(q->C * sizeof(double));
-    q->pi = calloc(k, sizeof(double));
-    q->Qn = malloc((size_t)k * k * sizeof(double));
-    q->Qn_lo = malloc((size_t)k * k * sizeof(double));
-    if (!q->cat_rates || !q->cat_prior || !q->pi || !q->Qn || !q->Qn_lo) return -1;
-    if (arbplf_k0_prepare(k, m->rate_matrix, m->use_equilibrium_divisor, m->rate_divisor, need_pi, &m->mix,
-                          q->cat_rates, q->cat_prior, q->pi, q->Qn, q->Qn_lo) != q->C) {
-        fprintf(stderr, "error: model preparation failed\n");
-        return -1;
-    }
-    for (int i = 0; i < k * k; i++)
-        if (!isfinite(q->Qn[i])) { fprintf(stderr, "error: the normalised rate matrix is not finite (zero rate divisor or singular equilibrium system)\n"); return -1; }
+    if (query_k0(q)) return -1;
 
     q->eng = get_group();
     if (!q->eng) return -1;
@@ -1033,7 +1054,8 @@ char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode) { 
 char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_rate_matrix_deriv, userdata, s_in, retcode); }
 char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_mixture_deriv, userdata, s_in, retcode); }
 
-/* Host-only validation (JSON grammar, model, reductions); no GPU is touched.
+/* Host-only validation (JSON grammar, model, reductions and, where a site is selected, the prepared model's values
+ * against what the transition matrix kernel accepts); no GPU is touched.
  * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta", "newton_update",
  * "cat_posterior", "site_rate", "rate_matrix_deriv" or "mixture_deriv".
  * Returns 0 when the input would be accepted. */
@@ -1051,6 +1073,8 @@ int arbplf_validate_string(const char *what, const char *s_in)
     query q;
     query_init(&q);
     int rc = query_parse(&q, kind, json_doc_root(doc));
+    /* as query_prepare: a document that selects no site is answered without preparing its model */
+    if (rc == 0 && q.r_site.selection_len > 0) rc = query_k0(&q);
     query_clear(&q);
     json_doc_free(doc);
     return rc;

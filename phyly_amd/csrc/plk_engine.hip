@@ -41,6 +41,8 @@
 
 #include "plk.h"
 #include "plk_dd.h"
+#define PLK_K1_FN __host__ __device__ static inline      /* k_expm_dd calls plk_k1_squarings: the header itself has no HIP in it */
+#include "plk_k1_check.h"     /* what K1 accepts (host) and its squaring count (host and, by the line above, device) */
 #include "plk_program.h"     /* traversal program: opcodes, builder, device formats and their checkers (host only) */
 
 #define PLK_MAX_K 64
@@ -498,9 +500,7 @@ __global__ __launch_bounds__(1024) void k_expm_dd(int ks, int E, const double *_
     if (threadIdx.x == 0) {
         double norm = 0;
         for (int i = 0; i < k; i++) norm = fmax(norm, s_row[i]);
-        int sq = 0;
-        while (norm > 0.03125) { norm *= 0.5; sq++; }
-        s_sq = sq;
+        s_sq = plk_k1_squarings(norm);      /* from the exponent, at most PLK_K1_MAX_SQ: no input decides how long this runs */
         dd cn = dd_make(1.0, 0.0);
         s_coef[0] = cn;
         for (int n = 1; n <= EXPM_TERMS; n++) { cn = dd_div_d(cn, (double)n); s_coef[n] = cn; }
@@ -1530,11 +1530,47 @@ extern "C" int plk_set_tree(plk_engine *h, int N, const int *indptr, const int *
     return PLK_OK;
 }
 
+/* The engine's arrays are in CSR order, and so is the edge that the check's line names; the drivers, which name edges in
+ * the order of the user's `edges` in their own check, print the engine's line as it is, so it says which order it means. */
+#define K1_CSR_NOTE " (edges numbered in CSR order)"
+
+/* the model values of the engine with `edge_rates` against what K1 accepts (plk_k1_check.h); PLK_E_ARG and the diagnostic */
+static int k1_check(plk_engine *h, const char *who, const double *edge_rates)
+{
+    char msg[320];
+    const size_t kk = (size_t)h->k * h->k;
+    if (plk_k1_check_values(h->k, h->C, h->E, h->Qn.data(), h->Qn.data() + kk, edge_rates, h->cat_rates.data(), h->cat_prior.data(),
+                            h->root_mode, h->root_w.data(), msg, sizeof msg)) {
+        h->err = std::string(who) + ": " + msg + K1_CSR_NOTE;
+        return PLK_E_ARG;
+    }
+    return PLK_OK;
+}
+
+/* a direction matrix of the Frechet entry points: every entry finite */
+static int k1_check_direction(plk_engine *h, const char *who, int nL, const double *L_hi, const double *L_lo)
+{
+    const size_t kk = (size_t)h->k * h->k;
+    for (int m = 0; m < nL; m++) {
+        const long bad = plk_k1_check_matrix(h->k, L_hi + m * kk, L_lo ? L_lo + m * kk : nullptr);
+        if (bad) {
+            h->err = std::string(who) + ": direction matrix " + std::to_string(m) + " is not finite at entry (" +
+                     std::to_string((bad - 1) / h->k) + ", " + std::to_string((bad - 1) % h->k) + ")";
+            return PLK_E_ARG;
+        }
+    }
+    return PLK_OK;
+}
+
 static int run_expm(plk_engine *h, bool post = false, bool need_dP = true)
 {
     const int k = h->k, C = h->C, E = h->E;
     const size_t kk = (size_t)k * k, n = (size_t)C * E * kk;
     int rc;
+    /* Belt and braces: plk_set_model and plk_update_edge_rates are the only writers of h->edge_rates today (the fit and
+     * Newton drivers go through the latter) and both have run this check, so it cannot fire.  It is here for a writer
+     * added later: should it fire, the refused rates stay in h->edge_rates until the next plk_update_edge_rates. */
+    if ((rc = k1_check(h, "K1", h->edge_rates.data()))) return rc;
     if ((rc = dev_reserve(h, &h->d_Pdd, &h->pdd_cap, n))) return rc;
     if ((rc = dev_reserve(h, &h->d_P, &h->p_cap, n))) return rc;
     if ((rc = dev_reserve(h, &h->d_dP, &h->dp_cap, n))) return rc;
@@ -1596,6 +1632,14 @@ extern "C" int plk_set_model(plk_engine *h, int k, int C, const double *Qn, cons
     if (C > PLK_MAX_C) { h->err = "plk_set_model: more than 64 rate categories is not supported"; return PLK_E_UNSUPPORTED; }
     if (root_mode < PLK_ROOT_NONE || root_mode > PLK_ROOT_EQUILIBRIUM) { h->err = "plk_set_model: bad root mode"; return PLK_E_ARG; }
     if ((root_mode == PLK_ROOT_CUSTOM || root_mode == PLK_ROOT_EQUILIBRIUM) && !root_w) { h->err = "plk_set_model: root_w required"; return PLK_E_ARG; }
+    {
+        /* before anything of the engine changes: a refused model leaves the previous one in place */
+        char msg[320];
+        if (plk_k1_check_values(k, C, h->E, Qn, Qn_lo, edge_rates_csr, cat_rates, cat_prior, root_mode, root_w, msg, sizeof msg)) {
+            h->err = std::string("plk_set_model: ") + msg + K1_CSR_NOTE;
+            return PLK_E_ARG;
+        }
+    }
     HIPCHK(h, hipSetDevice(h->device));
     if (h->k != k) { h->pat_mode = 0; }
     h->k = k; h->C = C; h->K = pad_K(k); h->root_mode = root_mode;
@@ -1628,11 +1672,22 @@ extern "C" int plk_update_edge_rates(plk_engine *h, const double *edge_rates_csr
 {
     if (!plk_live(h) || !edge_rates_csr) return PLK_E_ARG;
     if (h->k == 0) { h->err = "plk_update_edge_rates: set the model first"; return PLK_E_ARG; }
+    { int rc = k1_check(h, "plk_update_edge_rates", edge_rates_csr); if (rc) return rc; }      /* refused: the previous rates stay */
     HIPCHK(h, hipSetDevice(h->device));
     h->edge_rates.assign(edge_rates_csr, edge_rates_csr + h->E);
     HIPCHK(h, hipMemcpyAsync(h->d_edge_rates, h->edge_rates.data(), h->E * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h->model_dirty = true;
     return PLK_OK;
+}
+
+/* the check of plk_set_model / plk_update_edge_rates on its own: no engine, no GPU */
+extern "C" int plk_check_model_values(int k, int C, int E, const double *Qn, const double *Qn_lo, const double *edge_rates,
+                                      const double *cat_rates, const double *cat_prior, int root_mode, const double *root_w)
+{
+    if (k > PLK_MAX_K || C > PLK_MAX_C) return PLK_E_UNSUPPORTED;
+    if (root_mode < PLK_ROOT_NONE || root_mode > PLK_ROOT_EQUILIBRIUM) return PLK_E_ARG;
+    if ((root_mode == PLK_ROOT_CUSTOM || root_mode == PLK_ROOT_EQUILIBRIUM) && !root_w) return PLK_E_ARG;
+    return plk_k1_check_values(k, C, E, Qn, Qn_lo, edge_rates, cat_rates, cat_prior, root_mode, root_w, nullptr, 0) ? PLK_E_ARG : PLK_OK;
 }
 
 extern "C" int plk_get_transition_matrices(plk_engine *h, double *P_out)
@@ -3271,6 +3326,7 @@ extern "C" int plk_edge_expect_multi(plk_engine *h, int nL, const double *L_hi, 
     if (!plk_live(h)) return PLK_E_ARG;
     if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_edge_expect: tree, model and patterns must be set"; return PLK_E_ARG; }
     if (!L_hi || nL < 1 || coef_mode < PLK_COEF_PRIOR || coef_mode > PLK_COEF_PRIOR_RATE) { h->err = "plk_edge_expect: bad direction matrix or coefficient mode"; return PLK_E_ARG; }
+    { int rcL = k1_check_direction(h, "plk_edge_expect", nL, L_hi, L_lo); if (rcL) return rcL; }
     HIPCHK(h, hipSetDevice(h->device));
     QueryTimer qt(h);
     int rc;
@@ -3343,6 +3399,8 @@ extern "C" int plk_get_frechet_matrices(plk_engine *h, const double *L_hi, const
 {
     if (!plk_live(h) || !L_hi || !F_out) return PLK_E_ARG;
     if (h->k == 0) { h->err = "plk_get_frechet_matrices: model must be set"; return PLK_E_ARG; }
+    if (coef_mode < PLK_COEF_PRIOR || coef_mode > PLK_COEF_PRIOR_RATE) { h->err = "plk_get_frechet_matrices: bad coefficient mode"; return PLK_E_ARG; }
+    { int rcL = k1_check_direction(h, "plk_get_frechet_matrices", 1, L_hi, L_lo); if (rcL) return rcL; }
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }

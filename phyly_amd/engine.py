@@ -27,7 +27,21 @@ _lib = None
 
 
 class EngineError(RuntimeError):
-    pass
+    code = 0          # the PLK_E_* code of the failed call
+
+
+E_ARG = 2
+
+
+def check_model_values(Qn, edge_rates, cat_rates, cat_prior, root_mode=ROOT_NONE, root_w=None, Qn_lo=None):
+    """plk_check_model_values: the PLK_E_* code plk_set_model would give these values (0 = accepted); no engine, no GPU"""
+    lib = load_library()
+    Qn = _f64(Qn)
+    Qn_lo = _f64(Qn_lo) if Qn_lo is not None else None
+    er, cr, cp = _f64(edge_rates), _f64(cat_rates), _f64(cat_prior)
+    rw = _f64(root_w) if root_w is not None else None
+    return int(lib.plk_check_model_values(Qn.shape[0], len(cr), len(er), _ptr(Qn), _ptr(Qn_lo), _ptr(er), _ptr(cr), _ptr(cp),
+                                          int(root_mode), _ptr(rw)))
 
 
 def load_library():
@@ -50,6 +64,7 @@ def load_library():
     lib.plk_set_tree.argtypes = [vp, ci, vp, vp, vp]
     lib.plk_set_model.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]
     lib.plk_update_edge_rates.argtypes = [vp, vp]
+    lib.plk_check_model_values.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, ci, vp]
     lib.plk_set_patterns_codes.argtypes = [vp, cl, vp, ci, ci, vp]
     lib.plk_set_patterns_dense.argtypes = [vp, cl, vp, ci]
     lib.plk_set_site_weights.argtypes = [vp, vp, ci]
@@ -130,7 +145,9 @@ class Engine:
 
     def _check(self, rc):
         if rc:
-            raise EngineError(self._lib.plk_last_error(self._h).decode())
+            err = EngineError(self._lib.plk_last_error(self._h).decode())
+            err.code = int(rc)
+            raise err
 
     def set_tree(self, indptr, indices, preorder):
         indptr, indices, preorder = _i32(indptr), _i32(indices), _i32(preorder)
@@ -141,13 +158,14 @@ class Engine:
     def set_model(self, Qn, edge_rates_csr, cat_rates, cat_prior, root_mode, root_w=None, Qn_lo=None):
         Qn = _f64(Qn)
         Qn_lo = _f64(Qn_lo) if Qn_lo is not None else None
-        self.k = Qn.shape[0]
+        k = Qn.shape[0]
         cat_rates, cat_prior = _f64(cat_rates), _f64(cat_prior)
-        self.C = len(cat_rates)
+        C = len(cat_rates)
         er = _f64(edge_rates_csr)
         rw = _f64(root_w) if root_w is not None else None
-        self._check(self._lib.plk_set_model(self._h, self.k, self.C, _ptr(Qn), _ptr(Qn_lo), _ptr(er), _ptr(cat_rates),
+        self._check(self._lib.plk_set_model(self._h, k, C, _ptr(Qn), _ptr(Qn_lo), _ptr(er), _ptr(cat_rates),
                                             _ptr(cat_prior), int(root_mode), _ptr(rw)))
+        self.k, self.C = k, C         # a refused model leaves the previous one in place
 
     def update_edge_rates(self, edge_rates_csr):
         er = _f64(edge_rates_csr)

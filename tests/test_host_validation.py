@@ -364,3 +364,33 @@ def test_empty_edge_list_is_rejected_like_the_reference(validate, capfd, oracle)
     import json
     with pytest.raises(RuntimeError):
         oracle.arbplf_ll(json.dumps(x))
+
+
+# Values the transition matrix kernel cannot take (phyly_amd/csrc/plk_k1_check.h): the JSON grammar
+# accepts them, the reference, working in Arb, evaluates them; the drivers refuse them after the model preparation and
+# before any device work, with one line that names the edge and the category.
+K1_REFUSED = {
+    "edge_rate_1e308_gamma4": (_md(edge_rate_coefficients=[2.0, 1e308, 0.5],
+                                   gamma_rate_mixture={"gamma_shape": 0.5, "gamma_categories": 4}), "edge 1 "),
+    "rate_divisor_1e-300": (_md(rate_divisor=1e-300), "edge 0 "),
+    "mixture_rate_1e200_on_edge_1e200": (_md(edge_rate_coefficients=[0.0, 0.0, 1e200], rate_divisor=7.0,
+                                             rate_mixture={"rates": [0.0, 1e200], "prior": [0.5, 0.5]}), "edge 2 "),
+}
+
+
+@pytest.mark.parametrize("name", sorted(K1_REFUSED))
+def test_values_beyond_the_kernel_limit_refused(validate, capfd, name):
+    x, edge = K1_REFUSED[name]
+    capfd.readouterr()
+    assert validate(x) != 0
+    err = capfd.readouterr().err.strip().splitlines()
+    assert len(err) == 1, err
+    assert err[0].startswith("error: ") and edge in err[0] and "rate category " in err[0] and "2^40" in err[0], err
+
+
+def test_values_at_the_kernel_limit_accepted(validate):
+    """with the fixed divisor 7, |Qn|_inf = 2 x 7.2 / 7 (row 0 of GOOD's rate matrix has the largest exit rate, 7.2; row 2:
+    6.5; row 1: 6): an edge rate just below 2^40 / |Qn|_inf is accepted, one just above it refused"""
+    top = 2.0 ** 40 / (2 * 7.2 / 7.0)
+    assert validate(_md(rate_divisor=7.0, edge_rate_coefficients=[2.0, top * (1 - 2.0 ** -40), 0.5])) == 0
+    assert validate(_md(rate_divisor=7.0, edge_rate_coefficients=[2.0, top * (1 + 2.0 ** -40), 0.5])) != 0
