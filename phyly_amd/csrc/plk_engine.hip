@@ -37,6 +37,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "plk.h"
@@ -225,16 +226,6 @@ static bool plk_live(const plk_engine *h)
     return !g_exiting && g_live.count(h) != 0;
 }
 
-/* HIPCHKC: the same inside a function that owns per-call device memory through a local `cleanup` lambda */
-#define HIPCHKC(h, call)                                                           \
-    do {                                                                           \
-        hipError_t e_ = (call);                                                    \
-        if (e_ != hipSuccess) {                                                    \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);         \
-            cleanup();                                                             \
-            return PLK_E_DEVICE;                                                   \
-        }                                                                          \
-    } while (0)
 #define HIPCHK(h, call)                                                            \
     do {                                                                           \
         hipError_t e_ = (call);                                                    \
@@ -2097,6 +2088,22 @@ static void launch_fused(plk_engine *h, const FusedArgs &a, unsigned grid, size_
     hipLaunchKernelGGL((k_ll_fused4<D, NS>), dim3(grid), dim3(PLK_TILE), lds, h->stream, a);
 }
 
+/* the padded state counts the generic kernels are compiled for: f(std::integral_constant<int, K>) with the engine's K */
+template <typename F>
+static void dispatch_K(int K, F &&f)
+{
+    switch (K) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 20: f(std::integral_constant<int, 20>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 61: f(std::integral_constant<int, 61>{}); break;
+    default: f(std::integral_constant<int, 64>{}); break;
+    }
+}
+
 template <int K>
 static void launch_generic(plk_engine *h, const GenArgs &a, unsigned grid)
 {
@@ -2276,16 +2283,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
         a.codes = h->d_codes; a.defs = h->d_defs; a.B = h->d_B; a.cat_prior = h->d_cat_prior;
         a.root_w = h->d_root_w; a.w = h->d_w; a.slots = h->d_slots; a.site_ll = d_out;
         a.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
-        switch (h->K) {
-        case 2: launch_generic<2>(h, a, grid); break;
-        case 4: launch_generic<4>(h, a, grid); break;
-        case 8: launch_generic<8>(h, a, grid); break;
-        case 16: launch_generic<16>(h, a, grid); break;
-        case 20: launch_generic<20>(h, a, grid); break;
-        case 32: launch_generic<32>(h, a, grid); break;
-        case 61: launch_generic<61>(h, a, grid); break;
-        default: launch_generic<64>(h, a, grid); break;
-        }
+        dispatch_K(h->K, [&](auto Kc) { launch_generic<decltype(Kc)::value>(h, a, grid); });
         h->info_ll_kernel = 2;
     }
     {
@@ -2444,6 +2442,114 @@ static int copy_site_rows(plk_engine *h, size_t rows, long n, long s0, const dou
     return PLK_OK;
 }
 
+/* ---------------------------------------------------------------------- */
+/* what the down / up drivers share: storage maps, the call's integer      */
+/* tables, the site-chunk plan and the output epilogue                     */
+/* ---------------------------------------------------------------------- */
+
+/* storage indices of the current program (plk_program.h); build_program() has run */
+static PlkStorageMaps storage_maps(const plk_engine *h)
+{
+    PlkStorageMaps m;
+    plk_storage_maps_build(h->N, h->E, h->indptr.data(), h->tip_edge, h->scale_node.data(), m);
+    return m;
+}
+
+/* node_has_data as the kernels read it: one int per node (all ones until patterns say otherwise) */
+static std::vector<int> has_data_ints(plk_engine *h)
+{
+    if (h->node_has_data.size() != (size_t)h->N) h->node_has_data.assign(h->N, 1);
+    return std::vector<int>(h->node_has_data.begin(), h->node_has_data.end());
+}
+
+/* The integer tables of one call, gathered into one host block that goes to the grow-only d_u4pack in one copy.  put()
+ * returns the table's offset in the block; every table starts at a multiple of 4 ints (the op tables are read as int4). */
+struct IntPack {
+    std::vector<int> words;
+    size_t put(const int *src, size_t n)
+    {
+        const size_t off = words.size();
+        words.insert(words.end(), src, src + n);
+        while (words.size() % 4) words.push_back(0);
+        return off;
+    }
+    size_t put_opt(const int *src, size_t n) { return src ? put(src, n) : 0; }     /* an optional mask */
+    size_t put_has_data(plk_engine *h) { const std::vector<int> hd = has_data_ints(h); return put(hd.data(), hd.size()); }
+    /* four spare words follow the tables; the pair-sum passes keep their flag in the first one (flag()) */
+    int upload(plk_engine *h)
+    {
+        int rc;
+        if ((rc = dev_reserve(h, &h->d_u4pack, &h->u4pack_cap, words.size() + 4))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_u4pack, words.data(), words.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));      /* the block is a local of the caller */
+        return PLK_OK;
+    }
+    int *flag(const plk_engine *h) const { return h->d_u4pack + words.size(); }
+};
+
+/* sites per pass of a down / up driver (plk_site_chunk in plk_program.h), or PLK_E_NOMEM in the name of the query */
+static int plan_site_chunk(plk_engine *h, const char *who, size_t bytes_per_site, int tile, bool whole_tiles, long *chunk)
+{
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    *chunk = plk_site_chunk(h->S, free_b, h->work_cap * sizeof(double), bytes_per_site, h->opt_site_chunk, tile, whole_tiles);
+    if (*chunk > 0) return PLK_OK;
+    h->err = std::string(who) + (whole_tiles ? ": not enough device memory" : ": not enough device memory for one site");
+    return PLK_E_NOMEM;
+}
+
+/* site-summed marginals without per-site output: the up passes of the specialised drivers leave one weighted sum per
+ * wave, node and state (MVS) instead of the N k planes */
+static bool marginal_sums_only(bool deriv, bool marg, const double *site_out, const double *sums_out)
+{
+    return marg && !site_out && sums_out && !deriv;
+}
+
+/* the outputs of one site chunk: edge rows DV (drows of them, 0 unless a derivative was asked for) and marginal rows MV
+ * (mrows), or per-wave marginal sums MVS ([mrows][nwv]) in place of MV */
+struct UpDownOut {
+    size_t drows = 0, mrows = 0, nwv = 0;
+    const double *DV = nullptr, *MV = nullptr;
+    const double *MVS = nullptr;       /* null unless the pass left per-wave sums in place of MV (marginal_sums_only) */
+};
+
+/* per-chunk epilogue: weighted row sums into dsum / msum (when sums are wanted), per-site rows to the host */
+static int updown_chunk_out(plk_engine *h, const UpDownOut &o, long n, long s0, bool want_sums, long double *dsum, long double *msum,
+                            double *site_out)
+{
+    int rc;
+    if (want_sums) {
+        const double *w = h->d_w ? h->d_w + s0 : nullptr;
+        if (o.drows && (rc = wsum_rows(h, (int)o.drows, n, o.DV, w, dsum))) return rc;
+        if (o.mrows && o.MVS) { if ((rc = wsum_rows(h, (int)o.mrows, (long)o.nwv, o.MVS, nullptr, msum))) return rc; }
+        else if (o.mrows && (rc = wsum_rows(h, (int)o.mrows, n, o.MV, w, msum))) return rc;
+    }
+    if (site_out) return copy_site_rows(h, o.drows ? o.drows : o.mrows, n, s0, o.drows ? o.DV : o.MV, site_out);
+    return PLK_OK;
+}
+
+static inline void put_dd(double *dst, long double v)
+{
+    const double hi = (double)v;
+    dst[0] = hi;
+    dst[1] = (double)(v - (long double)hi);
+}
+
+/* the final split of n accumulated sums into {hi, lo} pairs */
+static void put_dd_rows(double *dst, const long double *src, size_t n)
+{
+    for (size_t r = 0; r < n; r++) put_dd(dst + 2 * r, src[r]);
+}
+
+/* end of a deriv / marginal query: wait for the stream, then hand out the sums (when asked for) */
+static int updown_finish(plk_engine *h, double *sums_out, const std::vector<long double> &sums)
+{
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = std::string("plk_deriv/plk_marginal: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
+    if (sums_out) put_dd_rows(sums_out, sums.data(), sums.size());
+    return PLK_OK;
+}
+
 template <int T>
 static void launch_updown_mfma(plk_engine *h, const MUpArgs &a, const MDownProg &pg, unsigned grid, size_t lds, bool deriv, bool marg, bool nodes)
 {
@@ -2469,19 +2575,11 @@ static int run_updown_mfma(plk_engine *h, bool deriv, bool marg, const int *edge
     const int T = (k + 15) / 16, R = 4 * T, kk4 = (k + 3) / 4;
     const long S = h->S;
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
-    const int ntips = (int)h->tip_edge.size();
-    std::vector<int> edge_tip(E, -1), edge_int(E, -1), node_int(N, -1);
-    for (int t = 0; t < ntips; t++) edge_tip[h->tip_edge[t]] = t;
-    int nie = 0, nin = 0;
-    for (int e = 0; e < E; e++) if (edge_tip[e] < 0) edge_int[e] = nie++;
-    for (int a = 0; a < N; a++) if (h->indptr[a + 1] > h->indptr[a]) node_int[a] = nin++;
-    std::vector<int> te = h->tip_edge;
-    te.push_back(-1);
+    const PlkStorageMaps sm = storage_maps(h);
+    const std::vector<int> &edge_tip = sm.edge_tip, &edge_int = sm.edge_int, &node_int = sm.node_int, &node_scale = sm.node_scale;
+    const int ntips = sm.ntips, nie = sm.nie, nin = sm.nin, nsc = sm.nsc;
     std::vector<double> rwd((size_t)4 * R, 0.0);
     for (int i = 0; i < k; i++) rwd[(size_t)(i & 3) * R + (i >> 2)] = h->root_w[i];
-    std::vector<int> node_scale(N, -1);
-    int nsc = 0;
-    for (int a = 0; a < N; a++) if (node_int[a] >= 0 && h->scale_node[a]) node_scale[a] = nsc++;
 
     /* derivative queries without marginals on the edge-at-a-time up pass: nodes whose children are all leaves are finished
      * inside their parent's visit (their F never goes through HBM), and the up pass rebuilds their L from the tip tables,
@@ -2504,7 +2602,6 @@ static int run_updown_mfma(plk_engine *h, bool deriv, bool marg, const int *edge
     }
     const std::vector<plk_op4> &dops = dch.ops;
     const int nslots_m = std::max(h->slots_needed, 1);
-    auto cleanup = [&]() {};        /* everything below lives in grow-only engine buffers: no per-call hipMalloc / hipFree */
     if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
     /* PLK_OPT_UP_NODES = 1: derivative queries without marginals take the node-visit up pass over edge vectors only
      * (k_up_nodes_mfma), when the depth-first down pass applies (its staged code rows fit the LDS).  Measured equal to
@@ -2521,25 +2618,21 @@ static int run_updown_mfma(plk_engine *h, bool deriv, bool marg, const int *edge
     }
     /* the call's integer tables, one upload: [ops (16-byte aligned first)][edge_tip][edge_int][node_int][tip edges][node_scale]
      * [obs nodes][has_data][edge mask][node mask] */
-    std::vector<int> pack;
-    auto put = [&](const int *src, size_t n) { const size_t o = pack.size(); pack.insert(pack.end(), src, src + n); while (pack.size() & 3) pack.push_back(0); return o; };
-    const size_t o_ops = put(reinterpret_cast<const int *>(dops.data()), dops.size() * 4);
-    const size_t o_et = put(edge_tip.data(), (size_t)E), o_ei = put(edge_int.data(), (size_t)E), o_ni = put(node_int.data(), (size_t)N);
-    const size_t o_te = put(te.data(), te.size()), o_ns = put(node_scale.data(), (size_t)N);
-    const size_t o_obs = put(h->obs_nodes.data(), h->obs_nodes.size());
-    std::vector<int> hd(h->node_has_data.begin(), h->node_has_data.end());
-    const size_t o_has = put(hd.data(), (size_t)N);
-    const size_t o_em = edge_mask ? put(edge_mask, (size_t)E) : 0, o_nm = node_mask ? put(node_mask, (size_t)N) : 0;
-    const size_t o_vis = nodes ? put(un.rec.data(), un.rec.size()) : 0;
-    const size_t o_inl = any_inl ? put(node_inl.data(), (size_t)N) : 0;
+    IntPack pack;
+    const size_t o_ops = pack.put(reinterpret_cast<const int *>(dops.data()), dops.size() * 4);
+    const size_t o_et = pack.put(edge_tip.data(), (size_t)E), o_ei = pack.put(edge_int.data(), (size_t)E), o_ni = pack.put(node_int.data(), (size_t)N);
+    const size_t o_te = pack.put(sm.tip_edges.data(), sm.tip_edges.size()), o_ns = pack.put(node_scale.data(), (size_t)N);
+    const size_t o_obs = pack.put(h->obs_nodes.data(), h->obs_nodes.size());
+    const size_t o_has = pack.put_has_data(h);
+    const size_t o_em = pack.put_opt(edge_mask, (size_t)E), o_nm = pack.put_opt(node_mask, (size_t)N);
+    const size_t o_vis = nodes ? pack.put(un.rec.data(), un.rec.size()) : 0;
+    const size_t o_inl = any_inl ? pack.put(node_inl.data(), (size_t)N) : 0;
     const size_t nfr = (size_t)C * E * T * kk4 * 64, ntab = (size_t)C * (ntips + 1) * h->nchar * 4 * R;
-    if ((rc = dev_reserve(h, &h->d_u4pack, &h->u4pack_cap, pack.size() + 4)) ||
-        (rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, 2 * ntab + rwd.size())) ||
+    if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, 2 * ntab + rwd.size())) ||
         (rc = dev_reserve(h, &h->d_uvmat, &h->uvmat_cap, 3 * nfr))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_u4pack, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_u4tip + 2 * ntab, rwd.data(), rwd.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));      /* pack and rwd are locals */
-    int *pk = h->d_u4pack;
+    if ((rc = pack.upload(h))) return rc;            /* its wait covers rwd, a local too */
+    const int *pk = h->d_u4pack;
     const int4 *d_dops = reinterpret_cast<const int4 *>(pk + o_ops);
     const int *d_et = pk + o_et, *d_ei = pk + o_ei, *d_ni = pk + o_ni, *d_te = pk + o_te, *d_ns = pk + o_ns, *d_obsm = pk + o_obs, *d_has = pk + o_has;
     const int *d_emask = edge_mask ? pk + o_em : nullptr, *d_nmask = node_mask ? pk + o_nm : nullptr;
@@ -2552,22 +2645,15 @@ static int run_updown_mfma(plk_engine *h, bool deriv, bool marg, const int *edge
                        k, R, E, ntips, h->nchar, d_te, h->d_Pdd, h->d_defs, h->K, d_tipd);
     hipLaunchKernelGGL(k_build_dtip_dist, dim3(ntips + 1, C), dim3(256), 0, h->stream,
                        k, R, E, ntips, h->nchar, d_te, d_M, h->d_defs, h->K, d_dtip, dzero);
-    if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
+    if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
 
-    /* site-summed marginals without per-site output: the up pass leaves per-wave sums (MVS) instead of the N k planes */
-    const bool msum_only = marg && !site_out && sums_out && !deriv;
+    const bool msum_only = marginal_sums_only(deriv, marg, site_out, sums_out);
     const size_t per_site = ((size_t)(nie + 2 * (size_t)nin) * C * R * 4 + (size_t)nslots_m * R * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg && !msum_only ? (size_t)N * k : 0)) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
-    budget += h->work_cap * sizeof(double);
-    long chunk = (long)std::min<size_t>((size_t)((S + MF_SITES - 1) / MF_SITES * MF_SITES), budget / (per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0)));
-    if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
-    chunk = chunk / MF_SITES * MF_SITES;
-    if (chunk < MF_SITES) { cleanup(); h->err = "plk_deriv/plk_marginal: not enough device memory"; return PLK_E_NOMEM; }
+    long chunk;
+    if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0), MF_SITES, true, &chunk))) return rc;
     /* site-summed marginals: one weighted sum per wave, node and state (sized for a whole chunk) */
     const size_t mvs_doubles = msum_only ? (size_t)N * k * (size_t)((chunk + MF_SITES - 1) / MF_SITES) * (MF_BLOCK / 64) : 0;
-    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles))) { cleanup(); return rc; }
+    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles))) return rc;
 
     std::vector<long double> dsum(deriv ? E : 0, 0.0L), msum(marg ? (size_t)N * k : 0, 0.0L);
     for (long s0 = 0; s0 < S; s0 += chunk) {
@@ -2609,27 +2695,12 @@ static int run_updown_mfma(plk_engine *h, bool deriv, bool marg, const int *edge
         else if (T == 2) launch_updown_mfma<2>(h, a, pg, grid, lds, deriv, marg, nv);
         else if (T == 3) launch_updown_mfma<3>(h, a, pg, grid, lds, deriv, marg, nv);
         else launch_updown_mfma<4>(h, a, pg, grid, lds, deriv, marg, nv);
-        if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_deriv/plk_marginal: kernel launch failed"; return PLK_E_DEVICE; }
-        if (sums_out) {
-            const double *w = h->d_w ? h->d_w + s0 : nullptr;
-            if (deriv && (rc = wsum_rows(h, E, n, a.DV, w, dsum.data()))) { cleanup(); return rc; }
-            if (marg && msum_only) { if ((rc = wsum_rows(h, N * k, (long)nwv, a.MVS, nullptr, msum.data()))) { cleanup(); return rc; } }
-            else if (marg && (rc = wsum_rows(h, N * k, n, a.MV, w, msum.data()))) { cleanup(); return rc; }
-        }
-        if (site_out && (rc = copy_site_rows(h, deriv ? (size_t)E : (size_t)N * k, n, s0, deriv ? a.DV : a.MV, site_out))) { cleanup(); return rc; }
+        if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: kernel launch failed"; return PLK_E_DEVICE; }
+        UpDownOut o;
+        o.drows = dsum.size(); o.mrows = msum.size(); o.nwv = nwv; o.DV = a.DV; o.MV = a.MV; o.MVS = a.MVS;
+        if ((rc = updown_chunk_out(h, o, n, s0, sums_out != nullptr, dsum.data(), msum.data(), site_out))) return rc;
     }
-    hipError_t e = hipStreamSynchronize(h->stream);
-    cleanup();
-    if (e != hipSuccess) { h->err = std::string("plk_deriv/plk_marginal: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
-    if (sums_out) {
-        const std::vector<long double> &src = deriv ? dsum : msum;
-        for (size_t r = 0; r < src.size(); r++) {
-            const double hi = (double)src[r];
-            sums_out[2 * r] = hi;
-            sums_out[2 * r + 1] = (double)(src[r] - (long double)hi);
-        }
-    }
-    return PLK_OK;
+    return updown_finish(h, sums_out, deriv ? dsum : msum);
 }
 
 /* deriv / marginal for k = 4 with compact codes: interleaved-vector kernels (plk_updown4.h) */
@@ -2669,26 +2740,12 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     const int ER = nM * E;                 /* rows of the edge-form output: [form][edge] */
     const long S = h->S;
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
-    const int ntips = (int)h->tip_edge.size();
-    std::vector<int> edge_tip(E, -1), edge_int(E, -1), node_int(N, -1);
-    for (int t = 0; t < ntips; t++) edge_tip[h->tip_edge[t]] = t;
-    int nie = 0, nin = 0;
-    for (int e = 0; e < E; e++) if (edge_tip[e] < 0) edge_int[e] = nie++;
-    for (int a = 0; a < N; a++) if (h->indptr[a + 1] > h->indptr[a]) node_int[a] = nin++;
-    if (nin == 0) { node_int[h->preorder[0]] = nin++; }      /* a single-node tree still has a root vector */
-    std::vector<int> te = h->tip_edge;
-    te.push_back(-1);
-    std::vector<int> node_scale(N, -1);
-    int nsc = 0;
-    for (int a = 0; a < N; a++) if (node_int[a] >= 0 && h->scale_node[a]) node_scale[a] = nsc++;
+    const PlkStorageMaps sm = storage_maps(h);               /* E > 0 here (use_updown4, pair_sums_run): the edge mask and the edge rows below are never empty */
+    const std::vector<int> &edge_tip = sm.edge_tip, &edge_int = sm.edge_int, &node_int = sm.node_int, &node_scale = sm.node_scale;
+    const int ntips = sm.ntips, nie = sm.nie, nin = sm.nin, nsc = sm.nsc;
 
-    int *d_et = nullptr, *d_ei = nullptr, *d_ni = nullptr, *d_te = nullptr, *d_emask = nullptr, *d_nmask = nullptr;
-    int *d_has = nullptr, *d_ns = nullptr, *d_oe2 = nullptr, *d_obs2 = nullptr;
-    int4 *d_ops2 = nullptr;
-    int *d_psflag = nullptr;
     /* nodes the up pass handles inside their parent's visit (see Up4Args.node_inline) */
     std::vector<int> node_inline(N, 0);
-    int *d_inl = nullptr;
     for (int p = 0; p < N; p++) {
         const int pdeg = h->indptr[p + 1] - h->indptr[p];
         if (pdeg < 1 || pdeg > 2) continue;
@@ -2763,43 +2820,28 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
         if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
     }
     if (!ps) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
-    const int *d_vis4 = nullptr, *d_ptabs = nullptr, *d_rebuild = nullptr;
-    double *d_tip4 = nullptr, *d_dtip4 = nullptr, *d_ptab4 = nullptr;
-    size_t nptab = 0;
-    auto cleanup = [&]() {};        /* everything below lives in grow-only engine buffers: no per-call hipMalloc / hipFree */
     const size_t ntab = (size_t)C * (ntips + 1) * h->nchar * 4;
-    {
-        /* all small integer tables of this call in one host block, one upload */
-        if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
-        std::vector<int> hd(h->node_has_data.begin(), h->node_has_data.end());
-        std::vector<int> pack;
-        auto put = [&](const int *src, size_t n) { const size_t off = pack.size(); pack.insert(pack.end(), src, src + n); while (pack.size() % 4) pack.push_back(0); return off; };
-        const size_t o_ops = put(reinterpret_cast<const int *>(ops2.data()), ops2.size() * 4);
-        const size_t o_et = put(edge_tip.data(), (size_t)E), o_ei = put(edge_int.data(), (size_t)E), o_ni = put(node_int.data(), (size_t)N);
-        const size_t o_te = put(te.data(), te.size()), o_has = put(hd.data(), (size_t)N), o_ns = put(node_scale.data(), (size_t)N);
-        const size_t o_oe = put(h->op_edge.data(), h->op_edge.size()), o_obs = put(h->obs_nodes.data(), h->obs_nodes.size());
-        const size_t o_inl = put(node_inline.data(), (size_t)N);
-        const size_t o_em = edge_mask && E > 0 ? put(edge_mask, (size_t)E) : 0, o_nm = node_mask ? put(node_mask, (size_t)N) : 0;
-        const size_t o_vis = nodes4 ? put(un4.rec.data(), un4.rec.size()) : 0;
-        const size_t o_pt = npairs4 ? put(pair_tabs.data(), pair_tabs.size()) : 0;
-        const size_t o_rb = any_rebuild ? put(rebuild_tab.data(), rebuild_tab.size()) : 0;
-        nptab = (size_t)C * npairs4 * h->nchar * h->nchar * 4;
-        if ((rc = dev_reserve(h, &h->d_u4pack, &h->u4pack_cap, pack.size() + 4))) return rc;    /* the spare word after the tables: the pair-sum pass's flag */
-        d_psflag = h->d_u4pack + pack.size();
-        if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, ntab * (size_t)(1 + nM) + nptab))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->d_u4pack, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));      /* pack is a local */
-        int *b = h->d_u4pack;
-        d_ops2 = reinterpret_cast<int4 *>(b + o_ops);
-        d_et = b + o_et; d_ei = b + o_ei; d_ni = b + o_ni; d_te = b + o_te; d_has = b + o_has; d_ns = b + o_ns;
-        d_oe2 = b + o_oe; d_obs2 = b + o_obs; d_inl = b + o_inl;
-        d_emask = edge_mask && E > 0 ? b + o_em : nullptr;
-        d_nmask = node_mask ? b + o_nm : nullptr;
-        d_vis4 = nodes4 ? b + o_vis : nullptr;
-        d_ptabs = npairs4 ? b + o_pt : nullptr;
-        d_rebuild = any_rebuild ? b + o_rb : nullptr;
-        d_tip4 = h->d_u4tip; d_dtip4 = h->d_u4tip + ntab; d_ptab4 = h->d_u4tip + ntab * (size_t)(1 + nM);
-    }
+    /* all small integer tables of this call in one host block, one upload */
+    IntPack pack;
+    const size_t o_ops = pack.put(reinterpret_cast<const int *>(ops2.data()), ops2.size() * 4);
+    const size_t o_et = pack.put(edge_tip.data(), (size_t)E), o_ei = pack.put(edge_int.data(), (size_t)E), o_ni = pack.put(node_int.data(), (size_t)N);
+    const size_t o_te = pack.put(sm.tip_edges.data(), sm.tip_edges.size()), o_has = pack.put_has_data(h), o_ns = pack.put(node_scale.data(), (size_t)N);
+    const size_t o_oe = pack.put(h->op_edge.data(), h->op_edge.size()), o_obs = pack.put(h->obs_nodes.data(), h->obs_nodes.size());
+    const size_t o_inl = pack.put(node_inline.data(), (size_t)N);
+    const size_t o_em = pack.put_opt(edge_mask, (size_t)E), o_nm = pack.put_opt(node_mask, (size_t)N);
+    const size_t o_vis = nodes4 ? pack.put(un4.rec.data(), un4.rec.size()) : 0;
+    const size_t o_pt = npairs4 ? pack.put(pair_tabs.data(), pair_tabs.size()) : 0;
+    const size_t o_rb = any_rebuild ? pack.put(rebuild_tab.data(), rebuild_tab.size()) : 0;
+    const size_t nptab = (size_t)C * npairs4 * h->nchar * h->nchar * 4;
+    if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, ntab * (size_t)(1 + nM) + nptab)) || (rc = pack.upload(h))) return rc;
+    int *const d_psflag = pack.flag(h);
+    const int *b = h->d_u4pack;
+    const int4 *d_ops2 = reinterpret_cast<const int4 *>(b + o_ops);
+    const int *d_et = b + o_et, *d_ei = b + o_ei, *d_ni = b + o_ni, *d_te = b + o_te, *d_has = b + o_has, *d_ns = b + o_ns;
+    const int *d_oe2 = b + o_oe, *d_obs2 = b + o_obs, *d_inl = b + o_inl;
+    const int *d_emask = edge_mask ? b + o_em : nullptr, *d_nmask = node_mask ? b + o_nm : nullptr;
+    const int *d_vis4 = nodes4 ? b + o_vis : nullptr, *d_ptabs = npairs4 ? b + o_pt : nullptr, *d_rebuild = any_rebuild ? b + o_rb : nullptr;
+    double *d_tip4 = h->d_u4tip, *d_dtip4 = h->d_u4tip + ntab, *d_ptab4 = h->d_u4tip + ntab * (size_t)(1 + nM);
     hipLaunchKernelGGL(k_build_tip, dim3(ntips + 1, C), dim3(64), 0, h->stream,
                        E, ntips + 1, h->nchar, d_te, h->d_Pdd, h->d_defs, d_tip4);
     for (int m = 0; m < nM; m++)
@@ -2808,22 +2850,16 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     if (npairs4)       /* pair tables: [C][npairs * nchar units][nchar][4], the ll kernels' builder on a list of pairs only */
         hipLaunchKernelGGL(k_build_tables_pt, dim3(npairs4, C), dim3(64), 0, h->stream,
                            E, npairs4, npairs4 * h->nchar, h->nchar, d_ptabs, h->d_Pdd, h->d_defs, d_ptab4);
-    if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
+    if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
 
-    const bool msum_only = marg && !site_out && sums_out && !deriv;      /* per-wave sums instead of the N x 4 planes */
+    const bool msum_only = marginal_sums_only(deriv, marg, site_out, sums_out);      /* per-wave sums instead of the N x 4 planes */
     const size_t per_site = ((size_t)(2 * (size_t)nin) * C * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? ER : 0) + (marg && !msum_only ? (size_t)N * 4 : 0)) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
-    budget += h->work_cap * sizeof(double);
-    long chunk = (long)std::min<size_t>((size_t)S, budget / (per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0)));
-    if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
-    if (chunk < 1) { cleanup(); h->err = "plk_deriv/plk_marginal: not enough device memory for one site"; return PLK_E_NOMEM; }
-    if (chunk < S) chunk = std::max<long>(UD4_BLOCK, chunk / UD4_BLOCK * UD4_BLOCK);
+    long chunk;
+    if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0), UD4_BLOCK, false, &chunk))) return rc;
     const size_t mvs_doubles = msum_only ? (size_t)N * 4 * (size_t)((chunk + UD4_BLOCK - 1) / UD4_BLOCK) * (UD4_BLOCK / 64) : 0;   /* per-wave marginal sums */
     const size_t ps_rows = ps ? (ps->mix_D ? (size_t)2 * MIX4_MAX_C : (size_t)C * E * 16 + (size_t)C * 4) : 0;
     const size_t ps_doubles = ps ? ps_rows * pair_sums_grid(h, (chunk + PS4_BLOCK - 1) / PS4_BLOCK) : 0;
-    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles + ps_doubles))) { cleanup(); return rc; }
+    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles + ps_doubles))) return rc;
     if (ps) {
         ps->acc.assign(ps_rows, 0.0L);
         HIPCHK(h, hipMemsetAsync(d_psflag, 0, sizeof(int), h->stream));
@@ -2871,16 +2907,16 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
                 MixSensOut mo;
                 mo.part = p; mo.flag = d_psflag; mo.wsite = h->d_w ? h->d_w + s0 : nullptr; mo.D = ps->mix_D;
                 hipLaunchKernelGGL(k_up4_mixsens, dim3(pgrid), dim3(PS4_BLOCK), 0, h->stream, a, mo, (int)nbatch);   /* every row of part is written */
-                if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_mixture_sens: kernel launch failed"; return PLK_E_DEVICE; }
-                if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, mo.part, d_psflag))) { cleanup(); return rc; }
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_mixture_sens: kernel launch failed"; return PLK_E_DEVICE; }
+                if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, mo.part, d_psflag))) return rc;
                 continue;
             }
             PairSumOut o;
             o.part = p; o.flag = d_psflag; o.wsite = h->d_w ? h->d_w + s0 : nullptr; o.want_root = ps->want_root ? 1 : 0;
             HIPCHK(h, hipMemsetAsync(o.part, 0, ps_rows * pgrid * sizeof(double), h->stream));     /* masked edges: exactly 0 */
             hipLaunchKernelGGL(k_up4_pairsums, dim3(pgrid), dim3(PS4_BLOCK), 0, h->stream, a, o, (int)nbatch);
-            if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_edge_pair_sums: kernel launch failed"; return PLK_E_DEVICE; }
-            if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, o.part, d_psflag))) { cleanup(); return rc; }
+            if (hipGetLastError() != hipSuccess) { h->err = "plk_edge_pair_sums: kernel launch failed"; return PLK_E_DEVICE; }
+            if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, o.part, d_psflag))) return rc;
             continue;
         }
         if (nodes4 && C == 1) hipLaunchKernelGGL(k_up4_nodes<1>, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
@@ -2891,27 +2927,12 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
         else if (deriv && nM == 4) hipLaunchKernelGGL((k_up4<true, false, 4>), dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
         else if (deriv) hipLaunchKernelGGL((k_up4<true, false>), dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
         else hipLaunchKernelGGL((k_up4<false, true>), dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
-        if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_deriv/plk_marginal: kernel launch failed"; return PLK_E_DEVICE; }
-        if (sums_out) {
-            const double *w = h->d_w ? h->d_w + s0 : nullptr;
-            if (deriv && E > 0 && (rc = wsum_rows(h, ER, n, a.DV, w, dsum.data()))) { cleanup(); return rc; }
-            if (marg && msum_only) { if ((rc = wsum_rows(h, N * 4, (long)nwv, a.MVS, nullptr, msum.data()))) { cleanup(); return rc; } }
-            else if (marg && (rc = wsum_rows(h, N * 4, n, a.MV, w, msum.data()))) { cleanup(); return rc; }
-        }
-        if (site_out && (rc = copy_site_rows(h, deriv ? (size_t)ER : (size_t)N * 4, n, s0, deriv ? a.DV : a.MV, site_out))) { cleanup(); return rc; }
+        if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: kernel launch failed"; return PLK_E_DEVICE; }
+        UpDownOut o;
+        o.drows = dsum.size(); o.mrows = msum.size(); o.nwv = nwv; o.DV = a.DV; o.MV = a.MV; o.MVS = a.MVS;
+        if ((rc = updown_chunk_out(h, o, n, s0, sums_out != nullptr, dsum.data(), msum.data(), site_out))) return rc;
     }
-    hipError_t e = hipStreamSynchronize(h->stream);
-    cleanup();
-    if (e != hipSuccess) { h->err = std::string("plk_deriv/plk_marginal: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
-    if (sums_out) {
-        const std::vector<long double> &src = deriv ? dsum : msum;
-        for (size_t r = 0; r < src.size(); r++) {
-            const double hi = (double)src[r];
-            sums_out[2 * r] = hi;
-            sums_out[2 * r + 1] = (double)(src[r] - (long double)hi);
-        }
-    }
-    return PLK_OK;
+    return updown_finish(h, sums_out, deriv ? dsum : msum);
 }
 
 /* deriv / marginal / edge expectations for 9 <= k <= 20 with compact codes: register-resident vector kernels
@@ -2937,13 +2958,9 @@ static int run_updown_vec(plk_engine *h, bool deriv, bool marg, const int *edge_
     const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
     const long S = h->S;
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
-    const int ntips = (int)h->tip_edge.size();
-    std::vector<int> edge_tip(E, -1), edge_int(E, -1), node_int(N, -1), node_scale(N, -1);
-    for (int t = 0; t < ntips; t++) edge_tip[h->tip_edge[t]] = t;
-    int nie = 0, nin = 0, nsc = 0;
-    for (int e = 0; e < E; e++) if (edge_tip[e] < 0) edge_int[e] = nie++;
-    for (int a = 0; a < N; a++) if (h->indptr[a + 1] > h->indptr[a]) node_int[a] = nin++;
-    for (int a = 0; a < N; a++) if (node_int[a] >= 0 && h->scale_node[a]) node_scale[a] = nsc++;
+    const PlkStorageMaps sm = storage_maps(h);
+    const std::vector<int> &edge_tip = sm.edge_tip, &node_int = sm.node_int, &node_scale = sm.node_scale;
+    const int ntips = sm.ntips, nie = sm.nie, nin = sm.nin, nsc = sm.nsc;
     /* down-pass program and up-pass visit records + matrix list, both checked before anything is launched */
     /* nodes finished inside their parent's visit (no marginals asked for): the up pass rebuilds their L vector from the
      * tip tables, so the down pass does not store it (a third of the stored vectors at BASELINE config 4) */
@@ -2962,16 +2979,13 @@ static int run_updown_vec(plk_engine *h, bool deriv, bool marg, const int *edge_
     }
     const int nstream = (int)uv.kind.size();
     const int nslots = std::max(h->slots_needed, 1);
-    std::vector<int> te = h->tip_edge;
-    te.push_back(-1);
     /* integer tables of this call: one upload into the grow-only block */
-    std::vector<int> pack;
-    auto put = [&](const int *src, size_t n) { const size_t off = pack.size(); pack.insert(pack.end(), src, src + n); while (pack.size() % 4) pack.push_back(0); return off; };
-    const size_t o_ops = put(reinterpret_cast<const int *>(ch.ops.data()), ch.ops.size() * 4);
-    const size_t o_obs = put(h->obs_nodes.data(), h->obs_nodes.size());
-    const size_t o_vis = put(uv.rec.data(), uv.rec.size());
-    const size_t o_kind = put(uv.kind.data(), uv.kind.size()), o_edge = put(uv.edge.data(), uv.edge.size());
-    const size_t o_te = put(te.data(), te.size());
+    IntPack pack;
+    const size_t o_ops = pack.put(reinterpret_cast<const int *>(ch.ops.data()), ch.ops.size() * 4);
+    const size_t o_obs = pack.put(h->obs_nodes.data(), h->obs_nodes.size());
+    const size_t o_vis = pack.put(uv.rec.data(), uv.rec.size());
+    const size_t o_kind = pack.put(uv.kind.data(), uv.kind.size()), o_edge = pack.put(uv.edge.data(), uv.edge.size());
+    const size_t o_te = pack.put(sm.tip_edges.data(), sm.tip_edges.size());
     /* the state a character code observes: its definition row is one 1.0 among zeros (leaf marginals of such codes are one
      * dot product in the up pass instead of a matrix-vector product) */
     std::vector<int> code_state((size_t)std::max(h->nchar, 1), -1);
@@ -2980,14 +2994,11 @@ static int run_updown_vec(plk_engine *h, bool deriv, bool marg, const int *edge_
         for (int j = 0; j < k; j++) if (h->defs[(size_t)cd * k + j] != 0.0) { nnz++; at = j; }
         if (nnz == 1 && h->defs[(size_t)cd * k + at] == 1.0) code_state[cd] = at;
     }
-    const size_t o_cs = put(code_state.data(), code_state.size());
+    const size_t o_cs = pack.put(code_state.data(), code_state.size());
     const size_t ntab = (size_t)C * (ntips + 1) * h->nchar * K;
     const size_t nmat = (size_t)C * E * K * K + (size_t)C * (nstream + 3) * K * K;
-    if ((rc = dev_reserve(h, &h->d_u4pack, &h->u4pack_cap, pack.size() + 4)) ||
-        (rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, 2 * ntab)) ||
-        (rc = dev_reserve(h, &h->d_uvmat, &h->uvmat_cap, nmat))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_u4pack, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));      /* pack is a local */
+    if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, 2 * ntab)) ||
+        (rc = dev_reserve(h, &h->d_uvmat, &h->uvmat_cap, nmat)) || (rc = pack.upload(h))) return rc;
     const int *b = h->d_u4pack;
     double *d_PT = h->d_uvmat, *d_MS = h->d_uvmat + (size_t)C * E * K * K;
     double *d_tipv = h->d_u4tip, *d_dtipv = h->d_u4tip + ntab;
@@ -3001,16 +3012,10 @@ static int run_updown_vec(plk_engine *h, bool deriv, bool marg, const int *edge_
                        k, K, E, ntips, h->nchar, b + o_te, d_M, h->d_defs, K, d_dtipv, dzero);
     if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
 
-    const bool msum_only = marg && !site_out && sums_out && !deriv;      /* per-wave sums instead of the N x k planes */
+    const bool msum_only = marginal_sums_only(deriv, marg, site_out, sums_out);      /* per-wave sums instead of the N x k planes */
     const size_t per_site = ((size_t)(2 * (size_t)nin) * C * K + (size_t)nslots * K + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg && !msum_only ? (size_t)N * k : 0)) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
-    budget += h->work_cap * sizeof(double);
-    long chunk = (long)std::min<size_t>((size_t)S, budget / (per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0)));
-    if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
-    if (chunk < 1) { h->err = "plk_deriv/plk_marginal: not enough device memory for one site"; return PLK_E_NOMEM; }
-    if (chunk < S) chunk = std::max<long>(UDV_BLOCK, chunk / UDV_BLOCK * UDV_BLOCK);
+    long chunk;
+    if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0), UDV_BLOCK, false, &chunk))) return rc;
     const size_t mvs_doubles = msum_only ? (size_t)N * k * (size_t)((chunk + UDV_BLOCK - 1) / UDV_BLOCK) * (UDV_BLOCK / 64) : 0;   /* per-wave marginal sums */
     if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + mvs_doubles))) return rc;
 
@@ -3045,24 +3050,11 @@ static int run_updown_vec(plk_engine *h, bool deriv, bool marg, const int *edge_
         if (K == 16) launch_updown_vec<16>(h, a, b + o_obs, grid, deriv, marg);
         else launch_updown_vec<20>(h, a, b + o_obs, grid, deriv, marg);
         if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: kernel launch failed"; return PLK_E_DEVICE; }
-        if (sums_out) {
-            const double *w = h->d_w ? h->d_w + s0 : nullptr;
-            if (deriv && (rc = wsum_rows(h, E, n, a.DV, w, dsum.data()))) return rc;
-            if (marg && msum_only) { if ((rc = wsum_rows(h, N * k, (long)nwv, a.MVS, nullptr, msum.data()))) return rc; }
-            else if (marg && (rc = wsum_rows(h, N * k, n, a.MV, w, msum.data()))) return rc;
-        }
-        if (site_out && (rc = copy_site_rows(h, deriv ? (size_t)E : (size_t)N * k, n, s0, deriv ? a.DV : a.MV, site_out))) return rc;
+        UpDownOut o;
+        o.drows = dsum.size(); o.mrows = msum.size(); o.nwv = nwv; o.DV = a.DV; o.MV = a.MV; o.MVS = a.MVS;
+        if ((rc = updown_chunk_out(h, o, n, s0, sums_out != nullptr, dsum.data(), msum.data(), site_out))) return rc;
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (sums_out) {
-        const std::vector<long double> &src = deriv ? dsum : msum;
-        for (size_t r = 0; r < src.size(); r++) {
-            const double hi = (double)src[r];
-            sums_out[2 * r] = hi;
-            sums_out[2 * r + 1] = (double)(src[r] - (long double)hi);
-        }
-    }
-    return PLK_OK;
+    return updown_finish(h, sums_out, deriv ? dsum : msum);
 }
 
 static bool use_updown4(const plk_engine *h)
@@ -3095,53 +3087,37 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     if (!ps) h->info_updown_kernel = 2;
     const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
     const long S = h->S;
-    /* padded edge-indexed streams */
-    double *d_PT = nullptr, *d_PN = nullptr, *d_DT = nullptr;
-    int *d_emask = nullptr, *d_nmask = nullptr;
-    int *d_has = nullptr, *d_ns = nullptr, *d_psflag = nullptr;
-    const size_t strm = (size_t)C * E * K * K;
-    auto cleanup = [&]() {
-        if (d_PT) (void)hipFree(d_PT);
-        if (d_PN) (void)hipFree(d_PN);
-        if (d_DT) (void)hipFree(d_DT);
-        if (d_emask) (void)hipFree(d_emask);
-        if (d_nmask) (void)hipFree(d_nmask);
-        if (d_has) (void)hipFree(d_has);
-        if (d_ns) (void)hipFree(d_ns);
-        if (d_psflag) (void)hipFree(d_psflag);
-    };
-    if ((rc = dev_alloc(h, &d_PT, strm)) || (rc = dev_alloc(h, &d_PN, strm)) || (rc = dev_alloc(h, &d_DT, strm))) { cleanup(); return rc; }
+    /* padded edge-indexed streams in the grow-only matrix buffer; each starts at a multiple of 32 doubles (256 bytes, what
+     * an allocation of its own would give it), also when K K C E is odd */
+    const size_t strm = ((size_t)C * E * K * K + 31) / 32 * 32;
+    if ((rc = dev_reserve(h, &h->d_uvmat, &h->uvmat_cap, 3 * strm))) return rc;
+    double *d_PT = h->d_uvmat, *d_PN = d_PT + strm, *d_DT = d_PN + strm;
     const int bt = K * K >= 256 ? 256 : 64;
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, h->d_P, d_PT);
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 1, h->d_P, d_PN);
     if (!ps || ps->mix_D) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
-    if (edge_mask && (rc = dev_upload(h, &d_emask, edge_mask, (size_t)E))) { cleanup(); return rc; }
-    if (node_mask && (rc = dev_upload(h, &d_nmask, node_mask, (size_t)N))) { cleanup(); return rc; }
-    if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
-    { std::vector<int> hd(h->node_has_data.begin(), h->node_has_data.end()); if ((rc = dev_upload(h, &d_has, hd.data(), (size_t)N))) { cleanup(); return rc; } }
+    /* the call's integer tables; of the storage maps the generic kernels take the rescaling slots only */
+    if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
+    const PlkStorageMaps sm = storage_maps(h);
+    const int nsc = sm.nsc;
+    IntPack pack;
+    const size_t o_em = pack.put_opt(edge_mask, (size_t)E), o_nm = pack.put_opt(node_mask, (size_t)N);
+    const size_t o_has = pack.put_has_data(h), o_ns = pack.put(sm.node_scale.data(), (size_t)N);
+    if ((rc = pack.upload(h))) return rc;
+    const int *pk = h->d_u4pack;
+    const int *d_emask = edge_mask ? pk + o_em : nullptr, *d_nmask = node_mask ? pk + o_nm : nullptr, *d_has = pk + o_has, *d_ns = pk + o_ns;
+    int *const d_psflag = pack.flag(h);
 
     /* chunk the site axis so that the stored vectors fit */
-    if (h->prog_dirty) { if ((rc = build_program(h))) { cleanup(); return rc; } }
-    std::vector<int> node_scale(N, -1);
-    int nsc = 0;
-    for (int a = 0; a < N; a++) if (h->indptr[a + 1] > h->indptr[a] && h->scale_node[a]) node_scale[a] = nsc++;
-    if ((rc = dev_upload(h, &d_ns, node_scale.data(), (size_t)N))) { cleanup(); return rc; }
     const size_t per_site = ((size_t)(E + 2 * (size_t)N) * C * k + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg ? (size_t)N * k : 0)) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
-    budget += h->work_cap * sizeof(double);
-    long chunk = (long)std::min<size_t>((size_t)S, budget / per_site);
-    if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
-    if (chunk < 1) { cleanup(); h->err = "plk_deriv/plk_marginal: not enough device memory for one site"; return PLK_E_NOMEM; }
-    if (chunk < S) chunk = std::max<long>(GEN_BLOCK, chunk / GEN_BLOCK * GEN_BLOCK);
+    long chunk;
+    if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site, GEN_BLOCK, false, &chunk))) return rc;
     const size_t ps_rows = ps ? (ps->mix_D ? (size_t)2 * C : (size_t)C * E * k * k + (size_t)C * k) : 0;
     const size_t ps_doubles = ps ? ps_rows * pair_sums_grid(h, (chunk + GEN_BLOCK - 1) / GEN_BLOCK) : 0;
-    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + ps_doubles))) { cleanup(); return rc; }
+    if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site / sizeof(double) * (size_t)chunk + ps_doubles))) return rc;
     if (ps) {
         ps->acc.assign(ps_rows, 0.0L);
-        if ((rc = dev_alloc(h, &d_psflag, 1))) { cleanup(); return rc; }
-        HIPCHKC(h, hipMemsetAsync(d_psflag, 0, sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(d_psflag, 0, sizeof(int), h->stream));
     }
 
     std::vector<long double> dsum(deriv ? E : 0, 0.0L), msum(marg ? (size_t)N * k : 0, 0.0L);
@@ -3166,75 +3142,34 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
         a.LH = p; p += n;
         a.DV = p; if (deriv) p += (size_t)E * n;
         a.MV = p; if (marg) p += (size_t)N * k * n;
-        if (deriv) HIPCHKC(h, hipMemsetAsync(a.DV, 0, (size_t)E * n * sizeof(double), h->stream));
-        if (marg) HIPCHKC(h, hipMemsetAsync(a.MV, 0, (size_t)N * k * n * sizeof(double), h->stream));
+        if (deriv) HIPCHK(h, hipMemsetAsync(a.DV, 0, (size_t)E * n * sizeof(double), h->stream));
+        if (marg) HIPCHK(h, hipMemsetAsync(a.MV, 0, (size_t)N * k * n * sizeof(double), h->stream));
         const unsigned grid = (unsigned)((n + GEN_BLOCK - 1) / GEN_BLOCK);
         if (ps) {
             const unsigned pgrid = pair_sums_grid(h, (long)grid);
             if (ps->mix_D) {
                 MixSensOut mo;
                 mo.part = p; mo.flag = d_psflag; mo.wsite = h->d_w ? h->d_w + s0 : nullptr; mo.D = nullptr;
-                switch (K) {
-                case 2: launch_mixsens<2>(h, a, mo, grid, pgrid); break;
-                case 4: launch_mixsens<4>(h, a, mo, grid, pgrid); break;
-                case 8: launch_mixsens<8>(h, a, mo, grid, pgrid); break;
-                case 16: launch_mixsens<16>(h, a, mo, grid, pgrid); break;
-                case 20: launch_mixsens<20>(h, a, mo, grid, pgrid); break;
-                case 32: launch_mixsens<32>(h, a, mo, grid, pgrid); break;
-                case 61: launch_mixsens<61>(h, a, mo, grid, pgrid); break;
-                default: launch_mixsens<64>(h, a, mo, grid, pgrid); break;
-                }
-                if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_mixture_sens: kernel launch failed"; return PLK_E_DEVICE; }
-                if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, mo.part, d_psflag))) { cleanup(); return rc; }
+                dispatch_K(K, [&](auto Kc) { launch_mixsens<decltype(Kc)::value>(h, a, mo, grid, pgrid); });
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_mixture_sens: kernel launch failed"; return PLK_E_DEVICE; }
+                if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, mo.part, d_psflag))) return rc;
                 continue;
             }
             PairSumOut o;
             o.part = p; o.flag = d_psflag; o.wsite = h->d_w ? h->d_w + s0 : nullptr; o.want_root = ps->want_root ? 1 : 0;
-            HIPCHKC(h, hipMemsetAsync(o.part, 0, ps_rows * pgrid * sizeof(double), h->stream));     /* masked edges: exactly 0 */
-            switch (K) {
-            case 2: launch_pairsums<2>(h, a, o, grid, pgrid); break;
-            case 4: launch_pairsums<4>(h, a, o, grid, pgrid); break;
-            case 8: launch_pairsums<8>(h, a, o, grid, pgrid); break;
-            case 16: launch_pairsums<16>(h, a, o, grid, pgrid); break;
-            case 20: launch_pairsums<20>(h, a, o, grid, pgrid); break;
-            case 32: launch_pairsums<32>(h, a, o, grid, pgrid); break;
-            case 61: launch_pairsums<61>(h, a, o, grid, pgrid); break;
-            default: launch_pairsums<64>(h, a, o, grid, pgrid); break;
-            }
-            if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_edge_pair_sums: kernel launch failed"; return PLK_E_DEVICE; }
-            if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, o.part, d_psflag))) { cleanup(); return rc; }
+            HIPCHK(h, hipMemsetAsync(o.part, 0, ps_rows * pgrid * sizeof(double), h->stream));     /* masked edges: exactly 0 */
+            dispatch_K(K, [&](auto Kc) { launch_pairsums<decltype(Kc)::value>(h, a, o, grid, pgrid); });
+            if (hipGetLastError() != hipSuccess) { h->err = "plk_edge_pair_sums: kernel launch failed"; return PLK_E_DEVICE; }
+            if ((rc = pair_sums_finish(h, ps, ps_rows, pgrid, o.part, d_psflag))) return rc;
             continue;
         }
-        switch (K) {
-        case 2: launch_updown<2>(h, a, grid, deriv, marg); break;
-        case 4: launch_updown<4>(h, a, grid, deriv, marg); break;
-        case 8: launch_updown<8>(h, a, grid, deriv, marg); break;
-        case 16: launch_updown<16>(h, a, grid, deriv, marg); break;
-        case 20: launch_updown<20>(h, a, grid, deriv, marg); break;
-        case 32: launch_updown<32>(h, a, grid, deriv, marg); break;
-        case 61: launch_updown<61>(h, a, grid, deriv, marg); break;
-        default: launch_updown<64>(h, a, grid, deriv, marg); break;
-        }
-        if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_deriv/plk_marginal: kernel launch failed"; return PLK_E_DEVICE; }
-        if (sums_out) {
-            const double *w = h->d_w ? h->d_w + s0 : nullptr;
-            if (deriv && (rc = wsum_rows(h, E, n, a.DV, w, dsum.data()))) { cleanup(); return rc; }
-            if (marg && (rc = wsum_rows(h, N * k, n, a.MV, w, msum.data()))) { cleanup(); return rc; }
-        }
-        if (site_out && (rc = copy_site_rows(h, deriv ? (size_t)E : (size_t)N * k, n, s0, deriv ? a.DV : a.MV, site_out))) { cleanup(); return rc; }
+        dispatch_K(K, [&](auto Kc) { launch_updown<decltype(Kc)::value>(h, a, grid, deriv, marg); });
+        if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: kernel launch failed"; return PLK_E_DEVICE; }
+        UpDownOut o;
+        o.drows = dsum.size(); o.mrows = msum.size(); o.DV = a.DV; o.MV = a.MV;
+        if ((rc = updown_chunk_out(h, o, n, s0, sums_out != nullptr, dsum.data(), msum.data(), site_out))) return rc;
     }
-    hipError_t e = hipStreamSynchronize(h->stream);
-    cleanup();
-    if (e != hipSuccess) { h->err = std::string("plk_deriv/plk_marginal: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
-    if (sums_out) {
-        const std::vector<long double> &src = deriv ? dsum : msum;
-        for (size_t r = 0; r < src.size(); r++) {
-            const double hi = (double)src[r];
-            sums_out[2 * r] = hi;
-            sums_out[2 * r + 1] = (double)(src[r] - (long double)hi);
-        }
-    }
-    return PLK_OK;
+    return updown_finish(h, sums_out, deriv ? dsum : msum);
 }
 
 /* ====================================================================== */
@@ -3337,8 +3272,7 @@ extern "C" int plk_edge_expect_multi(plk_engine *h, int nL, const double *L_hi, 
     const size_t kk = (size_t)k * k, n2 = 4 * kk;
     /* how many directions one pass of the kernels can carry */
     const int per_pass = use_updown4(h) && !use_mfma(h) ? 4 : 1;
-    /* grow-only engine buffers: no per-call hipMalloc / hipFree */
-    auto cleanup = [&]() {};
+    /* everything below lives in grow-only engine buffers: no per-call hipMalloc / hipFree */
     const int threads = n2 >= 1024 ? 1024 : (n2 >= 256 ? 256 : 64);
     int use_lds;
     const size_t lds_bytes = expm_lds_bytes((size_t)2 * k, threads, &use_lds);
@@ -3376,13 +3310,12 @@ extern "C" int plk_edge_expect_multi(plk_engine *h, int nL, const double *L_hi, 
         if (site_out) { if (nm == nL) so = site_out; else { tmp_site.assign((size_t)S * nm * E, 0.0); so = tmp_site.data(); } }
         if (sums_out) su = sums_out + (size_t)m0 * E * 2;
         rc = run_updown(h, true, false, edge_mask, nullptr, so, su, d_F, 0, nm);
-        if (rc) { cleanup(); return rc; }
+        if (rc) return rc;
         if (site_out && nm != nL)
             for (long s = 0; s < S; s++)
                 for (int r = 0; r < nm * E; r++)
                     site_out[((size_t)s * nL + m0) * E + r] = tmp_site[(size_t)s * nm * E + r];
     }
-    cleanup();
     return PLK_OK;
 }
 
@@ -3446,13 +3379,6 @@ static int pair_sums_run(plk_engine *h, const int *edge_mask, PairSumReq &ps, co
     return PLK_OK;
 }
 
-static inline void put_dd(double *dst, long double v)
-{
-    const double hi = (double)v;
-    dst[0] = hi;
-    dst[1] = (double)(v - (long double)hi);
-}
-
 extern "C" int plk_edge_pair_sums(plk_engine *h, const int *edge_mask, double *W_out, double *root_out)
 {
     if (!plk_live(h)) return PLK_E_ARG;
@@ -3463,8 +3389,8 @@ extern "C" int plk_edge_pair_sums(plk_engine *h, const int *edge_mask, double *W
     int rc;
     if ((rc = pair_sums_run(h, edge_mask, ps, "plk_edge_pair_sums"))) return rc;
     const size_t nW = (size_t)h->C * h->E * h->k * h->k;
-    for (size_t r = 0; r < nW; r++) put_dd(W_out + 2 * r, ps.acc[r]);
-    if (root_out) for (size_t r = 0; r < (size_t)h->C * h->k; r++) put_dd(root_out + 2 * r, ps.acc[nW + r]);
+    put_dd_rows(W_out, ps.acc.data(), nW);
+    if (root_out) put_dd_rows(root_out, ps.acc.data() + nW, (size_t)h->C * h->k);
     return PLK_OK;
 }
 
@@ -3527,7 +3453,7 @@ extern "C" int plk_rate_matrix_sens(plk_engine *h, double *G_out, double *root_o
     for (size_t ce = 0; ce < CE; ce++)
         for (int i = 0; i < k; i++)
             for (int j = 0; j < k; j++) G[(size_t)i * k + j] += ldexpl((long double)F[ce * kk + (size_t)j * k + i], expo[ce]);
-    for (size_t r = 0; r < kk; r++) put_dd(G_out + 2 * r, G[r]);
+    put_dd_rows(G_out, G.data(), kk);
     if (root_out) {
         const size_t nW = CE * kk;
         for (int i = 0; i < k; i++) {
@@ -3692,16 +3618,7 @@ static int cat_posterior_impl(plk_engine *h, double *post_out, double *rate_out,
         a.g.codes = h->d_codes; a.g.defs = h->d_defs; a.g.B = h->d_B; a.g.cat_prior = h->d_cat_prior;
         a.g.root_w = h->d_root_w; a.g.w = h->d_w; a.g.slots = h->d_slots; a.g.site_ll = d_ll; a.g.partial = nullptr;
         a.cat_rates = h->d_cat_rates; a.post = d_post; a.expo = h->d_cp_expo; a.rate = d_rate; a.partial = d_part; a.zero_flag = h->d_cp_flag;
-        switch (K) {
-        case 2: launch_catpost_generic<2>(h, a, grid); break;
-        case 4: launch_catpost_generic<4>(h, a, grid); break;
-        case 8: launch_catpost_generic<8>(h, a, grid); break;
-        case 16: launch_catpost_generic<16>(h, a, grid); break;
-        case 20: launch_catpost_generic<20>(h, a, grid); break;
-        case 32: launch_catpost_generic<32>(h, a, grid); break;
-        case 61: launch_catpost_generic<61>(h, a, grid); break;
-        default: launch_catpost_generic<64>(h, a, grid); break;
-        }
+        dispatch_K(K, [&](auto Kc) { launch_catpost_generic<decltype(Kc)::value>(h, a, grid); });
         h->info_cat_posterior_kernel = 2;
     }
     HIPCHK(h, hipGetLastError());
@@ -3947,16 +3864,7 @@ static void launch_hess_pass(plk_engine *h, const UpArgs &a, unsigned grid)
 
 static void launch_hess_pass_k(plk_engine *h, const UpArgs &a, unsigned grid)
 {
-    switch (h->K) {
-    case 2: launch_hess_pass<2>(h, a, grid); break;
-    case 4: launch_hess_pass<4>(h, a, grid); break;
-    case 8: launch_hess_pass<8>(h, a, grid); break;
-    case 16: launch_hess_pass<16>(h, a, grid); break;
-    case 20: launch_hess_pass<20>(h, a, grid); break;
-    case 32: launch_hess_pass<32>(h, a, grid); break;
-    case 61: launch_hess_pass<61>(h, a, grid); break;
-    default: launch_hess_pass<64>(h, a, grid); break;
-    }
+    dispatch_K(h->K, [&](auto Kc) { launch_hess_pass<decltype(Kc)::value>(h, a, grid); });
 }
 
 /*
@@ -4018,26 +3926,18 @@ static int second_order_generic(plk_engine *h, std::vector<long double> &Hrow, s
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 1, h->d_dP, d_DN);
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, d_d2P, d_D2T);
     if (hipGetLastError() != hipSuccess) { cleanup(); h->err = "plk_hess: matrix set-up failed"; return PLK_E_DEVICE; }
-    if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
-    { std::vector<int> hd(h->node_has_data.begin(), h->node_has_data.end()); if ((rc = dev_upload(h, &d_has, hd.data(), (size_t)N))) { cleanup(); return rc; } }
+    { const std::vector<int> hd = has_data_ints(h); if ((rc = dev_upload(h, &d_has, hd.data(), (size_t)N))) { cleanup(); return rc; } }
 
     /* exact power-of-two rescaling as in the first-order passes (trees of any size): the traversal program marks the
      * nodes, the factors are stored per pass, every pass reports the common exponent of its site likelihoods */
     if (h->prog_dirty) { if ((rc = build_program(h))) { cleanup(); return rc; } }
-    std::vector<int> node_scale(N, -1);
-    int nsc = 0;
-    for (int a = 0; a < N; a++) if (h->indptr[a + 1] > h->indptr[a] && h->scale_node[a]) node_scale[a] = nsc++;
-    if ((rc = dev_upload(h, &d_ns, node_scale.data(), (size_t)N))) { cleanup(); return rc; }
+    const PlkStorageMaps sm = storage_maps(h);
+    const int nsc = sm.nsc;
+    if ((rc = dev_upload(h, &d_ns, sm.node_scale.data(), (size_t)N))) { cleanup(); return rc; }
     const size_t per_site_d = (size_t)(E + 2 * (size_t)N) * C * k + (size_t)(nsc + 2) * C + 2 + (size_t)E;
     const size_t per_site = (per_site_d + 2 + (size_t)E) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
-    budget += h->work_cap * sizeof(double);
-    long chunk = (long)std::min<size_t>((size_t)S, budget / per_site);
-    if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
-    if (chunk < 1) { cleanup(); h->err = "plk_hess: not enough device memory for one site"; return PLK_E_NOMEM; }
-    if (chunk < S) chunk = std::max<long>(GEN_BLOCK, chunk / GEN_BLOCK * GEN_BLOCK);
+    long chunk;
+    if ((rc = plan_site_chunk(h, "plk_hess", per_site, GEN_BLOCK, false, &chunk))) { cleanup(); return rc; }
     if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site_d * (size_t)chunk)) ||
         (rc = dev_alloc(h, &d_LH0, (size_t)chunk)) || (rc = dev_alloc(h, &d_XM0, (size_t)chunk)) ||
         (rc = dev_alloc(h, &d_D0, (size_t)E * chunk))) { cleanup(); return rc; }
@@ -4119,16 +4019,10 @@ static int second_order_k4(plk_engine *h, std::vector<long double> &Hrow, std::v
     const int N = h->N, E = h->E, C = h->C;
     const long S = h->S;
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
-    const int ntips = (int)h->tip_edge.size();
-    std::vector<int> edge_tip(E, -1), node_int(N, -1), node_scale(N, -1);
-    for (int t = 0; t < ntips; t++) edge_tip[h->tip_edge[t]] = t;
-    int nin = 0, nsc = 0;
-    for (int a = 0; a < N; a++) if (h->indptr[a + 1] > h->indptr[a]) node_int[a] = nin++;
-    for (int a = 0; a < N; a++) if (node_int[a] >= 0 && h->scale_node[a]) node_scale[a] = nsc++;
-    std::vector<int> te = h->tip_edge;
-    te.push_back(-1);
-    if (h->node_has_data.size() != (size_t)N) h->node_has_data.assign(N, 1);
-    std::vector<int> hd(h->node_has_data.begin(), h->node_has_data.end());
+    const PlkStorageMaps sm = storage_maps(h);
+    const std::vector<int> &edge_tip = sm.edge_tip, &node_int = sm.node_int, &node_scale = sm.node_scale, &te = sm.tip_edges;
+    const int ntips = sm.ntips, nin = sm.nin, nsc = sm.nsc;
+    const std::vector<int> hd = has_data_ints(h);
 
     double *d_Q2 = nullptr, *d_d2P = nullptr, *d_tab = nullptr, *d_LH0 = nullptr, *d_XM0 = nullptr, *d_D0 = nullptr;
     dd *d_G = nullptr;
@@ -4154,14 +4048,8 @@ static int second_order_k4(plk_engine *h, std::vector<long double> &Hrow, std::v
     const size_t per_model = 2 * vs1 + sc1 + 2 * (size_t)C + 2 + (size_t)E;
     const size_t per_site_d = (size_t)NMX * per_model;
     const size_t per_site = (per_site_d + 2 + (size_t)E) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
-    budget += h->work_cap * sizeof(double);
-    long chunk = (long)std::min<size_t>((size_t)S, budget / per_site);
-    if (h->opt_site_chunk > 0) chunk = std::min<long>(chunk, h->opt_site_chunk);
-    if (chunk < 1) { cleanup(); h->err = "plk_second_order: not enough device memory for one site"; return PLK_E_NOMEM; }
-    if (chunk < S) chunk = std::max<long>(UD4_BLOCK, chunk / UD4_BLOCK * UD4_BLOCK);
+    long chunk;
+    if ((rc = plan_site_chunk(h, "plk_second_order", per_site, UD4_BLOCK, false, &chunk))) { cleanup(); return rc; }
     if ((rc = dev_reserve(h, &h->d_work, &h->work_cap, per_site_d * (size_t)chunk)) ||
         (rc = dev_alloc(h, &d_LH0, (size_t)chunk)) || (rc = dev_alloc(h, &d_XM0, (size_t)chunk)) ||
         (rc = dev_alloc(h, &d_D0, (size_t)E * chunk))) { cleanup(); return rc; }
@@ -4242,20 +4130,14 @@ extern "C" int plk_second_order(plk_engine *h, double *grad_sums_out /* [E][2] o
     if (use_hess4(h)) { h->info_updown_kernel = 5; rc = second_order_k4(h, Hrow, G, grad_sums_out ? gsum.data() : nullptr); }
     else { h->info_updown_kernel = 2; rc = second_order_generic(h, Hrow, G, grad_sums_out ? gsum.data() : nullptr); }
     if (rc) return rc;
-    if (grad_sums_out)
-        for (int i = 0; i < E; i++) {
-            const double hi = (double)gsum[i];
-            grad_sums_out[2 * i] = hi;
-            grad_sums_out[2 * i + 1] = (double)(gsum[i] - (long double)hi);
-        }
+    if (grad_sums_out) put_dd_rows(grad_sums_out, gsum.data(), gsum.size());
     if (hess_sums_out)
         for (int i = 0; i < E; i++)
             for (int j = 0; j <= i; j++) {
                 /* both triangles of the likelihood Hessian were computed; average them */
                 const long double v = (Hrow[(size_t)i * E + j] + Hrow[(size_t)j * E + i]) * 0.5L - G[(size_t)i * E + j];
-                const double hi = (double)v, lo = (double)(v - (long double)hi);
-                hess_sums_out[2 * ((size_t)i * E + j)] = hess_sums_out[2 * ((size_t)j * E + i)] = hi;
-                hess_sums_out[2 * ((size_t)i * E + j) + 1] = hess_sums_out[2 * ((size_t)j * E + i) + 1] = lo;
+                put_dd(hess_sums_out + 2 * ((size_t)i * E + j), v);
+                put_dd(hess_sums_out + 2 * ((size_t)j * E + i), v);
             }
     return PLK_OK;
 }

@@ -914,6 +914,61 @@ static inline std::string plk_fused_check_cpp(int N, const PlkProgram &pg, const
 }
 
 /* ------------------------------------------------------------------------------------------------------------ */
+/* what the down / up drivers share: dense storage indices of the stored vectors, and the site-chunk plan         */
+/* ------------------------------------------------------------------------------------------------------------ */
+
+/*
+ * Where the down / up passes keep what they store per site: a leaf edge has a tip slot and no vector, an internal edge a
+ * dense index into the edge vectors, a node with children a dense index into the node vectors, and a rescaled such node a
+ * dense index into the stored factors.  Everything else is -1.  All indices grow with the edge / node number.
+ */
+struct PlkStorageMaps {
+    std::vector<int> edge_tip;         /* E: tip slot of a leaf edge */
+    std::vector<int> edge_int;         /* E: storage index of an internal edge */
+    std::vector<int> node_int;         /* N: storage index of a node with children */
+    std::vector<int> node_scale;       /* N: rescaling slot of a stored node the program rescales */
+    std::vector<int> tip_edges;        /* ntips + 1: CSR edge per tip slot, then -1 for the pseudo slot (raw definitions) */
+    int ntips = 0, nie = 0, nin = 0, nsc = 0;
+};
+
+/* (run_updown4 used to give a tree without any node with children a root vector.  Every driver is reached with E > 0 only,
+ * where the root has a child, so that rule never fired and is not kept.) */
+static inline void plk_storage_maps_build(int N, int E, const int *indptr, const std::vector<int> &tip_edge, const char *scale_node,
+                                          PlkStorageMaps &m)
+{
+    m.ntips = (int)tip_edge.size();
+    m.edge_tip.assign(E, -1); m.edge_int.assign(E, -1); m.node_int.assign(N, -1); m.node_scale.assign(N, -1);
+    m.nie = m.nin = m.nsc = 0;
+    for (int t = 0; t < m.ntips; t++) m.edge_tip[tip_edge[t]] = t;
+    for (int e = 0; e < E; e++) if (m.edge_tip[e] < 0) m.edge_int[e] = m.nie++;
+    for (int a = 0; a < N; a++) if (indptr[a + 1] > indptr[a]) m.node_int[a] = m.nin++;
+    for (int a = 0; a < N; a++) if (m.node_int[a] >= 0 && scale_node[a]) m.node_scale[a] = m.nsc++;
+    m.tip_edges = tip_edge;
+    m.tip_edges.push_back(-1);
+}
+
+/*
+ * Sites per pass of a down / up driver whose workspace takes bytes_per_site: what fits the free device memory (all but
+ * 4 GiB of it, or half of it at 6 GiB and below) plus the workspace the engine already holds, capped by S and by
+ * opt_site_chunk (> 0).  A chunk shorter than S is a whole number of tiles, at least one.  whole_tiles (the matrix-core
+ * kernels, whose grids cover whole tiles): S counts rounded up to the tile and the chunk is always rounded down to whole
+ * tiles.  Returns 0 when not even one site (whole_tiles: one tile) fits.
+ */
+static inline long plk_site_chunk(long S, size_t free_bytes, size_t retained_work_bytes, size_t bytes_per_site, long opt_site_chunk,
+                                  int tile, bool whole_tiles)
+{
+    size_t budget = free_bytes > (size_t)(6ull << 30) ? free_bytes - (size_t)(4ull << 30) : free_bytes / 2;
+    budget += retained_work_bytes;
+    const size_t all = whole_tiles ? (size_t)((S + tile - 1) / tile * tile) : (size_t)S;
+    long chunk = (long)std::min<size_t>(all, budget / bytes_per_site);
+    if (opt_site_chunk > 0) chunk = std::min<long>(chunk, opt_site_chunk);
+    if (whole_tiles) return chunk / tile * tile;
+    if (chunk < 1) return 0;
+    if (chunk < S) chunk = std::max<long>(tile, chunk / tile * tile);
+    return chunk;
+}
+
+/* ------------------------------------------------------------------------------------------------------------ */
 /* down passes that traverse the program (k_down_fused4, k_ll_mfma, k_down_fused_mfma): int4 ops with an          */
 /* observation chain (z = tip slot of the next observation op, w = its staged row; the last one wraps with bit 30) */
 /* ------------------------------------------------------------------------------------------------------------ */

@@ -139,11 +139,23 @@ def one_category(md, r):
     return md1
 
 
-def _site_ll(oracle, md, cache=None, key=None):
+def _model(oracle, md, cache=None, key=None):
+    """(m, w) of a document; prepared once per cache and key (the binary128 exponentials of a large k take seconds)"""
+    if cache is not None and ("model", key) in cache:
+        return cache["model", key]
+    m = oracle.parse_model(md)
+    mw = (m, oracle.prepare(m))
+    if cache is not None:
+        cache["model", key] = mw
+    return mw
+
+
+def _site_ll(oracle, md, cache=None, key=None, keep_model=True):
+    """keep_model = False: the prepared model is not kept (the difference steps of zero_rate_term, which nothing reuses)"""
     if cache is not None and key in cache:
         return cache[key]
-    m = oracle.parse_model(md)
-    ll, _ = oracle.site_ll(m, oracle.prepare(m), B=m.B, precise=2)
+    m, w = _model(oracle, md, cache if keep_model else None, key)
+    ll, _ = oracle.site_ll(m, w, B=m.B, precise=2)
     ll = np.asarray(ll, dtype=LD)
     if cache is not None:
         cache[key] = ll
@@ -161,7 +173,7 @@ def zero_rate_term(oracle, md, ll_s, wt_p, h0=FD_H, cache=None):
     divided by 4 while the disagreement shrinks, and the step of the smallest disagreement is taken."""
     def g(r):
         with np.errstate(over="ignore"):
-            return np.sum(wt_p * np.where(wt_p != 0, np.exp(_site_ll(oracle, one_category(md, r), cache, ("ll", float(r))) - ll_s), 0))
+            return np.sum(wt_p * np.where(wt_p != 0, np.exp(_site_ll(oracle, one_category(md, r), cache, ("ll", float(r)), keep_model=False) - ll_s), 0))
     g0 = g(0.0)
     best = None
     h = h0
@@ -177,14 +189,13 @@ def zero_rate_term(oracle, md, ll_s, wt_p, h0=FD_H, cache=None):
 
 def expectations(oracle, md, weights, cache=None):
     """(prior_out [C], rate_out [C], rate_tol [C]) of plk_mixture_sens from the oracle alone, in long double.
-    cache: a dict the caller keeps for ONE document; the per-site oracle values, which do not depend on the weights, are
-    kept there, so that a second weight vector costs no oracle call.
+    cache: a dict the caller keeps for ONE document; the prepared models and the per-site oracle values, which do not
+    depend on the weights, are kept there, so that a second weight vector costs no oracle call.
     rate_tol[c] is the accuracy of the expected rate_out[c] relative to max_c |rate_out|: 0 where the value comes from
     binary128 derivatives, and for a category of rate 0 the larger of 1e-9 and ten times the disagreement of the two
     difference steps (asserted below 1e-8, so that a test cannot hide behind it)."""
     assert not isinstance(md.get("rate_divisor"), str), "the one-category models need a numeric divisor"
-    m = oracle.parse_model(md)
-    w = oracle.prepare(m)
+    m, w = _model(oracle, md, cache, "mixture")
     C = int(w["C"])
     wt = np.asarray(weights, dtype=LD)
     ll_s = _site_ll(oracle, md, cache, "mixture")
@@ -201,8 +212,8 @@ def expectations(oracle, md, weights, cache=None):
         prior_out[c] = np.sum(wt * ratio)
         if r > 0:
             if cache is None or ("deriv", r) not in cache:
-                m1 = oracle.parse_model(md1)
-                d = np.asarray(oracle.site_deriv(m1, oracle.prepare(m1), m1.B, precise=2), dtype=LD)
+                m1, w1 = _model(oracle, md1, cache, ("ll", r))
+                d = np.asarray(oracle.site_deriv(m1, w1, m1.B, precise=2), dtype=LD)
                 if cache is not None:
                     cache["deriv", r] = d
             else:

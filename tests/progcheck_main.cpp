@@ -8,6 +8,7 @@
  * For every tree: program build + invariants, fused formats for every kernel variant the engine could launch
  * (assembly interpreter with 4-bit and 8-bit codes, C++ interpreter with one and two sites per lane), the chained
  * programs of the three down passes; and negative controls (corrupted words must be refused).
+ * Before the trees: a table of site-chunk plans (plk_site_chunk) against the rules the drivers used to spell out inline.
  * Prints "ok <trees> <ops>" and exits 0, or the first failure and exits 1.
  */
 #include <cstdio>
@@ -41,6 +42,36 @@ static bool make_tree(int N, const std::vector<int> &ea, const std::vector<int> 
 
 static long g_ops = 0;
 
+/* Invariants of PlkStorageMaps: edge_tip / edge_int partition the edges; node_int >= 0 exactly for the nodes with children;
+ * node_scale >= 0 only on a stored node the program rescales; every index is dense and increasing; the counts and the
+ * sentinel-ended tip edge list agree with the maps. */
+static std::string check_storage_maps(int N, int E, const int *ip, const PlkProgram &pg, const PlkStorageMaps &m)
+{
+    if ((int)m.edge_tip.size() != E || (int)m.edge_int.size() != E || (int)m.node_int.size() != N || (int)m.node_scale.size() != N) return "storage maps: sizes";
+    if (m.ntips != (int)pg.tip_edge.size() || (int)m.tip_edges.size() != m.ntips + 1 || m.tip_edges.back() != -1) return "storage maps: tip edge list";
+    std::vector<int> slot_seen(m.ntips, 0);
+    int nie = 0, nin = 0, nsc = 0, ntip = 0;
+    for (int e = 0; e < E; e++) {
+        if ((m.edge_tip[e] >= 0) == (m.edge_int[e] >= 0)) return "storage maps: edge " + std::to_string(e) + " is not exactly one of tip / internal";
+        if (m.edge_tip[e] >= 0) {
+            const int s = m.edge_tip[e];
+            if (s >= m.ntips || slot_seen[s]++ || m.tip_edges[s] != e || pg.tip_edge[s] != e) return "storage maps: tip slot of edge " + std::to_string(e);
+            ntip++;
+        } else if (m.edge_int[e] != nie++) return "storage maps: edge_int is not dense and increasing";
+    }
+    if (ntip != m.ntips || nie != m.nie) return "storage maps: edge counts";
+    for (int a = 0; a < N; a++) {
+        const bool stored = ip[a + 1] > ip[a];
+        if ((m.node_int[a] >= 0) != stored || m.node_int[a] < -1) return "storage maps: node_int of node " + std::to_string(a);
+        if (stored && m.node_int[a] != nin++) return "storage maps: node_int is not dense and increasing";
+        const bool scaled = stored && pg.scale_node[a];
+        if ((m.node_scale[a] >= 0) != scaled || m.node_scale[a] < -1) return "storage maps: node_scale of node " + std::to_string(a);
+        if (scaled && m.node_scale[a] != nsc++) return "storage maps: node_scale is not dense and increasing";
+    }
+    if (nin != m.nin || nsc != m.nsc) return "storage maps: node counts";
+    return "";
+}
+
 static std::string check_tree(const Tree &t, const std::vector<char> &has, int nchar)
 {
     const int N = t.N;
@@ -49,14 +80,14 @@ static std::string check_tree(const Tree &t, const std::vector<char> &has, int n
     g_ops += (long)pg.ops.size();
     std::string bad = plk_program_check(N, t.ip.data(), t.ix.data(), t.pre.data(), has.data(), pg);
     if (!bad.empty()) return bad;
-    /* storage indices as run_updown4 / run_updown_mfma compute them */
-    const int E = N - 1, ntips = (int)pg.tip_edge.size();
-    std::vector<int> edge_tip(E, -1), edge_int(E, -1), node_int(N, -1), node_scale(N, -1);
-    for (int k = 0; k < ntips; k++) edge_tip[pg.tip_edge[k]] = k;
-    int nie = 0, nin = 0, nsc = 0;
-    for (int e = 0; e < E; e++) if (edge_tip[e] < 0) edge_int[e] = nie++;
-    for (int a = 0; a < N; a++) if (t.ip[a + 1] > t.ip[a]) node_int[a] = nin++;
-    for (int a = 0; a < N; a++) if (node_int[a] >= 0 && pg.scale_node[a]) node_scale[a] = nsc++;
+    /* storage indices: the function the down / up drivers call, and its invariants; everything below runs on these maps */
+    const int E = N - 1;
+    PlkStorageMaps sm;
+    plk_storage_maps_build(N, E, t.ip.data(), pg.tip_edge, pg.scale_node.data(), sm);
+    bad = check_storage_maps(N, E, t.ip.data(), pg, sm);
+    if (!bad.empty()) return bad;
+    const std::vector<int> &edge_tip = sm.edge_tip, &edge_int = sm.edge_int, &node_int = sm.node_int, &node_scale = sm.node_scale;
+    const int ntips = sm.ntips, nie = sm.nie, nin = sm.nin, nsc = sm.nsc;
     for (int mode = 0; mode <= 4; mode++) {
         PlkChain ch;
         if (mode == 4) {          /* mode 3 without node storage (the vector ll kernel) */
@@ -354,9 +385,85 @@ static std::string check_tree(const Tree &t, const std::vector<char> &has, int n
     return "";
 }
 
+/* The site-chunk rules as the down / up drivers spelled them inline before plk_site_chunk() existed: the reference of the
+ * table below.  Ordinary rule (run_updown4, run_updown_vec, run_updown, second_order_generic, second_order_k4), 0 where
+ * they reported "not enough device memory for one site": */
+static long ref_chunk_ordinary(long S, size_t free_b, size_t work_bytes, size_t per_site, long opt_site_chunk, int BLOCK)
+{
+    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
+    budget += work_bytes;
+    long chunk = (long)std::min<size_t>((size_t)S, budget / per_site);
+    if (opt_site_chunk > 0) chunk = std::min<long>(chunk, opt_site_chunk);
+    if (chunk < 1) return 0;
+    if (chunk < S) chunk = std::max<long>(BLOCK, chunk / BLOCK * BLOCK);
+    return chunk;
+}
+/* ... and the matrix-core rule (run_updown_mfma), 0 where it reported "not enough device memory" */
+static long ref_chunk_mfma(long S, size_t free_b, size_t work_bytes, size_t per_site, long opt_site_chunk, int MF_SITES)
+{
+    size_t budget = free_b > (size_t)(6ull << 30) ? free_b - (size_t)(4ull << 30) : free_b / 2;
+    budget += work_bytes;
+    long chunk = (long)std::min<size_t>((size_t)((S + MF_SITES - 1) / MF_SITES * MF_SITES), budget / per_site);
+    if (opt_site_chunk > 0) chunk = std::min<long>(chunk, opt_site_chunk);
+    chunk = chunk / MF_SITES * MF_SITES;
+    if (chunk < MF_SITES) return 0;
+    return chunk;
+}
+
+static std::string check_chunk_planner()
+{
+    const size_t GiB = (size_t)1 << 30, MiB = (size_t)1 << 20;
+    const int tiles[3] = {64, 128, 256};
+    struct Case { long S_tiles, S_extra; size_t free_b, work_b, per_site; long opt_num, opt_den; const char *what; };
+    /* S = S_tiles * tile + S_extra, opt_site_chunk = tile * opt_num / opt_den */
+    const Case cases[] = {
+        {0, -1, 64 * GiB, 0, 1000, 0, 1, "S below one tile"},                      /* S_extra -1: tile - 1 sites */
+        {4, 0, 64 * GiB, 0, 1000, 0, 1, "S a whole number of tiles"},
+        {4, 1, 64 * GiB, 0, 1000, 0, 1, "S one over"},
+        {4, 1, 64 * GiB, 0, 1000, 2, 1, "forced chunk of two tiles"},
+        {4, 1, 64 * GiB, 0, 1000, 5, 2, "forced chunk of two and a half tiles"},
+        {10, 0, 64 * GiB, 0, 1000, 1, 2, "forced chunk below the tile"},           /* ordinary: one tile; matrix core: does not fit */
+        {0, -1, 64 * GiB, 0, 1000, 1, 2, "forced chunk below the tile, S below the tile"},
+        {10, 0, 2 * 1000 - 2, 0, 1000, 0, 1, "budget just below one site"},
+        {10, 0, 2 * 1000, 0, 1000, 0, 1, "budget of exactly one site"},            /* ordinary: rounded up to one tile */
+        {10, 0, 2 * 1000 - 2, 1, 1000, 0, 1, "the retained workspace makes one site fit"},
+        {10, 0, 0, 0, 1000, 0, 1, "no memory at all"},
+        {1000, 0, 6 * GiB, 0, MiB, 0, 1, "6 GiB free: half of it"},
+        {1000, 0, 6 * GiB + MiB, 0, MiB, 0, 1, "just above 6 GiB free: all but 4 GiB"},
+        {1000, 0, 6 * GiB, GiB, MiB, 0, 1, "retained workspace added after the 6 GiB branch"},
+        {1000, 0, 5 * GiB + MiB, GiB, MiB, 0, 1, "retained workspace does not move the branch"},
+        {1000, 3, 64 * GiB, 0, 16 * MiB, 0, 1, "memory-bound chunk, ragged S"},
+    };
+    for (int ti = 0; ti < 3; ti++)
+        for (const Case &c : cases) {
+            const int tile = tiles[ti];
+            const long S = c.S_tiles * tile + (c.S_extra < 0 ? tile + c.S_extra : c.S_extra), opt = tile * c.opt_num / c.opt_den;
+            for (int mc = 0; mc < 2; mc++) {
+                const long want = mc ? ref_chunk_mfma(S, c.free_b, c.work_b, c.per_site, opt, tile) : ref_chunk_ordinary(S, c.free_b, c.work_b, c.per_site, opt, tile);
+                const long got = plk_site_chunk(S, c.free_b, c.work_b, c.per_site, opt, tile, mc != 0);
+                if (got != want)
+                    return std::string("chunk planner (") + c.what + ", tile " + std::to_string(tile) + (mc ? ", matrix-core rule): " : ", ordinary rule): ") +
+                           std::to_string(got) + ", the inline formula gives " + std::to_string(want);
+            }
+        }
+    /* a few values worked out by hand, so that the reference is pinned too (tile 64, 1 MiB per site, 64000 sites) */
+    struct Lit { size_t free_b, work_b; long opt; bool mc; long want; };
+    const Lit lits[] = {
+        {6 * GiB, 0, 0, false, 3072}, {6 * GiB + MiB, 0, 0, false, 2048}, {6 * GiB, GiB, 0, false, 4096}, {6 * GiB + MiB, 0, 0, true, 2048},
+        {64 * GiB, 0, 32, false, 64}, {64 * GiB, 0, 32, true, 0}, {2 * MiB, 0, 0, false, 64}, {2 * MiB, 0, 0, true, 0}, {2 * MiB - 2, 0, 0, false, 0},
+        {64 * GiB, 0, 0, false, 61440}, {64 * GiB, 0, 100000, true, 61440},
+    };
+    for (const Lit &l : lits) {
+        const long got = plk_site_chunk(64000, l.free_b, l.work_b, MiB, l.opt, 64, l.mc);
+        if (got != l.want) return "chunk planner: literal case gives " + std::to_string(got) + ", expected " + std::to_string(l.want);
+    }
+    return "";
+}
+
 int main(int argc, char **argv)
 {
     long ntrees = 0;
+    { const std::string bad = check_chunk_planner(); if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; } }
     if (argc > 1) {
         FILE *f = fopen(argv[1], "r");
         if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
