@@ -392,10 +392,13 @@ enum {
                                        read from a table), 4 = with rebuilt tables (at least one node whose vector is the
                                        product of two table rows), 8 = two-leaf nodes finished inside their parent's visit
                                        (one rate category); 0 when another kernel family ran */
-    PLK_INFO_DOWN4_KERNEL = 18      /* k = 4 down pass of the last query that ran on the k = 4 up/down kernels (deriv, marginal,
+    PLK_INFO_DOWN4_KERNEL = 18,     /* k = 4 down pass of the last query that ran on the k = 4 up/down kernels (deriv, marginal,
                                        expectations, and the pair-sum and mixture-gradient passes): 4, 8 or 16 = k_down_fused4<D>
                                        with a register stack of that depth, 0 = k_down_store4 (the staged code rows do not fit
                                        the LDS, or the tree needs more than 16 slots) or no such query yet */
+    PLK_INFO_LL_FORM = 19           /* form of the last ll evaluation's k = 4 pair-table kernel: 1 = streamed codes with the tables
+                                       of all categories resident in LDS (k_ll_fused4_v4s; PLK_INFO_LL_VARIANT reports 6),
+                                       0 = a tile kernel or another family */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -416,11 +419,17 @@ enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PE
                                Marginal queries always take the one-edge-at-a-time passes.  ARBPLF_UP_NODES in the
                                environment sets the initial value. */,
        PLK_OPT_PAIR_TABLES = 6 /* k = 4 trees within 4 stack slots and 16 character definitions: two-leaf subtrees as table
-                               look-ups, grid-stride tile loop, one workgroup per CU.  1 (default): the interpreter with
-                               two sites per lane (k_ll_fused4_v4) on 1536-site tiles, or 1024-site tiles when the
+                               look-ups, grid-stride tile loop, one workgroup per CU.  1 (default): the streamed form of 7 where it
+                               fits, else the interpreter with two sites per lane (k_ll_fused4_v4) on 1536-site tiles, or 1024-site tiles when the
                                tables leave less LDS, else one site per lane; 5 / 6: two sites per lane on 1024 / 1536
                                sites; 2 / 3: one site per lane (k_ll_fused4_asm_pt) on 1024 / 512 sites; 0: the round-2
-                               interpreter over 256-site tiles, no pair tables */,
+                               interpreter over 256-site tiles, no pair tables; 7: two sites per lane with the codes
+                               streamed from a per-unit stream in device memory (built when the formats are uploaded:
+                               about one byte per site and leaf or cherry) and the tables of all categories resident in
+                               LDS (k_ll_fused4_v4s) wherever C x table bytes fit the LDS and the stream fits device
+                               memory, otherwise as 1; the default takes that form under the same conditions.  + 8: without the
+                               scalar-cache warm-up; streamed form, + 16: its waves meet before every unit instead of every
+                               category, + 32: never (measurements) */,
        PLK_OPT_VEC_REG_STACK = 7 /* 1 (default): the vector kernels (9 <= k <= 20) keep the three busiest stack slots in
                                registers (2 waves per SIMD); 0: every waiting vector goes through HBM slots (round 2) */,
        PLK_OPT_MFMA_NS2 = 8 /* 1: the matrix-core ll kernel for 33 <= k <= 64 gives a wave two groups of 16 sites (every staged

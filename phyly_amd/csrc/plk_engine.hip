@@ -113,6 +113,10 @@ struct plk_engine {
     bool vec_pt = false;
     int pt_kind = 0, pt_tile_sites = 0;  /* 1: k_ll_fused4_asm_pt, 2: k_ll_fused4_v4; sites per tile of the uploaded formats */
     unsigned v4_tip_base = 0;            /* LDS address of the table image = static LDS of the kernel */
+    PlkFusedV4S fv4s;                    /* streamed codes (k_ll_fused4_v4s): one op stream per category */
+    bool pt_stream = false;              /* the uploaded pt_kind 2 formats are the streamed-code ones */
+    unsigned *d_cstream = nullptr; size_t cstream_cap = 0;   /* the code stream (plk_stream_dword), built by upload_formats */
+    int *d_obs_row = nullptr;            /* staged row per observation of the program */
     int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [2][rows] staged-row nodes; [4][ntab] unit, edge, leaf edges of a pair */
     int num_cus = 256;
     int2 *d_ops = nullptr;
@@ -168,7 +172,7 @@ struct plk_engine {
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
-    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
+    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
 static std::string g_create_error;
@@ -811,6 +815,7 @@ __device__ __forceinline__ double wave64_sum_lane63(double x)
 #include "plk_fused4.h"
 #include "plk_fused4_asm.h"
 #include "plk_fused4_v4.h"
+#include "plk_fused4_v4s.h"
 #include "plk_mfma.h"
 #include "plk_mfma_updown.h"
 #include "plk_vec.h"
@@ -1389,7 +1394,7 @@ extern "C" void plk_destroy(plk_engine *h)
     void *ptrs[] = {h->d_indptr, h->d_indices, h->d_preorder, h->d_Qn, h->d_edge_rates, h->d_cat_rates,
                     h->d_cat_prior, h->d_root_w, h->d_Pdd, h->d_P, h->d_dP, h->d_scratch, h->d_codes,
                     h->d_defs, h->d_B, h->d_w, h->d_ops, h->d_fops, h->d_words, h->d_mat_edge, h->d_edge_slot, h->d_op_edge, h->d_tip_edge, h->d_obs_nodes,
-                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
+                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
                     h->d_cp_fops, h->d_cp_ops, h->d_cp_mat_edge, h->d_cp_tip_edge, h->d_cp_obs_nodes, h->d_cp_op_edge, h->d_cp_expo, h->d_cp_flag,
                     h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial, h->d_mixD};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1467,6 +1472,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_UP4_PATH: *out = h->info_up4_path; return PLK_OK;
     case PLK_INFO_DOWN4_KERNEL: *out = h->info_down4_kernel; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
+    case PLK_INFO_LL_FORM: *out = h->info_ll_form; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && ((h->fmt_pt && h->fmt_kind == 1) || (h->vec_pt && h->fmt_kind == 4)) ? h->fpt.npairs : 0; return PLK_OK;
     case PLK_INFO_STACK_SLOTS: *out = h->slots_needed; return PLK_OK;
@@ -1844,13 +1850,47 @@ static bool fused_asm_fits(const plk_engine *h)
  * (the combined code of a cherry is one byte); as many cherries become tables as the two-workgroups-per-CU LDS budget
  * takes.  Fills fpt; false when even the table-less image does not fit (the 256-site kernels take over). */
 /* PLK_OPT_PAIR_TABLES: which pair-table interpreter, how many sites per tile (candidates in order of preference) */
+/* Streamed codes or a tile kernel?  PLK_OPT_PAIR_TABLES 7 asks for the streamed form wherever it fits, and so does the
+ * default: against the parent's tile kernels it measured faster at every shape tried (profiles/ll_k4_stream_ab.json:
+ * kernel time -6.1 % at BASELINE config 3 with 10M sites, -6.5 % at 2.5M, -2.3 % at 1.25M -- inside that shape's spread, not
+ * slower --, -16 % with one category, -22 % at config 2), so no site count sends the default back to a tile kernel. */
+static bool stream_form_preferred(const plk_engine *h, long mode)
+{
+    (void)h;
+    return mode == 7 || mode == 1;
+}
+
 static bool build_fused_pt(plk_engine *h)
 {
     if (!h->opt_pair_tables || !h->opt_fused_asm || h->opt_fused_ns == 2 || h->slots_needed > 4 || h->nchar > 16) return false;
     if (h->obs_nodes.empty()) return false;
     struct Cand { int kind, tile; };
     std::vector<Cand> cands;
-    switch (h->opt_pair_tables & 7) {
+    h->pt_stream = false;
+    const long mode = h->opt_pair_tables & 7;
+    if ((mode == 1 || mode == 7) && h->S > 0 && stream_form_preferred(h, mode)) {
+        /* streamed codes: every cherry a table, the tables of all categories resident; needs the stream in device memory
+         * (an allocation that fails sends the query to the tile kernels, it does not fail it) */
+        plk_fused_pt_build(h->N, h->indptr.data(), h->indices.data(), h->pg, h->nchar, INT_MAX, h->fpt, true);
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, (const void *)k_ll_fused4_v4s<768>) == hipSuccess) {
+            const size_t lds = plk_fused_v4s_lds_bytes(h->fpt, h->nchar, h->C);
+            const size_t nunits = (size_t)((h->S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT);
+            size_t nobs = 0;
+            for (const PlkFusedPT::VOp &o : h->fpt.vops) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) nobs++;
+            if (nobs > 0 && lds + fa.sharedSizeBytes <= plk_pt_lds_limit(1024) && (fa.sharedSizeBytes + lds) / 32 < 65536 && h->fpt.units < 2048 &&
+                h->fpt.row_node.size() < 65536) {
+                if (dev_reserve(h, &h->d_cstream, &h->cstream_cap, nunits * (size_t)plk_stream_chunks((int)nobs) * PLK_V4S_UNIT) == PLK_OK) {
+                    h->v4_tip_base = (unsigned)fa.sharedSizeBytes;
+                    h->pt_kind = 2; h->pt_tile_sites = 1536; h->pt_stream = true;
+                    return true;
+                }
+                h->err.clear();
+                (void)hipGetLastError();
+            }
+        } else (void)hipGetLastError();
+    }
+    switch (mode) {
     case 2: cands = {{1, 1024}}; break;
     case 3: cands = {{1, 512}}; break;
     case 5: cands = {{2, 1024}}; break;
@@ -1907,7 +1947,12 @@ static int upload_formats(plk_engine *h, long kind)
          * are built from the unrounded P after it (k_build_tables_pt) */
         const PlkFusedPT &f = h->fpt;
         const int nrows = (int)f.row_node.size(), ntab = (int)f.tab_unit.size();
-        if (h->pt_kind == 2) {
+        if (h->pt_kind == 2 && h->pt_stream) {
+            /* streamed codes: op words per category, then the stream itself from the resident code rows */
+            plk_fused_v4s_words(f, h->nchar, h->C, h->v4_tip_base, h->fv4s);
+            if ((rc = dev_upload(h, &h->d_words_pt, h->fv4s.words.data(), h->fv4s.words.size()))) return rc;
+            if ((rc = dev_upload(h, &h->d_obs_row, h->fv4s.obs_row.data(), h->fv4s.obs_row.size()))) return rc;
+        } else if (h->pt_kind == 2) {
             /* the table image starts where the kernel's static LDS ends */
             hipFuncAttributes fa;
             const void *fn = h->pt_tile_sites == 1536 ? (const void *)k_ll_fused4_v4<768> : (const void *)k_ll_fused4_v4<512>;
@@ -1919,6 +1964,14 @@ static int upload_formats(plk_engine *h, long kind)
         std::vector<int> rn(f.row_node);
         rn.insert(rn.end(), f.row_node2.begin(), f.row_node2.end());
         if ((rc = dev_upload(h, &h->d_row_nodes, rn.data(), rn.size()))) return rc;
+        if (h->pt_stream) {
+            const long nunits = (h->S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
+            const size_t total = (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT;
+            if (total > h->cstream_cap || (total + 255) / 256 > 0x7fffffffu) { h->err = "internal: code stream size"; return PLK_E_ARG; }
+            hipLaunchKernelGGL(k_build_code_stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_codes, h->Spad, nunits,
+                               h->d_obs_row, h->fv4s.nobs, h->d_row_nodes, nrows, h->nchar, h->fv4s.chunks, h->d_cstream);
+            HIPCHK(h, hipGetLastError());
+        }
         std::vector<int> tabs(f.tab_unit);
         tabs.insert(tabs.end(), f.tab_edge.begin(), f.tab_edge.end());
         tabs.insert(tabs.end(), f.tab_eb.begin(), f.tab_eb.end());
@@ -2139,7 +2192,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     h->evk_next = (evi + 1) & 63;
     if ((rc = evk_resolve(h, evi))) return rc;           /* only waits when 64 evaluations are queued */
     HIPCHK(h, hipEventRecord(h->evk[evi][0], h->stream));
-    h->info_ll_variant = 0;
+    h->info_ll_variant = 0; h->info_ll_form = 0;
     if (fused) {
         const int NS = fused_sites_per_lane(h);
         grid = (unsigned)((S + PLK_TILE * NS - 1) / (PLK_TILE * NS));
@@ -2160,10 +2213,16 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
             const PlkFusedPT &f = h->fpt;
             const int tile = h->pt_tile_sites;
             const int ntiles = (int)((S + tile - 1) / tile);
+            int ntiles_out = ntiles;
             if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)ntiles + PLK_PARTIAL_OFF))) return rc; }
-            const size_t lds_pt = plk_fused_pt_lds_bytes(f, h->nchar, tile);
-            std::string bad = plk_fused_check_pt(h->N, h->indptr.data(), h->indices.data(), h->pg, f, h->nchar, tile, lds_pt, h->pt_kind == 2);
-            if (bad.empty() && h->pt_kind == 2) bad = plk_fused_check_v4(f, h->fv4, h->nchar, tile, h->v4_tip_base, lds_pt);
+            const bool strm = h->pt_kind == 2 && h->pt_stream;
+            const size_t lds_pt = strm ? plk_fused_v4s_lds_bytes(f, h->nchar, h->C) : plk_fused_pt_lds_bytes(f, h->nchar, tile);
+            /* the 32-bit program is replayed whatever the form (streamed: no code rows in LDS; its fields are the chain the
+             * streamed words are checked against) */
+            std::string bad = strm ? plk_fused_check_pt(h->N, h->indptr.data(), h->indices.data(), h->pg, f, h->nchar, 1, 0, true, false)
+                                   : plk_fused_check_pt(h->N, h->indptr.data(), h->indices.data(), h->pg, f, h->nchar, tile, lds_pt, h->pt_kind == 2);
+            if (bad.empty() && strm) bad = plk_fused_check_v4s(f, h->fv4s, h->nchar, h->C, h->v4_tip_base, lds_pt);
+            else if (bad.empty() && h->pt_kind == 2) bad = plk_fused_check_v4(f, h->fv4, h->nchar, tile, h->v4_tip_base, lds_pt);
             if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
             FusedPTArgs pa;
             pa.f = a;
@@ -2173,7 +2232,22 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
             pa.first_unit = f.first_unit; pa.first_row = f.first_row; pa.second_row = f.second_row; pa.ntiles = ntiles;
             pa.warm = (h->opt_pair_tables & 8) ? 0 : 1;      /* + 8: without the scalar-cache warm-up (measurements) */
             h->info_ll_variant = 5;
-            if (h->pt_kind == 2) {
+            if (strm) {
+                /* streamed codes: 768 lanes per CU, a wave per 128-site unit, one partial sum per wave */
+                const long nunits = (S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
+                grid = (unsigned)std::min<long>((nunits + 11) / 12, h->num_cus);
+                ntiles_out = (int)grid * 12;
+                if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)ntiles_out + PLK_PARTIAL_OFF))) return rc; }
+                FusedV4SArgs sa;
+                sa.pt = pa; sa.pt.f.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
+                sa.pt.nwords = (int)h->fv4s.stride;
+                sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
+                /* the waves of a workgroup meet before every category (+ 16: before every unit only, + 32: never; measurements,
+                 * DESIGN.md section 4) */
+                sa.sync = (h->opt_pair_tables & 32) ? 0 : (h->opt_pair_tables & 16) ? 1 : 2;
+                hipLaunchKernelGGL(k_ll_fused4_v4s<768>, dim3(grid), dim3(768), lds_pt, h->stream, sa);
+                h->info_ll_variant = 6; h->info_ll_form = 1;
+            } else if (h->pt_kind == 2) {
                 /* two sites per lane: one workgroup of tile / 2 lanes per CU */
                 FusedV4Args va;
                 va.pt = pa; va.first_y = h->fv4.first_y; va.first_z = h->fv4.first_z; va.second_z = h->fv4.second_z;
@@ -2188,7 +2262,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
                 grid = (unsigned)std::min(ntiles, 2 * h->num_cus);
                 hipLaunchKernelGGL(k_ll_fused4_asm_pt<512>, dim3(grid), dim3(512), lds_pt, h->stream, pa);
             }
-            grid = (unsigned)ntiles;                      /* one partial sum per tile */
+            grid = (unsigned)ntiles_out;                  /* one partial sum per tile (per wave of the streamed form) */
         } else if (use_asm) {
             FusedAsmArgs aa;
             aa.f = a; aa.words = h->d_words;

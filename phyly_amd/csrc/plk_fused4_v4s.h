@@ -1,0 +1,153 @@
+/*
+ * plk_fused4_v4s.h -- k_ll_fused4_v4s: the two-sites-per-lane pair-table interpreter (plk_fused4_v4.h) with the codes
+ * STREAMED to registers and the tables of all categories resident in LDS.
+ * Included by plk_engine.hip after plk_fused4_v4.h.
+ *
+ * k_ll_fused4_v4 keeps a tile's staged code rows in LDS (67 B x 1536 sites at BASELINE config 3), which leaves room for one
+ * category's tables: every tile and category restages 32 KB of tables between two workgroup barriers, every tile
+ * recomputes code(b) * nchar + code(c) of its pair rows, and a CU runs one workgroup whose waves idle at the barriers.
+ * Here nothing but the tables is in LDS: they are staged once per launch (C x units x nchar x 32 bytes) and every wave
+ * walks its own 128-site units.  The waves of a workgroup still meet once per unit and category, before the
+ * scalar-cache warm-up: left to drift, they read the matrix streams and op words of different categories at the same
+ * time (4 x 13 KB at config 3 through a 16 KB scalar cache) and the kernel runs 10 % longer (measured, DESIGN.md
+ * section 4).  Nothing is staged between those barriers, so they cost the waves' skew only.  The codes come from a stream in
+ * global memory that holds, per unit, the bytes of the observation ops in program order, four to a dword, one wave-wide
+ * 8-byte load per chunk of four observations (layout: plk_program.h, plk_stream_dword); it is built by
+ * k_build_code_stream when the formats are uploaded, not per evaluation -- it depends on the patterns and the tree only.
+ * The interpreter (tools/gen_fused4_v4.py, streamed mode -> plk_fused4_v4s_asm.h) extracts the next observation's code
+ * from the current dword (v_bfe_u32) and keeps two chunks in flight; per site the arithmetic is k_ll_fused4_v4's, instruction
+ * for instruction, so site log likelihoods are bit-identical.  The sum differs in the order of its double-double terms
+ * only: a wave keeps one running sum over its units (static assignment: reproducible) and writes one partial.
+ */
+#ifndef PLK_FUSED4_V4S_H
+#define PLK_FUSED4_V4S_H
+
+#include "plk_fused4_v4s_asm.h"
+
+struct FusedV4SArgs {
+    FusedPTArgs pt;             /* words = C op streams of stride dwords, nwords = stride; row_nodes / first_row / ntiles unused */
+    const unsigned *stream;     /* [units of 128 sites][chunks][64 lanes][site A dword, site B dword] */
+    int chunks;                 /* chunks of a unit, the spare ones included */
+    unsigned first_y;           /* LDS offset / 32 of the first observation's table in category 0 */
+    int sync;                   /* workgroup barrier: 1 before every unit, 2 before every category, 0 none */
+};
+
+/* stream[unit][chunk][lane][half]: one thread per dword; sites past S carry code 0 (the code rows are zero padded) */
+__global__ __launch_bounds__(256) void k_build_code_stream(const uint8_t *__restrict__ codes, long Spad, long nunits,
+                                                           const int *__restrict__ obs_row, int nobs, const int *__restrict__ row_nodes,
+                                                           int nrows, int nchar, int chunks, unsigned *__restrict__ out)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)nunits * chunks * PLK_V4S_UNIT;
+    if (idx >= total) return;
+    const int half = (int)(idx & 1), lane = (int)((idx >> 1) & 63);
+    const size_t uc = idx >> 7, unit = uc / (size_t)chunks;
+    const int chunk = (int)(uc - unit * (size_t)chunks);
+    const size_t site = unit * PLK_V4S_UNIT + (size_t)half * 64 + lane;
+    out[plk_stream_dword(unit, chunk, lane, half, chunks)] =
+        site < (size_t)Spad ? plk_stream_site_dword(codes, (size_t)Spad, site, obs_row, nobs, row_nodes, nrows, nchar, chunk) : 0u;
+}
+
+__device__ __forceinline__ void fused_run_program_v4s(double &lha, double &lhb, int &ea, int &eb, const void *ops, const void *mstream,
+                                                       const void *strm, unsigned voff, unsigned y0,
+                                                       double w0, double w1, double w2, double w3)
+{
+    int al, ah, bl, bh;
+#ifdef PLK_EXP_EMPTY
+    al = bl = 0; ah = bh = 0x3ff00000; ea = eb = 0;
+#else
+    asm volatile(PLK_V4S_PROGRAM
+                 : [al] "=v"(al), [ah] "=v"(ah), [bl] "=v"(bl), [bh] "=v"(bh), [ea] "=v"(ea), [eb] "=v"(eb)
+                 : [voff] "v"(voff), [ops] "s"(ops), [mstream] "s"(mstream), [strm] "s"(strm), [y0] "s"(y0),
+                   [w0] "s"(w0), [w1] "s"(w1), [w2] "s"(w2), [w3] "s"(w3)
+                 : PLK_V4S_CLOBBERS);
+#endif
+    lha = __hiloint2double(ah, al);
+    lhb = __hiloint2double(bh, bl);
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
+{
+    constexpr int NW = THREADS / 64;
+    const FusedPTArgs &aa = va.pt;
+    const FusedArgs &a = aa.f;
+    extern __shared__ double lds_dyn[];
+    const int tip_doubles = a.ntips * a.nchar * 4;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const PLK_AS4 double *prior = as_uniform(a.cat_prior);
+    const PLK_AS4 double *rootw = as_uniform(a.root_w);
+    const bool plain = a.root_mode == PLK_ROOT_NONE || a.root_mode == PLK_ROOT_UNIFORM;
+    const double wu = a.root_mode == PLK_ROOT_NONE ? 1.0 : 0.25;
+    const double rw0 = plain ? wu : rootw[0], rw1 = plain ? wu : rootw[1], rw2 = plain ? wu : rootw[2], rw3 = plain ? wu : rootw[3];
+    /* the tables of all categories, once per launch; the only barrier of the kernel */
+    {
+        const double2 *src = reinterpret_cast<const double2 *>(a.tip);
+        double2 *dst = reinterpret_cast<double2 *>(lds_dyn);
+        const int n2 = a.C * (tip_doubles / 2);
+        for (int i0 = tid; i0 < n2; i0 += 4 * THREADS) {
+            double2 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) v[u] = i0 + u * THREADS < n2 ? src[i0 + u * THREADS] : double2{0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < 4; u++) if (i0 + u * THREADS < n2) dst[i0 + u * THREADS] = v[u];
+        }
+    }
+    __syncthreads();
+    const long nunits = (a.S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
+    const unsigned cat32 = (unsigned)(a.ntips * a.nchar);
+    dd acc = dd_make(0.0, 0.0);
+    /* every wave makes the same number of passes (va.sync: the waves of the workgroup meet before every unit / category, so
+     * that they read the same category's matrices and op words through the scalar cache at the same time) */
+    const long stride = (long)gridDim.x * NW, passes = (nunits + stride - 1) / stride;
+    for (long pass = 0; pass < passes; pass++) {
+        const long u = pass * stride + (long)blockIdx.x * NW + wave;
+        const bool active = u < nunits;
+        const unsigned *strm = va.stream + (size_t)(active ? u : 0) * (size_t)va.chunks * PLK_V4S_UNIT;
+        double sum[2] = {0.0, 0.0};
+        int Eexp[2] = {0, 0};
+        bool have[2] = {false, false};
+        if (va.sync & 1) __syncthreads();
+        for (int c = 0; c < a.C; c++) {
+            const double *ps = a.PS + (size_t)c * (a.nmat + 1) * 16;
+            const unsigned *ops = aa.words + (size_t)c * aa.nwords;
+            if (va.sync & 2) __syncthreads();
+            if (!active) continue;
+            if (aa.warm) {
+                /* scalar-cache warm-up of the category's matrix stream and op words: the waves of a CU start a unit's category
+                 * loosely in step, each touches its share of the lines (no barrier: best effort) */
+                fused_touch_lines(ps, (unsigned)(a.nmat + 1) * 128u, (unsigned)wave * 64u, NW * 64u);
+                fused_touch_lines(ops, (unsigned)aa.nwords * 4u, (unsigned)wave * 64u, NW * 64u);
+            }
+            double lhs[2];
+            int esc[2];
+            fused_run_program_v4s(lhs[0], lhs[1], esc[0], esc[1], ops, ps, strm, (unsigned)lane * 8u, va.first_y + (unsigned)c * cat32,
+                                  rw0, rw1, rw2, rw3);
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const double lh = lhs[j];
+                const double term = prior[c] * lh;
+                if (term != 0.0) {
+                    if (!have[j]) { sum[j] = term; Eexp[j] = esc[j]; have[j] = true; }
+                    else if (esc[j] > Eexp[j]) { sum[j] = ldexp(sum[j], Eexp[j] - esc[j]) + term; Eexp[j] = esc[j]; }
+                    else sum[j] += ldexp(term, esc[j] - Eexp[j]);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const long s = u * PLK_V4S_UNIT + j * 64 + lane;
+            const double ll = have[j] ? log(sum[j]) + (double)Eexp[j] * 0.6931471805599453094 : -INFINITY;
+            if (active && s < a.S) {
+                if (a.site_ll) a.site_ll[s] = ll;
+                acc = dd_add(acc, dd_weighted(a.w, s, ll));
+            }
+        }
+    }
+    if (a.partial) {
+        const dd r = dd_wave_sum(acc);
+        if (lane == 0) a.partial[(size_t)blockIdx.x * NW + wave] = r;
+    }
+}
+
+#endif

@@ -570,16 +570,17 @@ static inline size_t plk_fused_pt_lds_bytes(const PlkFusedPT &fu, int nchar, int
  * next leaf op -- or, for a pair table, stand for exactly TIP_SET(b), TIP_MUL(c), MATVEC(edge above) of one cherry.
  */
 static inline std::string plk_fused_check_pt(int N, const int *ip, const int *ix, const PlkProgram &pg, const PlkFusedPT &fu, int nchar,
-                                             int tile, size_t lds_bytes_launched, bool fused_set_words = false)
+                                             int tile, size_t lds_bytes_launched, bool fused_set_words = false, bool rows_in_lds = true)
 {
+    if (!rows_in_lds) tile = 1;            /* streamed codes (k_ll_fused4_v4s): rows are indices only, the LDS holds C table images */
     const int nops = (int)pg.ops.size(), nrows = (int)fu.row_node.size(), nmat = (int)fu.mat_edge.size(), ntab = (int)fu.tab_unit.size();
     if (nchar < 1 || nchar > 16) return "pt program: pair tables need nchar <= 16";
     if (pg.slots_needed > 4) return "pt program: the tree needs a deeper register stack";
     if (fu.words.size() % 8 != 0 || fu.words.size() < 16) return "pt program: word buffer";
     if ((int)fu.row_node2.size() != nrows || (int)fu.tab_edge.size() != ntab || (int)fu.tab_eb.size() != ntab || (int)fu.tab_ec.size() != ntab) return "pt program: table sizes";
     const size_t tip_bytes = (size_t)fu.units * nchar * 32, code_bytes = (size_t)nrows * tile;
-    if (tip_bytes + code_bytes > lds_bytes_launched) return "pt program: LDS image larger than the launch's dynamic LDS";
-    if (!plk_pt_tile_ok(tile) || lds_bytes_launched > plk_pt_lds_limit(tile)) return "pt program: dynamic LDS above the limit";
+    if (rows_in_lds && tip_bytes + code_bytes > lds_bytes_launched) return "pt program: LDS image larger than the launch's dynamic LDS";
+    if (rows_in_lds && (!plk_pt_tile_ok(tile) || lds_bytes_launched > plk_pt_lds_limit(tile))) return "pt program: dynamic LDS above the limit";
     if (nrows < 1 || fu.units < 1 || fu.units >= 2048 || nrows >= 65536) return "pt program: field widths";
     for (int r = 0; r < nrows; r++)
         if (fu.row_node[r] < 0 || fu.row_node[r] >= N || fu.row_node2[r] < -1 || fu.row_node2[r] >= N) return "pt program: staged row names a node out of range";
@@ -771,6 +772,201 @@ static inline std::string plk_fused_check_v4(const PlkFusedPT &fu, const PlkFuse
         }
     if (end_block < 0) return "v4 program: no END";
     if ((size_t)end_block + 2 >= nblocks) return "v4 program: fewer than two spare blocks after the END";
+    return "";
+}
+
+/*
+ * Streamed codes: k_ll_fused4_v4s (plk_fused4_v4s.h) keeps the tables of ALL categories in LDS and no code rows; the codes
+ * of the observation ops reach the interpreter through registers, from a stream in global memory that is built when the
+ * formats are uploaded (k_build_code_stream).  A wave walks 128-site UNITS (lane l carries sites 128 u + l and
+ * 128 u + 64 + l).  Observation n of the program (in program order; its staged row is obs_row[n], a pair row's byte is
+ * code(b) * nchar + code(c)) is byte n % 4 of the site's dword in chunk n / 4; a chunk is one wave-wide 8-byte load,
+ *   dword index = ((unit * chunks + chunk) * 64 + lane) * 2 + half,
+ * and a unit has ceil(nobs / 4) chunks and PLK_V4S_AHEAD spare ones, which the interpreter's prefetch reads past the end.
+ * Op words as for k_ll_fused4_v4, one stream per category (stride dwords apart); an observation op's hi dword is
+ *   (LDS offset / 32 of the NEXT observation's table in that category's image) << 16 | bit offset of the NEXT
+ *   observation's code in its dword (the last observation names itself: its look-up is repeated and dropped),
+ * and an ADVANCE_k op (handler PLK_V4S_ADVANCE + k, k alternating from 0) stands before the observation op that
+ * extracts byte 0 of a new chunk: it waits for the older of the two chunks in flight, makes it the current dword and
+ * requests the chunk after next.
+ */
+#define PLK_V4S_ADVANCE 34
+#define PLK_V4S_CHUNK_BYTES 512
+#define PLK_V4S_UNIT 128               /* sites per unit */
+#define PLK_V4S_AHEAD 2                /* chunks in flight next to the current one = spare chunks of a unit */
+#ifdef __HIPCC__
+#define PLK_HD __host__ __device__
+#else
+#define PLK_HD
+#endif
+
+PLK_HD static inline int plk_stream_chunks(int nobs) { return (nobs + 3) / 4 + PLK_V4S_AHEAD; }
+PLK_HD static inline size_t plk_stream_dword(size_t unit, int chunk, int lane, int half, int chunks)
+{
+    return ((unit * (size_t)chunks + (size_t)chunk) * 64 + (size_t)lane) * 2 + (size_t)half;
+}
+/* byte offset of (unit, chunk, lane, site half, byte) in the stream */
+PLK_HD static inline size_t plk_stream_byte(size_t unit, int chunk, int lane, int half, int byte, int chunks)
+{
+    return plk_stream_dword(unit, chunk, lane, half, chunks) * 4 + (size_t)byte;
+}
+/* the dword of chunk `chunk` for one site: the bytes of observations 4 chunk .. 4 chunk + 3, 0 past the last;
+ * row_nodes = [2][nrows] as uploaded (node | second node of a pair row or -1), codes = [N][Spad] */
+PLK_HD static inline unsigned plk_stream_site_dword(const uint8_t *codes, size_t Spad, size_t site, const int *obs_row, int nobs,
+                                                    const int *row_nodes, int nrows, int nchar, int chunk)
+{
+    unsigned d = 0;
+    for (int b = 0; b < 4; b++) {
+        const int n = 4 * chunk + b;
+        if (n >= nobs) break;
+        const int row = obs_row[n], nb = row_nodes[row], nc = row_nodes[nrows + row];
+        unsigned code = codes[(size_t)nb * Spad + site];
+        if (nc >= 0) code = code * (unsigned)nchar + codes[(size_t)nc * Spad + site];
+        d |= (code & 0xffu) << (8 * b);
+    }
+    return d;
+}
+
+struct PlkFusedV4S {
+    std::vector<unsigned> words;       /* C streams of stride dwords: 2 dwords per op, blocks of 7 ops + 1 REFILL op, two spare blocks */
+    size_t stride = 0;
+    std::vector<int> obs_row;          /* staged row of observation n, program order */
+    std::vector<unsigned> first_y;     /* per category: LDS offset / 32 of the first observation's table */
+    int nobs = 0, chunks = 0, C = 0;
+};
+
+static inline size_t plk_fused_v4s_lds_bytes(const PlkFusedPT &fu, int nchar, int C) { return (size_t)C * fu.units * nchar * 32; }
+
+static inline void plk_fused_v4s_words(const PlkFusedPT &fu, int nchar, int C, unsigned tip_base, PlkFusedV4S &vs)
+{
+    std::vector<unsigned> ou;
+    vs.obs_row.clear();
+    for (const PlkFusedPT::VOp &o : fu.vops) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) { ou.push_back((unsigned)o.unit); vs.obs_row.push_back(o.row); }
+    const int nobs = (int)ou.size();
+    vs.nobs = nobs; vs.chunks = plk_stream_chunks(nobs); vs.C = C;
+    /* ops of one category with table fields relative to the category's image: {handler, unit * nchar << 16 | bit offset} */
+    struct Op { unsigned h, hi; bool obs; };
+    std::vector<Op> ops;
+    int oi = 0;
+    for (size_t src = 0; src < fu.words.size(); src++) {
+        const unsigned w = fu.words[src], hidx = w & 31;
+        if (hidx == OP_END) break;
+        if (!plk_word_is_obs(hidx) || oi >= nobs) { ops.push_back(Op{hidx, 0u, false}); continue; }
+        const int next = oi + 1 < nobs ? oi + 1 : oi;
+        if (next != oi && next % 4 == 0) ops.push_back(Op{(unsigned)PLK_V4S_ADVANCE + (unsigned)((next / 4 - 1) & 1), 0u, false});
+        ops.push_back(Op{hidx, ((ou[next] * (unsigned)nchar) << 16) | (unsigned)(8 * (next % 4)), true});
+        oi++;
+    }
+    ops.push_back(Op{(unsigned)OP_END, 0u, false});
+    const size_t nblocks = (ops.size() + 6) / 7 + 2;
+    vs.stride = nblocks * 16;
+    vs.words.assign((size_t)C * vs.stride, 0u);
+    vs.first_y.assign(C, 0u);
+    const unsigned tb32 = tip_base / 32, cat32 = (unsigned)fu.units * (unsigned)nchar;
+    for (int c = 0; c < C; c++) {
+        const unsigned base = tb32 + (unsigned)c * cat32;
+        unsigned *o = &vs.words[(size_t)c * vs.stride];
+        size_t src = 0;
+        for (size_t b = 0; b < nblocks; b++)
+            for (int j = 0; j < 8; j++, o += 2) {
+                if (j == 7) { o[0] = (unsigned)((b & 1) ? PLK_V4_REFILL_B : PLK_V4_REFILL_A) * PLK_V4_HANDLER_BYTES; continue; }
+                const Op op = src < ops.size() ? ops[src] : Op{(unsigned)OP_END, 0u, false};
+                src++;
+                o[0] = op.h * PLK_V4_HANDLER_BYTES;
+                if (op.obs) o[1] = op.hi + (base << 16);
+            }
+        vs.first_y[c] = base + (nobs ? ou[0] : 0u) * (unsigned)nchar;
+    }
+}
+
+/* Replays the streamed interpreter's fetches against the 32-bit program (which plk_fused_check_pt has checked against the
+ * tree's program: the chain of its row and table fields names, observation by observation, the staged row and the
+ * table of the program's op -- a pair row and a pair table for a cherry's three ops).  For every category: the stream is
+ * the program's ops in order with a REFILL op closing every block, an END and two spare blocks after its block; every
+ * observation op extracts the byte of the next observation's row (obs_row = the chain's rows) from the chunk that is
+ * the current one, which was requested two ADVANCEs (or the prologue) earlier and waited for; no request goes past the
+ * unit's chunks; table fields fit 16 bits and the LDS address of the largest code stays inside C x table bytes. */
+static inline std::string plk_fused_check_v4s(const PlkFusedPT &fu, const PlkFusedV4S &vs, int nchar, int C, unsigned tip_base,
+                                              size_t lds_bytes_launched)
+{
+    if (tip_base % 32 != 0) return "v4s program: LDS base granule";
+    if (C < 1 || vs.C != C || vs.stride % 16 != 0 || vs.stride < 48 || vs.words.size() != (size_t)C * vs.stride || (int)vs.first_y.size() != C) return "v4s program: word count";
+    const size_t tip_bytes = (size_t)fu.units * nchar * 32;
+    if ((size_t)C * tip_bytes > lds_bytes_launched || tip_base + lds_bytes_launched > plk_pt_lds_limit(1024)) return "v4s program: table images larger than the launch's dynamic LDS";
+    /* the chain of the 32-bit words: row and unit of every observation */
+    std::vector<long> crow, cunit;
+    std::vector<size_t> real;          /* indices of the program's words up to the END */
+    {
+        crow.push_back(fu.first_row); crow.push_back(fu.second_row); cunit.push_back(fu.first_unit);
+        size_t w = 0;
+        for (; w < fu.words.size() && (fu.words[w] & 31) != OP_END; w++) {
+            real.push_back(w);
+            if (plk_word_is_obs(fu.words[w] & 31)) { cunit.push_back((fu.words[w] >> 5) & 0x7ff); crow.push_back(fu.words[w] >> 16); }
+        }
+        if (w == fu.words.size()) return "v4s program: no END in the 32-bit program";
+    }
+    const int nobs = (int)cunit.size() - 1;
+    if (nobs < 1 || vs.nobs != nobs || (int)vs.obs_row.size() != nobs) return "v4s program: observation count";
+    if (vs.chunks != plk_stream_chunks(nobs) || PLK_V4S_AHEAD >= vs.chunks) return "v4s program: chunks of a unit";
+    for (int n = 0; n < nobs; n++) if (vs.obs_row[n] != crow[n] || crow[n] < 0 || crow[n] >= (long)fu.row_node.size()) return plk_fmt("v4s program: observation %ld streams another row than the program reads", n);
+    std::vector<char> pair_unit(fu.units, 0);
+    for (size_t t = 0; t < fu.tab_unit.size(); t++) if (fu.tab_eb[t] >= 0 && fu.tab_unit[t] >= 0 && fu.tab_unit[t] < fu.units) pair_unit[fu.tab_unit[t]] = 1;
+    const unsigned tb32 = tip_base / 32, cat32 = (unsigned)fu.units * (unsigned)nchar;
+    const size_t nblocks = vs.stride / 16;
+    for (int c = 0; c < C; c++) {
+        const unsigned base = tb32 + (unsigned)c * cat32;
+        auto y_ok = [&](unsigned y, long unit) {
+            if (unit < 0 || unit >= fu.units || y != base + (unsigned)unit * (unsigned)nchar || y >= 65536u) return false;
+            const size_t ncodes = pair_unit[unit] ? (size_t)nchar * nchar : (size_t)nchar;
+            return (size_t)y * 32 >= tip_base + (size_t)c * tip_bytes && ((size_t)y + ncodes) * 32 <= tip_base + (size_t)(c + 1) * tip_bytes;
+        };
+        if (!y_ok(vs.first_y[c], cunit[0])) return "v4s program: prologue table field";
+        const unsigned *wd = &vs.words[(size_t)c * vs.stride];
+        /* prologue: chunk 0 is waited for and current, chunks 1 .. AHEAD are in flight */
+        int cur = 0, requested = PLK_V4S_AHEAD, nadv = 0, oi = 0;
+        if (requested >= vs.chunks) return "v4s program: the prologue reads past the unit";
+        size_t src = 0;
+        long end_block = -1;
+        for (size_t b = 0; b < nblocks; b++)
+            for (int j = 0; j < 8; j++) {
+                const unsigned lo = wd[(b * 8 + j) * 2], hi = wd[(b * 8 + j) * 2 + 1];
+                if (lo % PLK_V4_HANDLER_BYTES != 0 || lo >= (unsigned)PLK_V4_HANDLER_SLOTS * PLK_V4_HANDLER_BYTES) return plk_fmt("v4s program: handler offset in block %ld", (long)b);
+                const unsigned hidx = lo / PLK_V4_HANDLER_BYTES;
+                if (j == 7) {
+                    if (hidx != (unsigned)((b & 1) ? PLK_V4_REFILL_B : PLK_V4_REFILL_A) || hi != 0) return plk_fmt("v4s program: block %ld does not end in its REFILL op", (long)b);
+                    continue;
+                }
+                if (end_block >= 0) { if (hidx != OP_END || hi != 0) return "v4s program: ops after END"; continue; }
+                if (hidx == (unsigned)PLK_V4S_ADVANCE || hidx == (unsigned)PLK_V4S_ADVANCE + 1) {
+                    if (hi != 0 || hidx - PLK_V4S_ADVANCE != (unsigned)(nadv & 1)) return plk_fmt("v4s program: ADVANCE %ld of the wrong kind", nadv);
+                    /* the older chunk in flight becomes current; the chunk after the ones in flight is requested */
+                    cur = requested - (PLK_V4S_AHEAD - 1);
+                    requested++;
+                    if (requested >= vs.chunks) return plk_fmt("v4s program: ADVANCE %ld reads past the unit's chunks", nadv);
+                    nadv++;
+                    continue;
+                }
+                if (hidx >= 32) return plk_fmt("v4s program: REFILL op inside block %ld", (long)b);
+                if (hidx == OP_END) {
+                    if (hi != 0) return "v4s program: stray fields in END";
+                    if (src != real.size() || oi != nobs) return "v4s program: END before the program's last op";
+                    end_block = (long)b;
+                    continue;
+                }
+                if (src >= real.size()) return "v4s program: more ops than the program";
+                const unsigned w = fu.words[real[src++]];
+                if (hidx != (w & 31)) return plk_fmt("v4s program: op %ld is not the program's", (long)(src - 1));
+                if (!plk_word_is_obs(hidx)) { if (hi != 0) return plk_fmt("v4s program: stray fields in op %ld", (long)(src - 1)); continue; }
+                if (oi >= nobs) return "v4s program: more observation ops than observations";
+                const int next = oi + 1 < nobs ? oi + 1 : oi;
+                if ((hi & 0xffffu) != (unsigned)(8 * (next % 4))) return plk_fmt("v4s program: observation %ld extracts the wrong byte", oi);
+                if (cur != next / 4) return plk_fmt("v4s program: observation %ld extracts from chunk %ld, its code is in chunk %ld", oi, cur, next / 4);
+                if (!y_ok(hi >> 16, cunit[next])) return plk_fmt("v4s program: table field of observation %ld", oi);
+                oi++;
+            }
+        if (end_block < 0) return "v4s program: no END";
+        if ((size_t)end_block + 2 >= nblocks) return "v4s program: fewer than two spare blocks after the END";
+    }
     return "";
 }
 

@@ -34,6 +34,17 @@ Registers (all named in the clobber list of the asm statement):
   s[20:21] program pointer (next block to request)   s[22:23] the op being executed (s23 = its fields)
   s[24:25] jump target (s25 = high half of the table address, constant)   s26 low half of the table address
   s27 = -1022   s28 s29 temporaries   s[30:31] matrix stream pointer
+
+Second emission mode, STREAMED codes (k_ll_fused4_v4s, plk_fused4_v4s.h -> plk_fused4_v4s_asm.h): the codes of the
+observation ops do not sit in LDS rows, they arrive packed four to a dword from a stream in global memory that holds a
+128-site unit's bytes in program order (plk_stream_dword in plk_program.h).  What differs from the text above:
+  hi dword  observation ops: bits 31:16 = LDS offset / 32 of the table the NEXT observation op reads (the category's base
+            included), bits 4:0 = bit offset (0 / 8 / 16 / 24) of that observation's code in the current dword
+  v[74:75]  the current dword of site A | site B   v76 lane * 8 (offset of the lane's dword pair in a chunk)
+  v[146:147] v[148:149]  the two chunks in flight   s[34:35] stream pointer (next chunk to request)   v77 unused
+  handlers 34 + k (k < 2) ADVANCE_k: wait for the older of the two chunks in flight, make it the current dword and
+  request the chunk after next into its register pair.  The op stream holds an ADVANCE before the observation op that
+  extracts the first byte of a new dword, kinds alternating from 0.
 """
 import os
 
@@ -97,6 +108,25 @@ def tipnext():
             "ds_read_u8 v74, v76", "@HALF ds_read_u8 v75, v76"]
 
 
+def tipnext_s():
+    # v_bfe_u32 reads bits 4:0 of its offset operand only: the op's field dword serves as it is
+    return ["s_lshr_b32 s28, s23, 16",
+            "v_bfe_u32 v72, v74, s23, 8", "v_bfe_u32 v73, v75, s23, 8",
+            "v_add_lshl_u32 v72, v72, s28, 5", "v_add_lshl_u32 v73, v73, s28, 5",
+            "ds_read_b128 v[56:59], v72", "ds_read_b128 v[60:63], v72 offset:16",
+            "ds_read_b128 v[64:67], v73", "ds_read_b128 v[68:71], v73 offset:16"]
+
+
+RING = (146, 148)             # streamed mode: register pairs of the two chunks in flight
+CHUNK_BYTES = 512             # one wave-wide dwordx2 load
+
+
+def advance(k):
+    return ["s_waitcnt vmcnt(1)", "v_mov_b64 v[74:75], %s" % pair(RING[k]),
+            "global_load_dwordx2 %s, v76, s[34:35]" % pair(RING[k]),
+            "s_add_u32 s34, s34, 0x%x" % CHUNK_BYTES, "s_addc_u32 s35, s35, 0"]
+
+
 def push(d):
     out = []
     for i in range(4):
@@ -146,9 +176,11 @@ def scale():
 RET = ["s_movrels_b64 s[22:23], s[68:69]", "s_addk_i32 m0, 0x2", "s_or_b32 s24, s26, s22", "s_setpc_b64 s[24:25]"]
 NSLOTS = 64
 REFILL_A, REFILL_B = 32, 33
+ADVANCE0 = 34
 
 
-def handlers():
+def handlers(streamed=False):
+    tipnext = tipnext_s if streamed else globals()["tipnext"]
     h = {}
     h[0] = ["s_waitcnt lgkmcnt(0)"] + tipset() + tipnext() + RET
     h[1] = ["s_waitcnt lgkmcnt(0)"] + tipmul() + tipnext() + RET
@@ -167,10 +199,13 @@ def handlers():
     adv = ["s_add_u32 s20, s20, 0x40", "s_addc_u32 s21, s21, 0"]
     h[REFILL_A] = ["s_waitcnt lgkmcnt(0)", "s_load_dwordx16 s[68:83], s[20:21], 0x0"] + adv + RET
     h[REFILL_B] = ["s_mov_b32 m0, 0", "s_waitcnt lgkmcnt(0)", "s_load_dwordx16 s[84:99], s[20:21], 0x0"] + adv + RET
+    if streamed:
+        for k in range(2):
+            h[ADVANCE0 + k] = advance(k) + RET
     return h
 
 
-def emit():
+def emit(streamed=False):
     L = []           # (text, is_label)
 
     def ins(lines):
@@ -182,11 +217,29 @@ def emit():
     for i in range(4):
         pro += ["v_mov_b32 v%d, 0" % (XA + 2 * i), "v_mov_b32 v%d, 0x3ff00000" % (XA + 2 * i + 1),
                 "v_mov_b32 v%d, 0" % (XB + 2 * i), "v_mov_b32 v%d, 0x3ff00000" % (XB + 2 * i + 1)]
-    pro += ["v_mov_b32 v78, 0", "v_mov_b32 v79, 0", "v_mov_b32 v77, %[clane]",
+    if streamed:
+        # the first three chunks: the current dword and the two in flight; no older vector memory operation may be counted
+        pro += ["s_waitcnt vmcnt(0)", "v_mov_b32 v76, %[voff]", "s_mov_b64 s[34:35], %[strm]",
+                "global_load_dwordx2 v[74:75], v76, s[34:35]",
+                "global_load_dwordx2 %s, v76, s[34:35] offset:%d" % (pair(RING[0]), CHUNK_BYTES),
+                "global_load_dwordx2 %s, v76, s[34:35] offset:%d" % (pair(RING[1]), 2 * CHUNK_BYTES),
+                "s_add_u32 s34, s34, 0x%x" % (3 * CHUNK_BYTES), "s_addc_u32 s35, s35, 0"]
+    pro += ["v_mov_b32 v78, 0", "v_mov_b32 v79, 0"] + ([] if streamed else ["v_mov_b32 v77, %[clane]"]) + [
             "s_mov_b64 s[20:21], %[ops]", "s_mov_b64 s[30:31], %[mstream]", "s_movk_i32 s27, 0xfc02", "s_mov_b32 m0, 0",
             "s_load_dwordx16 s[68:83], s[20:21], 0x0", "s_load_dwordx16 s[84:99], s[20:21], 0x40",
             "s_add_u32 s20, s20, 0x80", "s_addc_u32 s21, s21, 0",
-            "s_load_dwordx16 s[36:51], s[30:31], 0x0", "s_load_dwordx16 s[52:67], s[30:31], 0x40",
+            "s_load_dwordx16 s[36:51], s[30:31], 0x0", "s_load_dwordx16 s[52:67], s[30:31], 0x40"]
+    if streamed:
+        # prefetch chain start: the first observation's code is byte 0 of chunk 0, its values
+        pro += ["s_getpc_b64 s[24:25]", ".Lpcref_%=:", "s_add_u32 s26, s24, .Lh0_%=-.Lpcref_%=", "s_addc_u32 s25, s25, 0",
+                "s_waitcnt vmcnt(2)",
+                "v_bfe_u32 v72, v74, 0, 8", "v_bfe_u32 v73, v75, 0, 8",
+                "v_add_lshl_u32 v72, v72, %[y0], 5", "v_add_lshl_u32 v73, v73, %[y0], 5",
+                "ds_read_b128 v[56:59], v72", "ds_read_b128 v[60:63], v72 offset:16",
+                "ds_read_b128 v[64:67], v73", "ds_read_b128 v[68:71], v73 offset:16",
+                "s_waitcnt lgkmcnt(0)"]
+    else:
+        pro += [
             # prefetch chain start: codes of the first observation, its values, codes of the second
             "v_lshl_add_u32 v76, %[z0], 6, v77", "ds_read_u8 v74, v76", "@HALF ds_read_u8 v75, v76",
             "s_getpc_b64 s[24:25]", ".Lpcref_%=:", "s_add_u32 s26, s24, .Lh0_%=-.Lpcref_%=", "s_addc_u32 s25, s25, 0",
@@ -199,7 +252,7 @@ def emit():
     ins(pro)
     ins(RET)           # the first op
     # ---- handlers ----
-    h = handlers()
+    h = handlers(streamed)
     ins([".p2align 15", ".Lh0_%=:"])
     for idx in range(NSLOTS):
         if idx:
@@ -236,10 +289,12 @@ def main():
     sizes = {"v_mul_f64": 8, "v_fma_f64": 8, "v_mov_b64": 4, "v_mov_b32": 4, "v_max_u32": 4, "v_max3_u32": 8, "v_lshrrev_b32": 4,
              "v_sub_u32": 8, "v_ldexp_f64": 8, "v_add3_u32": 8, "v_add_lshl_u32": 8, "v_lshl_add_u32": 8, "ds_read_b128": 8,
              "ds_read_u8": 8, "s_waitcnt": 4, "s_add_u32": 8, "s_addc_u32": 4, "s_load_dwordx16": 8, "s_setpc_b64": 4,
-             "s_lshr_b32": 4, "s_and_b32": 8, "s_branch": 4, "s_movrels_b64": 4, "s_addk_i32": 4, "s_or_b32": 4, "s_mov_b32": 4}
-    for idx, body in handlers().items():
-        n = sum(sizes[b.replace("@HALF ", "").split()[0]] for b in body)
-        assert n <= HS, (idx, n)
+             "s_lshr_b32": 4, "s_and_b32": 8, "s_branch": 4, "s_movrels_b64": 4, "s_addk_i32": 4, "s_or_b32": 4, "s_mov_b32": 4,
+             "v_bfe_u32": 8, "global_load_dwordx2": 8}
+    for streamed in (False, True):
+        for idx, body in handlers(streamed).items():
+            n = sum(sizes[b.replace("@HALF ", "").split()[0]] for b in body)
+            assert n <= HS, (streamed, idx, n)
     vregs = ["v%d" % r for r in range(24, STACK0 + 64)]
     sregs = ["s%d" % r for r in range(20, 100)] + ["m0"]
     hdr = '''/* GENERATED by tools/gen_fused4_v4.py -- do not edit; change the generator and run it again.
@@ -266,6 +321,34 @@ def main():
 #endif
 ''' % (HS, NSLOTS, REFILL_A, REFILL_B, c_string(lines), ", ".join('"%s"' % v for v in vregs), ", ".join('"%s"' % s for s in sregs))
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "phyly_amd", "csrc", "plk_fused4_v4_asm.h")
+    with open(path, "w") as f:
+        f.write(hdr)
+    print("wrote", path, "(%d asm lines)" % len(lines))
+    # ---- streamed codes ----
+    lines = emit(True)
+    assert not any(t.startswith("@HALF ") for t in lines)
+    vregs += ["v%d" % r for r in range(RING[0], RING[1] + 2)]
+    hdr = '''/* GENERATED by tools/gen_fused4_v4.py -- do not edit; change the generator and run it again.
+ *
+ * Assembly text of k_ll_fused4_v4s (plk_fused4_v4s.h): the two-sites-per-lane interpreter with the codes streamed from
+ * global memory into registers.  Op format, handler numbering and the register map are documented in the generator. */
+#ifndef PLK_FUSED4_V4S_ASM_H
+#define PLK_FUSED4_V4S_ASM_H
+
+#define PLK_V4S_ADVANCE %d
+#define PLK_V4S_CHUNK_BYTES %d
+
+#define PLK_V4S_PROGRAM \\
+%s
+        ""
+
+#define PLK_V4S_CLOBBERS "memory", "scc", "vcc", \\
+        %s, \\
+        %s
+
+#endif
+''' % (ADVANCE0, CHUNK_BYTES, c_string(lines), ", ".join('"%s"' % v for v in vregs), ", ".join('"%s"' % s for s in sregs))
+    path = os.path.join(os.path.dirname(path), "plk_fused4_v4s_asm.h")
     with open(path, "w") as f:
         f.write(hdr)
     print("wrote", path, "(%d asm lines)" % len(lines))
