@@ -402,7 +402,11 @@ enum {
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
- * kernel applies; used by tests and by bench.py --kernel generic */
+ * kernel applies; used by tests and by bench.py --kernel generic.
+ * Which ll kernel runs is decided once, when the device formats of the program are uploaded (the engine's ll plan), not
+ * per evaluation.  Setting any option that decision reads (PLK_OPT_FUSED_SITES_PER_LANE, _FUSED_ASM, _MFMA, _PAIR_TABLES,
+ * _VEC_REG_STACK, _MFMA_NS2) marks the plan stale, PLK_OPT_FORCE_GENERIC the program itself: the next evaluation
+ * decides and uploads again. */
 int plk_set_option(plk_engine *h, int option, long value);
 enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PER_LANE = 2 /* 0 auto, 1, 2 */,
        PLK_OPT_FUSED_ASM = 3 /* 1 (default): assembly interpreter loop where applicable, 0: C++ loop */,

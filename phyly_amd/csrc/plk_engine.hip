@@ -49,6 +49,23 @@
 #define PLK_MAX_K 64
 #define PLK_MAX_C 64
 
+/* Which ll kernel runs for the engine's state, and how it is launched: the only record of the choice.  upload_formats
+ * writes it together with the device formats it names; ll_impl, build_tables, run_expm and plk_get_info read it. */
+enum LlFamily { LL_FUSED4 = 1, LL_GENERIC = 2, LL_MFMA = 3, LL_VEC = 4 };      /* the values of PLK_INFO_LL_KERNEL */
+struct LlPlan {
+    LlFamily family = LL_GENERIC;
+    PlkK4Choice k4;                      /* LL_FUSED4: variant, sites per tile, NS, D, pack4, table base (plk_k4_choose) */
+    bool pair_tables = false;            /* LL_FUSED4, LL_VEC: the formats are the pair-table ones (fpt) ... */
+    int npairs = 0;                      /* ... with so many cherries as tables (PLK_INFO_PAIR_TABLES) */
+    int block = 0, wg_sites = 0;         /* lanes per workgroup; sites per workgroup (k = 4: per tile) */
+    size_t lds = 0;                      /* dynamic LDS of the launch */
+    int mfma_T = 0;                      /* LL_MFMA: 16-row tiles of a matrix; two 16-site groups per wave */
+    bool mfma_ns2 = false;
+    bool vec_rs = false;                 /* LL_VEC: register stack, and its window of three slots */
+    int vec_reg_lo = 0;
+    long info_variant = 0, info_form = 0, info_exec_flops = 0;     /* PLK_INFO_LL_VARIANT, _FORM, _LL_EXEC_FLOPS */
+};
+
 struct plk_engine {
     int device = 0;
     hipStream_t stream = nullptr, own_stream = nullptr;   /* stream in use; the engine's own one */
@@ -92,11 +109,14 @@ struct plk_engine {
     double *d_w = nullptr;
 
     /* traversal program (plk_program.h) */
-    /* prog_dirty: the program must be rebuilt (tree / patterns / options changed); fmt_dirty: its device formats are
-     * not uploaded for kernel kind fmt_kind; tables_dirty: the P-dependent tables (matrix stream, tip tables, A
-     * fragments) are older than P */
+    /* prog_dirty: the program must be rebuilt (tree / patterns / PLK_OPT_FORCE_GENERIC changed); fmt_dirty: the ll plan
+     * and the device formats it chose are stale (set by build_program and by every option the plan reads);
+     * tables_dirty: the P-dependent tables (matrix stream, tip tables, A fragments) are older than P */
     bool prog_dirty = true, fmt_dirty = true, tables_dirty = true;
-    long fmt_kind = 0;
+    LlPlan plan;                         /* which ll kernel runs, and how: written by upload_formats, valid while !fmt_dirty */
+    size_t k4_static_lds[3] = {};        /* PlkK4Shape::static_lds, asked of the runtime once (k4_static_lds_known) */
+    hipError_t k4_static_lds_err[3] = {};
+    bool k4_static_lds_known = false;
     PlkProgram pg;
     std::vector<plk_op2> &ops = pg.ops;
     std::vector<int> &op_edge = pg.op_edge;          /* CSR edge per op or -1 */
@@ -106,15 +126,10 @@ struct plk_engine {
     int &slots_needed = pg.slots_needed;
     PlkFused fu;                         /* fused k = 4 formats of the program */
     PlkFusedPT fpt;                      /* ... and of the pair-table interpreter (k_ll_fused4_asm_pt) */
-    bool fmt_pt = false;                 /* the uploaded kind-1 formats are the pair-table ones */
     unsigned *d_words_pt = nullptr;
     PlkFusedV4 fv4;                      /* 64-bit ops of the two-sites-per-lane interpreter */
     PlkVecPT vpt;                        /* the vector ll kernel's program on pair tables */
-    bool vec_pt = false;
-    int pt_kind = 0, pt_tile_sites = 0;  /* 1: k_ll_fused4_asm_pt, 2: k_ll_fused4_v4; sites per tile of the uploaded formats */
-    unsigned v4_tip_base = 0;            /* LDS address of the table image = static LDS of the kernel */
     PlkFusedV4S fv4s;                    /* streamed codes (k_ll_fused4_v4s): one op stream per category */
-    bool pt_stream = false;              /* the uploaded pt_kind 2 formats are the streamed-code ones */
     unsigned *d_cstream = nullptr; size_t cstream_cap = 0;   /* the code stream (plk_stream_dword), built by upload_formats */
     int *d_obs_row = nullptr;            /* staged row per observation of the program */
     int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [2][rows] staged-row nodes; [4][ntab] unit, edge, leaf edges of a pair */
@@ -1421,9 +1436,9 @@ extern "C" int plk_set_option(plk_engine *h, int option, long value)
     if (option == PLK_OPT_FUSED_SITES_PER_LANE) { h->opt_fused_ns = value; h->fmt_dirty = true; return PLK_OK; }
     if (option == PLK_OPT_FUSED_ASM) { h->opt_fused_asm = value; h->fmt_dirty = true; return PLK_OK; }
     if (option == PLK_OPT_UP_NODES) { h->opt_up_nodes = value; return PLK_OK; }
-    if (option == PLK_OPT_MFMA) { h->opt_mfma = value; return PLK_OK; }
-    if (option == PLK_OPT_MFMA_NS2) { h->opt_mfma_ns2 = value; return PLK_OK; }
-    if (option == PLK_OPT_VEC_REG_STACK) { h->opt_vec_reg_stack = value; return PLK_OK; }
+    if (option == PLK_OPT_MFMA) { h->opt_mfma = value; h->fmt_dirty = true; return PLK_OK; }
+    if (option == PLK_OPT_MFMA_NS2) { h->opt_mfma_ns2 = value; h->fmt_dirty = true; return PLK_OK; }
+    if (option == PLK_OPT_VEC_REG_STACK) { h->opt_vec_reg_stack = value; h->fmt_dirty = true; return PLK_OK; }
     if (option == PLK_OPT_PAIR_TABLES) { h->opt_pair_tables = value; h->fmt_dirty = true; return PLK_OK; }
     h->err = "plk_set_option: unknown option";
     return PLK_E_ARG;
@@ -1474,7 +1489,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
     case PLK_INFO_LL_FORM: *out = h->info_ll_form; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
-    case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && ((h->fmt_pt && h->fmt_kind == 1) || (h->vec_pt && h->fmt_kind == 4)) ? h->fpt.npairs : 0; return PLK_OK;
+    case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && h->plan.pair_tables ? h->plan.npairs : 0; return PLK_OK;
     case PLK_INFO_STACK_SLOTS: *out = h->slots_needed; return PLK_OK;
     case PLK_INFO_PROGRAM_OPS: *out = (long)h->ops.size(); return PLK_OK;
     case PLK_INFO_LAST_LL_KERNEL_NS: *out = h->info_ll_kernel_ns; return PLK_OK;
@@ -1577,18 +1592,19 @@ static int run_expm(plk_engine *h, bool post = false, bool need_dP = true)
     const size_t lds_bytes = expm_lds_bytes((size_t)k, threads, &use_lds);
     if (!use_lds) { if ((rc = dev_reserve(h, &h->d_scratch, &h->scratch_cap, (size_t)C * E * EXPM_BUFFERS * kk))) return rc; }
     ExpmPost ep = {};
-    post = post && k == 4 && h->fmt_kind == 1 && !h->fmt_dirty && h->d_edge_slot;
+    const bool pt = h->plan.pair_tables;
+    post = post && k == 4 && !h->fmt_dirty && h->plan.family == LL_FUSED4 && h->d_edge_slot;
     if (post) {
         ep.edge_slot = h->d_edge_slot; ep.nmat1 = (int)h->mat_edge.size() + 1; ep.ntips1 = (int)h->tip_edge.size() + 1;
         ep.nchar = h->nchar; ep.defs = h->d_defs; ep.PS = h->d_PS; ep.tip = h->d_tip;
-        if (h->fmt_pt) { ep.nmat1 = (int)h->fpt.mat_edge.size() + 1; ep.ntips1 = h->fpt.units; }    /* no tip slots in edge_slot: tables below */
+        if (pt) { ep.nmat1 = (int)h->fpt.mat_edge.size() + 1; ep.ntips1 = h->fpt.units; }    /* no tip slots in edge_slot: tables below */
     }
     ep.skip_dP = need_dP ? 0 : 1;
     hipLaunchKernelGGL(k_expm_dd<false>, dim3(C * E), dim3(threads), lds_bytes, h->stream,
                        k, E, h->d_Qn, h->d_edge_rates, h->d_cat_rates, h->d_Pdd, h->d_P, h->d_dP,
                        h->d_scratch, use_lds, (const double *)nullptr, 0L, 0, (const int *)nullptr, (double *)nullptr, ep);
     HIPCHK(h, hipGetLastError());
-    if (post && h->fmt_pt) {
+    if (post && pt) {
         const int ntab = (int)h->fpt.tab_unit.size();
         hipLaunchKernelGGL(k_build_tables_pt, dim3(ntab, C), dim3(64), 0, h->stream,
                            E, ntab, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
@@ -1811,13 +1827,6 @@ static int build_program(plk_engine *h)
     return PLK_OK;
 }
 
-/* sites per lane of the fused kernel: 1 (the assembly interpreter, the fastest variant measured) unless the
- * option asks for the two-sites C++ variant and the stack (<= 8 slots) allows it */
-static int fused_sites_per_lane(const plk_engine *h)
-{
-    return h->opt_fused_ns == 2 && h->slots_needed <= 8 ? 2 : 1;
-}
-
 /* register-resident vector kernel (plk_vec.h): 9 <= k <= 32 with compact codes (amino acids); PLK_OPT_MFMA = 2
  * forces the matrix-core kernel instead */
 static bool use_vec(const plk_engine *h)
@@ -1831,163 +1840,81 @@ static bool use_mfma(const plk_engine *h)
     return !h->opt_force_generic && h->opt_mfma && h->pat_mode == 1 && h->k >= 9 && h->k <= 64;
 }
 
-/* dynamic LDS of k_ll_mfma: the A fragments of one matrix + one 64-byte code row per observed node */
-static size_t mfma_ll_lds_bytes(const plk_engine *h)
+/* dynamic LDS of k_ll_mfma / k_ll_mfma_ns2: the A fragments of one matrix + one code row of the workgroup's sites
+ * (MF_SITES, or twice that with two 16-site groups per wave) per observed node */
+static size_t mfma_ll_lds_bytes(const plk_engine *h, int sites)
 {
     const int T = (h->k + 15) / 16, kk4 = (h->k + 3) / 4;
-    return (size_t)T * kk4 * 64 * sizeof(double) + h->obs_nodes.size() * (size_t)MF_SITES;
+    return (size_t)T * kk4 * 64 * sizeof(double) + h->obs_nodes.size() * (size_t)sites;
 }
 
-/* k = 4 tile kernels: the assembly interpreter stages 4-bit codes when there are at most 16 character definitions,
- * which lets it take about twice the taxa of the C++ interpreter before the tile no longer fits the LDS */
-static bool fused_asm_fits(const plk_engine *h)
+/* the window of three stack slots that takes most pushes (register stack of the vector kernels) */
+static int vec_reg_window(const plk_engine *h)
 {
-    if (fused_sites_per_lane(h) != 1 || !plk_fused_asm_ok(h->pg) || !h->opt_fused_asm) return false;
-    return plk_fused_lds_bytes(h->pg, h->nchar, h->nchar <= 16 ? PLK_TILE / 2 : PLK_TILE) <= PLK_LDS_LIMIT;
+    std::vector<long> per_slot(std::max(h->slots_needed, 1), 0);
+    for (const plk_op2 &o : h->ops) if ((o.x & 0xff) == OP_PUSH && o.y < (int)per_slot.size()) per_slot[o.y]++;
+    long best = -1;
+    int lo_best = 0;
+    for (int lo = 0; lo + 3 <= std::max(h->slots_needed, 3); lo++) {
+        long cnt = 0;
+        for (int q = lo; q < lo + 3 && q < (int)per_slot.size(); q++) cnt += per_slot[q];
+        if (cnt > best) { best = cnt; lo_best = lo; }
+    }
+    return lo_best;
 }
 
-/* pair-table interpreter (k_ll_fused4_asm_pt): trees within the 4-slot VGPR stack and at most 16 character definitions
- * (the combined code of a cherry is one byte); as many cherries become tables as the two-workgroups-per-CU LDS budget
- * takes.  Fills fpt; false when even the table-less image does not fit (the 256-site kernels take over). */
-/* PLK_OPT_PAIR_TABLES: which pair-table interpreter, how many sites per tile (candidates in order of preference) */
-/* Streamed codes or a tile kernel?  PLK_OPT_PAIR_TABLES 7 asks for the streamed form wherever it fits, and so does the
- * default: against the parent's tile kernels it measured faster at every shape tried (profiles/ll_k4_stream_ab.json:
- * kernel time -6.1 % at BASELINE config 3 with 10M sites, -6.5 % at 2.5M, -2.3 % at 1.25M -- inside that shape's spread, not
- * slower --, -16 % with one category, -22 % at config 2), so no site count sends the default back to a tile kernel. */
-static bool stream_form_preferred(const plk_engine *h, long mode)
+/* the pair-table formats both the k = 4 and the vector kernels read: [2][rows] staged-row nodes; [4][ntab] unit, edge,
+ * leaf edges of a pair */
+static int upload_pair_table_lists(plk_engine *h)
 {
-    (void)h;
-    return mode == 7 || mode == 1;
+    const PlkFusedPT &f = h->fpt;
+    int rc;
+    std::vector<int> rn(f.row_node);
+    rn.insert(rn.end(), f.row_node2.begin(), f.row_node2.end());
+    if ((rc = dev_upload(h, &h->d_row_nodes, rn.data(), rn.size()))) return rc;
+    std::vector<int> tabs(f.tab_unit);
+    tabs.insert(tabs.end(), f.tab_edge.begin(), f.tab_edge.end());
+    tabs.insert(tabs.end(), f.tab_eb.begin(), f.tab_eb.end());
+    tabs.insert(tabs.end(), f.tab_ec.begin(), f.tab_ec.end());
+    return dev_upload(h, &h->d_tabs, tabs.data(), tabs.size());
 }
 
-static bool build_fused_pt(plk_engine *h)
-{
-    if (!h->opt_pair_tables || !h->opt_fused_asm || h->opt_fused_ns == 2 || h->slots_needed > 4 || h->nchar > 16) return false;
-    if (h->obs_nodes.empty()) return false;
-    struct Cand { int kind, tile; };
-    std::vector<Cand> cands;
-    h->pt_stream = false;
-    const long mode = h->opt_pair_tables & 7;
-    if ((mode == 1 || mode == 7) && h->S > 0 && stream_form_preferred(h, mode)) {
-        /* streamed codes: every cherry a table, the tables of all categories resident; needs the stream in device memory
-         * (an allocation that fails sends the query to the tile kernels, it does not fail it) */
-        plk_fused_pt_build(h->N, h->indptr.data(), h->indices.data(), h->pg, h->nchar, INT_MAX, h->fpt, true);
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, (const void *)k_ll_fused4_v4s<768>) == hipSuccess) {
-            const size_t lds = plk_fused_v4s_lds_bytes(h->fpt, h->nchar, h->C);
-            const size_t nunits = (size_t)((h->S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT);
-            size_t nobs = 0;
-            for (const PlkFusedPT::VOp &o : h->fpt.vops) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) nobs++;
-            if (nobs > 0 && lds + fa.sharedSizeBytes <= plk_pt_lds_limit(1024) && (fa.sharedSizeBytes + lds) / 32 < 65536 && h->fpt.units < 2048 &&
-                h->fpt.row_node.size() < 65536) {
-                if (dev_reserve(h, &h->d_cstream, &h->cstream_cap, nunits * (size_t)plk_stream_chunks((int)nobs) * PLK_V4S_UNIT) == PLK_OK) {
-                    h->v4_tip_base = (unsigned)fa.sharedSizeBytes;
-                    h->pt_kind = 2; h->pt_tile_sites = 1536; h->pt_stream = true;
-                    return true;
-                }
-                h->err.clear();
-                (void)hipGetLastError();
-            }
-        } else (void)hipGetLastError();
-    }
-    switch (mode) {
-    case 2: cands = {{1, 1024}}; break;
-    case 3: cands = {{1, 512}}; break;
-    case 5: cands = {{2, 1024}}; break;
-    case 6: cands = {{2, 1536}}; break;
-    default: {
-        /* 1536-site tiles run 1.3 x as long as 1024-site tiles (109 against 84 us a round at BASELINE config 3) and carry 1.5 x
-         * the sites; every CU runs ceil(tiles / CUs) rounds.  Few sites per GPU (a rank of an 8-way split) can need fewer
-         * round-times with the smaller tile: 1.25M sites are 4 rounds of 1536 (436 us) or 5 rounds of 1024 (420 us). */
-        auto rounds = [&](long tile) { const long nt = (h->S + tile - 1) / tile; return (double)((nt + h->num_cus - 1) / h->num_cus); };
-        if (h->S > 0 && rounds(1024) * 1.0 < rounds(1536) * 1.3) cands = {{2, 1024}, {2, 1536}, {1, 1024}, {1, 512}};
-        else cands = {{2, 1536}, {2, 1024}, {1, 1024}, {1, 512}};
-        break;
-    }
-    }
-    for (const Cand &cd : cands) {
-        const long limit = (long)plk_pt_lds_limit(cd.tile);
-        int max_pairs = INT_MAX;
-        for (int attempt = 0; attempt < 3; attempt++) {
-            plk_fused_pt_build(h->N, h->indptr.data(), h->indices.data(), h->pg, h->nchar, max_pairs, h->fpt, cd.kind == 2);
-            const long bytes = (long)plk_fused_pt_lds_bytes(h->fpt, h->nchar, cd.tile);
-            if (bytes <= limit && h->fpt.units < 2048 && h->fpt.row_node.size() < 65536) { h->pt_kind = cd.kind; h->pt_tile_sites = cd.tile; return true; }
-            if (h->fpt.npairs == 0) break;
-            /* a cherry as a table costs nchar - 2 more units and one row less than its two leaves */
-            const long per_pair = (long)(h->nchar - 2) * h->nchar * 32 - cd.tile;
-            if (per_pair <= 0) break;                       /* tables only shrink the image: nothing to give back */
-            const long drop = (bytes - limit + per_pair - 1) / per_pair;
-            max_pairs = drop >= h->fpt.npairs ? 0 : h->fpt.npairs - (int)drop;
-        }
-    }
-    return false;
-}
-
-static bool use_fused(const plk_engine *h)
-{
-    if (h->opt_force_generic) return false;
-    if (h->k != 4 || h->pat_mode != 1) return false;
-    if (h->slots_needed > PLK_FUSED_SLOTS) return false;
-    return fused_asm_fits(h) || plk_fused_lds_bytes(h->pg, h->nchar, PLK_TILE * fused_sites_per_lane(h)) <= PLK_LDS_LIMIT;
-}
-
-/* Device formats of the program for kernel kind (1 fused k = 4, 2 generic, 3 matrix cores, 4 vector): uploaded when
- * the program or the kind changes, not per evaluation. */
-static int upload_formats(plk_engine *h, long kind)
+/* k = 4 with compact codes: the fused kernel plk_k4_choose picks, or PLK_K4_NONE in p.k4.variant and nothing uploaded */
+static int upload_formats_fused4(plk_engine *h, LlPlan &p)
 {
     int rc;
-    const int nops = (int)h->ops.size(), ntips = (int)h->tip_edge.size();
-    std::vector<int> te = h->tip_edge;
-    te.push_back(-1);                                /* pseudo slot: the raw definitions (internal nodes with data) */
-    if ((rc = dev_upload(h, &h->d_tip_edge, te.data(), te.size()))) return rc;
-    if ((rc = dev_upload(h, &h->d_obs_nodes, h->obs_nodes.data(), h->obs_nodes.size()))) return rc;
-    h->fmt_pt = false;
-    if (kind == 1 && build_fused_pt(h)) {
-        /* pair-table interpreter: op words, staged-row nodes, table list; K1 writes the matrix stream itself, the tables
-         * are built from the unrounded P after it (k_build_tables_pt) */
-        const PlkFusedPT &f = h->fpt;
-        const int nrows = (int)f.row_node.size(), ntab = (int)f.tab_unit.size();
-        if (h->pt_kind == 2 && h->pt_stream) {
-            /* streamed codes: op words per category, then the stream itself from the resident code rows */
-            plk_fused_v4s_words(f, h->nchar, h->C, h->v4_tip_base, h->fv4s);
-            if ((rc = dev_upload(h, &h->d_words_pt, h->fv4s.words.data(), h->fv4s.words.size()))) return rc;
-            if ((rc = dev_upload(h, &h->d_obs_row, h->fv4s.obs_row.data(), h->fv4s.obs_row.size()))) return rc;
-        } else if (h->pt_kind == 2) {
-            /* the table image starts where the kernel's static LDS ends */
+    if (!h->k4_static_lds_known) {
+        /* a kernel the runtime cannot describe: the streamed form is then not chosen, a v4 tile kernel fails the query once chosen */
+        const void *fns[3] = {(const void *)k_ll_fused4_v4s<768>, (const void *)k_ll_fused4_v4<768>, (const void *)k_ll_fused4_v4<512>};
+        for (int i = 0; i < 3; i++) {
             hipFuncAttributes fa;
-            const void *fn = h->pt_tile_sites == 1536 ? (const void *)k_ll_fused4_v4<768> : (const void *)k_ll_fused4_v4<512>;
-            HIPCHK(h, hipFuncGetAttributes(&fa, fn));
-            h->v4_tip_base = (unsigned)fa.sharedSizeBytes;
-            plk_fused_v4_words(f, h->nchar, h->pt_tile_sites, h->v4_tip_base, h->fv4);
-            if ((rc = dev_upload(h, &h->d_words_pt, h->fv4.words.data(), h->fv4.words.size()))) return rc;
-        } else if ((rc = dev_upload(h, &h->d_words_pt, f.words.data(), f.words.size()))) return rc;
-        std::vector<int> rn(f.row_node);
-        rn.insert(rn.end(), f.row_node2.begin(), f.row_node2.end());
-        if ((rc = dev_upload(h, &h->d_row_nodes, rn.data(), rn.size()))) return rc;
-        if (h->pt_stream) {
-            const long nunits = (h->S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
-            const size_t total = (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT;
-            if (total > h->cstream_cap || (total + 255) / 256 > 0x7fffffffu) { h->err = "internal: code stream size"; return PLK_E_ARG; }
-            hipLaunchKernelGGL(k_build_code_stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_codes, h->Spad, nunits,
-                               h->d_obs_row, h->fv4s.nobs, h->d_row_nodes, nrows, h->nchar, h->fv4s.chunks, h->d_cstream);
-            HIPCHK(h, hipGetLastError());
+            h->k4_static_lds_err[i] = hipFuncGetAttributes(&fa, fns[i]);
+            if (h->k4_static_lds_err[i] == hipSuccess) h->k4_static_lds[i] = fa.sharedSizeBytes;
+            else (void)hipGetLastError();
         }
-        std::vector<int> tabs(f.tab_unit);
-        tabs.insert(tabs.end(), f.tab_edge.begin(), f.tab_edge.end());
-        tabs.insert(tabs.end(), f.tab_eb.begin(), f.tab_eb.end());
-        tabs.insert(tabs.end(), f.tab_ec.begin(), f.tab_ec.end());
-        if ((rc = dev_upload(h, &h->d_tabs, tabs.data(), tabs.size()))) return rc;
-        std::vector<int> em(2 * (size_t)h->E, -1);
-        for (size_t mi = 0; mi < f.mat_edge.size(); mi++) em[f.mat_edge[mi]] = (int)mi;
-        if ((rc = dev_upload(h, &h->d_edge_slot, em.data(), em.size()))) return rc;
-        if ((rc = dev_reserve(h, &h->d_PS, &h->ps_cap, (size_t)h->C * (f.mat_edge.size() + 1) * 16))) return rc;
-        if ((rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * f.units * h->nchar * 4))) return rc;
-        HIPCHK(h, hipMemsetAsync(h->d_PS, 0, (size_t)h->C * (f.mat_edge.size() + 1) * 16 * sizeof(double), h->stream));
-        (void)nrows; (void)ntab;
-        h->fmt_pt = true;
-    } else if (kind == 1) {
+        h->k4_static_lds_known = true;
+    }
+    PlkK4Shape sh = {h->nchar, h->C, h->S, h->num_cus, h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
+    std::copy(h->k4_static_lds, h->k4_static_lds + 3, sh.static_lds);
+    const long nunits = (h->S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
+    p.k4 = plk_k4_choose(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess, h->fu, h->fpt, h->fv4, h->fv4s);
+    if (p.k4.variant == PLK_K4_V4S && dev_reserve(h, &h->d_cstream, &h->cstream_cap, (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT) != PLK_OK) {
+        /* a stream that cannot be allocated sends the query to the tile kernels, it does not fail it */
+        h->err.clear();
+        (void)hipGetLastError();
+        p.k4 = plk_k4_choose(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, false, h->fu, h->fpt, h->fv4, h->fv4s);
+    }
+    const PlkK4Choice &c = p.k4;
+    if (c.variant == PLK_K4_NONE) return PLK_OK;
+    if (c.variant == PLK_K4_V4) HIPCHK(h, h->k4_static_lds_err[c.tile == 1536 ? PLK_K4_LDS_V4_768 : PLK_K4_LDS_V4_512]);
+    if (!c.bad.empty()) { h->err = "internal: " + c.bad; return PLK_E_ARG; }
+    p.family = LL_FUSED4;
+    p.block = c.block; p.wg_sites = c.tile; p.lds = c.lds;
+    p.info_variant = c.variant == PLK_K4_CPP ? 3 : c.variant == PLK_K4_ASM ? 1 : c.variant == PLK_K4_ASM_PT ? 5 : 6;
+    p.info_form = c.variant == PLK_K4_V4S ? 1 : 0;
+    const int ntips = (int)h->tip_edge.size();
+    if (c.variant == PLK_K4_CPP || c.variant == PLK_K4_ASM) {
         /* int4 ops of the C++ interpreter, 32-bit op words of the assembly interpreter, compact matrix list */
-        plk_fused_build(h->N, h->pg, h->fu);
         if ((rc = dev_upload(h, &h->d_fops, reinterpret_cast<const int4 *>(h->fu.fops.data()), h->fu.fops.size()))) return rc;
         if ((rc = dev_upload(h, &h->d_words, h->fu.words.data(), h->fu.words.size()))) return rc;
         std::vector<int> me = h->mat_edge;
@@ -2006,133 +1933,212 @@ static int upload_formats(plk_engine *h, long kind)
         hipLaunchKernelGGL(k_build_tip, dim3(ntips + 1, h->C), dim3(64), 0, h->stream,
                            h->E, ntips + 1, h->nchar, h->d_tip_edge, h->d_Pdd, h->d_defs, h->d_tip);
         HIPCHK(h, hipGetLastError());
-    } else {
-        /* OP_MATVEC ops name the next OP_MATVEC (y, wrapping to the first): the vector kernel touches the
-         * cache lines of the next matrix while it multiplies with the current one */
-        std::vector<plk_op2> gops(h->ops);
-        int first = -1, prev = -1;
-        for (int pc = 0; pc < nops; pc++)
-            if ((gops[pc].x & 0xff) == OP_MATVEC) {
-                if (first < 0) first = pc;
-                if (prev >= 0) gops[prev].y = pc;
-                prev = pc;
-            }
-        if (prev >= 0) gops[prev].y = first;
-        if ((rc = dev_upload(h, &h->d_ops, reinterpret_cast<const int2 *>(gops.data()), gops.size()))) return rc;
-        if ((rc = dev_upload(h, &h->d_op_edge, h->op_edge.data(), h->op_edge.size()))) return rc;
-        if ((rc = dev_reserve(h, &h->d_PS, &h->ps_cap, (size_t)h->C * std::max(nops, 1) * h->K * h->K))) return rc;
-        h->vec_pt = false;
-        if (kind == 4 && h->opt_pair_tables && h->K <= 32 && !h->obs_nodes.empty()) {
-            /* pair-table program for the vector kernel: two-leaf subtrees as rows of L2-resident tables (nchar^2 rows of K
-             * doubles each), as many as 64 MB of tables per category take */
-            const long per_pair = (long)h->nchar * h->nchar * h->K * (long)sizeof(double);
-            const int max_pairs = (int)std::min<long>(INT_MAX, (64L << 20) / std::max<long>(per_pair, 1));
-            plk_fused_pt_build(h->N, h->indptr.data(), h->indices.data(), h->pg, h->nchar, max_pairs, h->fpt, false);
-            if (h->fpt.npairs > 0) {
-                plk_vec_pt_build(h->fpt, h->nchar, h->vpt);
-                const std::string bad = plk_vec_pt_check(h->N, h->indptr.data(), h->indices.data(), h->pg, h->fpt, h->vpt, h->nchar, h->E);
-                if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
-                const PlkFusedPT &f = h->fpt;
-                std::vector<int> rn(f.row_node);
-                rn.insert(rn.end(), f.row_node2.begin(), f.row_node2.end());
-                std::vector<int> tabs(f.tab_unit);
-                tabs.insert(tabs.end(), f.tab_edge.begin(), f.tab_edge.end());
-                tabs.insert(tabs.end(), f.tab_eb.begin(), f.tab_eb.end());
-                tabs.insert(tabs.end(), f.tab_ec.begin(), f.tab_ec.end());
-                if ((rc = dev_upload(h, &h->d_row_nodes, rn.data(), rn.size())) || (rc = dev_upload(h, &h->d_tabs, tabs.data(), tabs.size())) ||
-                    (rc = dev_upload(h, &h->d_mops, reinterpret_cast<const int4 *>(h->vpt.ops.data()), h->vpt.ops.size())) ||
-                    (rc = dev_upload(h, &h->d_op_edge, h->vpt.op_edge.data(), h->vpt.op_edge.size())) ||
-                    (rc = dev_reserve(h, &h->d_PS, &h->ps_cap, (size_t)h->C * h->vpt.ops.size() * h->K * h->K)) ||
-                    (rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * f.units * h->nchar * h->K))) return rc;
-                h->vec_pt = true;
-            }
+        return PLK_OK;
+    }
+    /* pair-table interpreters: op words, staged-row nodes, table list; K1 writes the matrix stream itself, the tables
+     * are built from the unrounded P after it (k_build_tables_pt) */
+    const PlkFusedPT &f = h->fpt;
+    p.pair_tables = true; p.npairs = f.npairs;
+    const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? h->fv4s.words : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
+    if ((rc = dev_upload(h, &h->d_words_pt, words.data(), words.size()))) return rc;
+    /* d_obs_row before the pair-table lists: the order in which these buffers were first allocated when the kernels were
+     * measured (with it after them, the streamed kernel at 1.25M sites of BASELINE config 3 ran 0.3 % longer) */
+    if (c.variant == PLK_K4_V4S && (rc = dev_upload(h, &h->d_obs_row, h->fv4s.obs_row.data(), h->fv4s.obs_row.size()))) return rc;
+    if ((rc = upload_pair_table_lists(h))) return rc;
+    if (c.variant == PLK_K4_V4S) {
+        /* streamed codes: the stream itself from the resident code rows */
+        const size_t total = (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT;
+        if (total > h->cstream_cap || (total + 255) / 256 > 0x7fffffffu) { h->err = "internal: code stream size"; return PLK_E_ARG; }
+        hipLaunchKernelGGL(k_build_code_stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_codes, h->Spad, nunits,
+                           h->d_obs_row, h->fv4s.nobs, h->d_row_nodes, (int)f.row_node.size(), h->nchar, h->fv4s.chunks, h->d_cstream);
+        HIPCHK(h, hipGetLastError());
+    }
+    std::vector<int> em(2 * (size_t)h->E, -1);
+    for (size_t mi = 0; mi < f.mat_edge.size(); mi++) em[f.mat_edge[mi]] = (int)mi;
+    if ((rc = dev_upload(h, &h->d_edge_slot, em.data(), em.size()))) return rc;
+    if ((rc = dev_reserve(h, &h->d_PS, &h->ps_cap, (size_t)h->C * (f.mat_edge.size() + 1) * 16))) return rc;
+    if ((rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * f.units * h->nchar * 4))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->d_PS, 0, (size_t)h->C * (f.mat_edge.size() + 1) * 16 * sizeof(double), h->stream));
+    return PLK_OK;
+}
+
+/* what the generic, vector and matrix-core kernels share: the int2 program, the edge per op, room for the matrix stream */
+static int upload_formats_generic(plk_engine *h, LlPlan &p)
+{
+    int rc;
+    const int nops = (int)h->ops.size();
+    /* OP_MATVEC ops name the next OP_MATVEC (y, wrapping to the first): the vector kernel touches the
+     * cache lines of the next matrix while it multiplies with the current one */
+    std::vector<plk_op2> gops(h->ops);
+    int first = -1, prev = -1;
+    for (int pc = 0; pc < nops; pc++)
+        if ((gops[pc].x & 0xff) == OP_MATVEC) {
+            if (first < 0) first = pc;
+            if (prev >= 0) gops[prev].y = pc;
+            prev = pc;
         }
-        if (kind == 4 && h->vec_pt) {
-            /* formats uploaded above */
-        } else if (kind == 4) {
-            if ((rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * (ntips + 1) * h->nchar * h->K))) return rc;
-            /* vector program: observation ops chained two ahead (value of the next op, code of the one after) */
-            PlkChain ch;
-            plk_chain_build(h->N, h->pg, 3, h->indices.data(), nullptr, nullptr, nullptr, ch);
-            const std::string bad = plk_chain_check(h->N, h->pg, ch, 3, INT_MAX, 0, 0, 0, 0, 0);
+    if (prev >= 0) gops[prev].y = first;
+    if ((rc = dev_upload(h, &h->d_ops, reinterpret_cast<const int2 *>(gops.data()), gops.size()))) return rc;
+    if ((rc = dev_upload(h, &h->d_op_edge, h->op_edge.data(), h->op_edge.size()))) return rc;
+    if ((rc = dev_reserve(h, &h->d_PS, &h->ps_cap, (size_t)h->C * std::max(nops, 1) * h->K * h->K))) return rc;
+    p.family = LL_GENERIC;
+    p.block = GEN_BLOCK; p.wg_sites = GEN_BLOCK;
+    return PLK_OK;
+}
+
+/* 9 <= k <= 32 with compact codes: register-resident vector kernel (plk_vec.h), on pair tables where there are cherries */
+static int upload_formats_vec(plk_engine *h, LlPlan &p)
+{
+    int rc;
+    if ((rc = upload_formats_generic(h, p))) return rc;
+    p.family = LL_VEC;
+    p.block = VEC_BLOCK; p.wg_sites = VEC_BLOCK;
+    /* register stack (PLK_OPT_VEC_REG_STACK, default on): the window of three slots that takes most pushes */
+    p.vec_rs = h->opt_vec_reg_stack && h->K <= 20 && h->slots_needed >= 1;
+    p.vec_reg_lo = p.vec_rs ? vec_reg_window(h) : 0;
+    if (h->opt_pair_tables && h->K <= 32 && !h->obs_nodes.empty()) {
+        /* pair-table program for the vector kernel: two-leaf subtrees as rows of L2-resident tables (nchar^2 rows of K
+         * doubles each), as many as 64 MB of tables per category take */
+        const long per_pair = (long)h->nchar * h->nchar * h->K * (long)sizeof(double);
+        const int max_pairs = (int)std::min<long>(INT_MAX, (64L << 20) / std::max<long>(per_pair, 1));
+        plk_fused_pt_build(h->N, h->indptr.data(), h->indices.data(), h->pg, h->nchar, max_pairs, h->fpt, false);
+        if (h->fpt.npairs > 0) {
+            plk_vec_pt_build(h->fpt, h->nchar, h->vpt);
+            const std::string bad = plk_vec_pt_check(h->N, h->indptr.data(), h->indices.data(), h->pg, h->fpt, h->vpt, h->nchar, h->E);
             if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
-            h->mfma_first_slot = ch.first_slot; h->mfma_first_row = ch.first_row; h->vec_second_row = ch.second_row;
-            if ((rc = dev_upload(h, &h->d_mops, reinterpret_cast<const int4 *>(ch.ops.data()), ch.ops.size()))) return rc;
-        } else if (kind == 3) {
-            const int T = (h->k + 15) / 16, R = 4 * T, kk4 = (h->k + 3) / 4;
-            std::vector<double> rwd((size_t)4 * R, 0.0);
-            for (int i = 0; i < h->k; i++) rwd[(size_t)(i & 3) * R + (i >> 2)] = h->root_w[i];
-            if ((rc = dev_upload(h, &h->d_root_wd, rwd.data(), rwd.size()))) return rc;
-            if ((rc = dev_reserve(h, &h->d_frag, &h->frag_cap, (size_t)h->C * nops * T * kk4 * 64))) return rc;
-            if ((rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * (ntips + 1) * h->nchar * 4 * R))) return rc;
-            /* MFMA program: observation ops name their staged code row and the next observation op */
-            PlkChain ch;
-            plk_chain_build(h->N, h->pg, 0, nullptr, nullptr, nullptr, nullptr, ch);
-            const std::string bad = plk_chain_check(h->N, h->pg, ch, 0, INT_MAX, 0, 0, 0, MF_SITES,
-                                                    (size_t)h->obs_nodes.size() * MF_SITES);
-            if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
-            h->mfma_first_slot = ch.first_slot; h->mfma_first_row = ch.first_row;
-            h->mfma_first_mv = -1;
-            for (size_t pc = 0; pc < h->pg.ops.size() && h->mfma_first_mv < 0; pc++) if ((h->pg.ops[pc].x & 0xff) == OP_MATVEC) h->mfma_first_mv = (int)pc;
-            if ((rc = dev_upload(h, &h->d_mops, reinterpret_cast<const int4 *>(ch.ops.data()), ch.ops.size()))) return rc;
+            if ((rc = upload_pair_table_lists(h)) ||
+                (rc = dev_upload(h, &h->d_mops, reinterpret_cast<const int4 *>(h->vpt.ops.data()), h->vpt.ops.size())) ||
+                (rc = dev_upload(h, &h->d_op_edge, h->vpt.op_edge.data(), h->vpt.op_edge.size())) ||
+                (rc = dev_reserve(h, &h->d_PS, &h->ps_cap, (size_t)h->C * h->vpt.ops.size() * h->K * h->K)) ||
+                (rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * h->fpt.units * h->nchar * h->K))) return rc;
+            p.pair_tables = true; p.npairs = h->fpt.npairs;
+            return PLK_OK;
         }
     }
-    h->fmt_kind = kind;
+    if ((rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * (h->tip_edge.size() + 1) * h->nchar * h->K))) return rc;
+    /* vector program: observation ops chained two ahead (value of the next op, code of the one after) */
+    PlkChain ch;
+    plk_chain_build(h->N, h->pg, 3, h->indices.data(), nullptr, nullptr, nullptr, ch);
+    const std::string bad = plk_chain_check(h->N, h->pg, ch, 3, INT_MAX, 0, 0, 0, 0, 0);
+    if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
+    h->mfma_first_slot = ch.first_slot; h->mfma_first_row = ch.first_row; h->vec_second_row = ch.second_row;
+    return dev_upload(h, &h->d_mops, reinterpret_cast<const int4 *>(ch.ops.data()), ch.ops.size());
+}
+
+/* 9 <= k <= 64 with compact codes: fp64 matrix-core kernel (plk_mfma.h) */
+static int upload_formats_mfma(plk_engine *h, LlPlan &p)
+{
+    int rc;
+    if ((rc = upload_formats_generic(h, p))) return rc;
+    const int nops = (int)h->ops.size(), ntips = (int)h->tip_edge.size();
+    const int T = (h->k + 15) / 16, R = 4 * T, kk4 = (h->k + 3) / 4;
+    p.family = LL_MFMA;
+    p.mfma_T = T;
+    /* two 16-site groups per wave (PLK_OPT_MFMA_NS2) when the staged code rows of 128 sites fit the LDS */
+    p.mfma_ns2 = h->opt_mfma_ns2 == 1 && T >= 3 && mfma_ll_lds_bytes(h, 2 * MF_SITES) <= PLK_LDS_LIMIT;
+    p.block = MF_BLOCK; p.wg_sites = p.mfma_ns2 ? 2 * MF_SITES : MF_SITES;
+    p.lds = mfma_ll_lds_bytes(h, p.wg_sites);
+    std::vector<double> rwd((size_t)4 * R, 0.0);
+    for (int i = 0; i < h->k; i++) rwd[(size_t)(i & 3) * R + (i >> 2)] = h->root_w[i];
+    if ((rc = dev_upload(h, &h->d_root_wd, rwd.data(), rwd.size()))) return rc;
+    if ((rc = dev_reserve(h, &h->d_frag, &h->frag_cap, (size_t)h->C * nops * T * kk4 * 64))) return rc;
+    if ((rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * (ntips + 1) * h->nchar * 4 * R))) return rc;
+    /* MFMA program: observation ops name their staged code row and the next observation op */
+    PlkChain ch;
+    plk_chain_build(h->N, h->pg, 0, nullptr, nullptr, nullptr, nullptr, ch);
+    const std::string bad = plk_chain_check(h->N, h->pg, ch, 0, INT_MAX, 0, 0, 0, MF_SITES, (size_t)h->obs_nodes.size() * MF_SITES);
+    if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
+    h->mfma_first_slot = ch.first_slot; h->mfma_first_row = ch.first_row;
+    h->mfma_first_mv = -1;
+    for (size_t pc = 0; pc < h->pg.ops.size() && h->mfma_first_mv < 0; pc++) if ((h->pg.ops[pc].x & 0xff) == OP_MATVEC) h->mfma_first_mv = (int)pc;
+    return dev_upload(h, &h->d_mops, reinterpret_cast<const int4 *>(ch.ops.data()), ch.ops.size());
+}
+
+/* executed fp64 work per site (PLK_INFO_LL_EXEC_FLOPS): products and elementwise multiplies of the program the plan runs */
+static long ll_exec_flops(const plk_engine *h, const LlPlan &p)
+{
+    long nprod = 0, nmul = 0;
+    if (p.family == LL_VEC && p.pair_tables) {
+        for (const PlkFusedPT::VOp &o : h->fpt.vops) { if (o.code == OP_MATVEC) nprod++; if (o.code == OP_TIP_MUL || o.code == OP_POPMUL) nmul++; }
+    } else if (p.family == LL_FUSED4 && p.pair_tables) {
+        nprod = (long)h->fpt.mat_edge.size();
+        for (unsigned w : h->fpt.words) {
+            const unsigned hx = w & 31;
+            if (hx == OP_TIP_MUL || hx == PLK_WORD_TIPMUL_NOWAIT || hx == PLK_WORD_MATVEC_TIPMUL) nmul++;
+            if ((hx >= 16 && hx < 20) || hx >= 28 || (hx >= PLK_WORD_SET_POPMUL && hx < PLK_WORD_SET_POPMUL + 4)) nmul++;
+        }
+    } else {
+        for (const plk_op2 &o : h->ops) {
+            const int code = o.x & 0xff;
+            if (code == OP_MATVEC) nprod++;
+            /* leaf edges: a table row multiplied in (fused, vector and matrix-core kernels) or a full product (generic) */
+            if (code == OP_TIP_MUL || code == OP_NODE_MUL || code == OP_POPMUL) nmul++;
+            if ((code == OP_TIP_SET || code == OP_TIP_MUL) && p.family == LL_GENERIC) { nprod++; if (code == OP_TIP_MUL) nmul++; }
+        }
+    }
+    const long kp = p.family == LL_MFMA ? (h->k + 15) / 16 * 16 : h->k;
+    return (long)h->C * (nprod * (2 * kp * kp - kp) + nmul * h->k);
+}
+
+/* The ll plan of the engine's state and the device formats it names: chosen, replayed on the host and uploaded when the
+ * program or an option the plan reads changes, not per evaluation.  On an error the formats stay dirty, so the next
+ * evaluation fails the same way. */
+static int upload_formats(plk_engine *h)
+{
+    int rc;
+    h->fmt_dirty = true;
+    std::vector<int> te = h->tip_edge;
+    te.push_back(-1);                                /* pseudo slot: the raw definitions (internal nodes with data) */
+    if ((rc = dev_upload(h, &h->d_tip_edge, te.data(), te.size()))) return rc;
+    if ((rc = dev_upload(h, &h->d_obs_nodes, h->obs_nodes.data(), h->obs_nodes.size()))) return rc;
+    LlPlan p;
+    if (!h->opt_force_generic && h->k == 4 && h->pat_mode == 1 && (rc = upload_formats_fused4(h, p))) return rc;
+    if (p.family != LL_FUSED4) {
+        /* trees with so many observed nodes that their staged code rows do not fit in LDS take the generic kernel */
+        if (use_vec(h)) rc = upload_formats_vec(h, p);
+        else if (use_mfma(h) && mfma_ll_lds_bytes(h, MF_SITES) <= PLK_LDS_LIMIT) rc = upload_formats_mfma(h, p);
+        else rc = upload_formats_generic(h, p);
+        if (rc) return rc;
+    }
+    p.info_exec_flops = ll_exec_flops(h, p);
+    h->plan = p;
     h->fmt_dirty = false;
     h->tables_dirty = true;
     return PLK_OK;
 }
 
-/* P-dependent tables of kernel kind, from the current P (used when K1 ran without writing them itself) */
-static int build_tables(plk_engine *h, long kind)
+/* P-dependent tables of the plan's kernel family, from the current P (used when K1 ran without writing them itself) */
+static int build_tables(plk_engine *h)
 {
+    const LlPlan &p = h->plan;
     const int nops = (int)h->ops.size(), ntips = (int)h->tip_edge.size(), K = h->K, C = h->C;
-    if (kind == 1) {
-        /* the fused formats are written by K1 itself (ExpmPost) */
-        return run_expm(h, true);
-    } else {
-        if (kind == 4 && h->vec_pt) {
-            const int nv = (int)h->vpt.ops.size(), ntab = (int)h->fpt.tab_unit.size();
-            hipLaunchKernelGGL(k_build_stream, dim3(nv, C), dim3(K * K >= 256 ? 256 : 64), 0, h->stream,
-                               h->k, K, h->E, nv, h->d_op_edge, h->d_P, h->d_PS);
-            hipLaunchKernelGGL(k_build_tables_pt_vec, dim3(ntab, C, 8), dim3(256), (size_t)4 * h->nchar * h->k * sizeof(double), h->stream,
-                               h->k, K, h->E, ntab, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
-            HIPCHK(h, hipGetLastError());
-            h->tables_dirty = false;
-            return PLK_OK;
-        }
-        if (nops > 0)
-            hipLaunchKernelGGL(k_build_stream, dim3(nops, C), dim3(K * K >= 256 ? 256 : 64), 0, h->stream,
-                               h->k, K, h->E, nops, h->d_op_edge, h->d_P, h->d_PS);
-        if (kind == 4) {
-            hipLaunchKernelGGL(k_build_tip_vec, dim3(ntips + 1, C), dim3(256), 0, h->stream,
-                               h->k, K, h->E, ntips, h->nchar, h->d_tip_edge, h->d_Pdd, h->d_defs, h->d_tip);
-        } else if (kind == 3) {
-            const int T = (h->k + 15) / 16, R = 4 * T, kk4 = (h->k + 3) / 4;
-            hipLaunchKernelGGL(k_build_frag, dim3(nops, C), dim3(256), 0, h->stream,
-                               h->k, T, kk4, h->E, nops, h->d_op_edge, h->d_P, h->d_frag);
-            hipLaunchKernelGGL(k_build_tip_dist, dim3(ntips + 1, C), dim3(256), 0, h->stream,
-                               h->k, R, h->E, ntips, h->nchar, h->d_tip_edge, h->d_Pdd, h->d_defs, h->K, h->d_tip);
-        }
+    if (p.family == LL_FUSED4) return run_expm(h, true);      /* the fused formats are written by K1 itself (ExpmPost) */
+    if (p.family == LL_VEC && p.pair_tables) {
+        const int nv = (int)h->vpt.ops.size(), ntab = (int)h->fpt.tab_unit.size();
+        hipLaunchKernelGGL(k_build_stream, dim3(nv, C), dim3(K * K >= 256 ? 256 : 64), 0, h->stream,
+                           h->k, K, h->E, nv, h->d_op_edge, h->d_P, h->d_PS);
+        hipLaunchKernelGGL(k_build_tables_pt_vec, dim3(ntab, C, 8), dim3(256), (size_t)4 * h->nchar * h->k * sizeof(double), h->stream,
+                           h->k, K, h->E, ntab, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
+        HIPCHK(h, hipGetLastError());
+        h->tables_dirty = false;
+        return PLK_OK;
+    }
+    if (nops > 0)
+        hipLaunchKernelGGL(k_build_stream, dim3(nops, C), dim3(K * K >= 256 ? 256 : 64), 0, h->stream,
+                           h->k, K, h->E, nops, h->d_op_edge, h->d_P, h->d_PS);
+    if (p.family == LL_VEC) {
+        hipLaunchKernelGGL(k_build_tip_vec, dim3(ntips + 1, C), dim3(256), 0, h->stream,
+                           h->k, K, h->E, ntips, h->nchar, h->d_tip_edge, h->d_Pdd, h->d_defs, h->d_tip);
+    } else if (p.family == LL_MFMA) {
+        const int T = p.mfma_T, R = 4 * T, kk4 = (h->k + 3) / 4;
+        hipLaunchKernelGGL(k_build_frag, dim3(nops, C), dim3(256), 0, h->stream,
+                           h->k, T, kk4, h->E, nops, h->d_op_edge, h->d_P, h->d_frag);
+        hipLaunchKernelGGL(k_build_tip_dist, dim3(ntips + 1, C), dim3(256), 0, h->stream,
+                           h->k, R, h->E, ntips, h->nchar, h->d_tip_edge, h->d_Pdd, h->d_defs, h->K, h->d_tip);
     }
     HIPCHK(h, hipGetLastError());
     h->tables_dirty = false;
     return PLK_OK;
-}
-
-/* the window of three stack slots that takes most pushes (register stack of the vector kernels) */
-static int vec_reg_window(const plk_engine *h)
-{
-    std::vector<long> per_slot(std::max(h->slots_needed, 1), 0);
-    for (const plk_op2 &o : h->ops) if ((o.x & 0xff) == OP_PUSH && o.y < (int)per_slot.size()) per_slot[o.y]++;
-    long best = -1;
-    int lo_best = 0;
-    for (int lo = 0; lo + 3 <= std::max(h->slots_needed, 3); lo++) {
-        long cnt = 0;
-        for (int q = lo; q < lo + 3 && q < (int)per_slot.size(); q++) cnt += per_slot[q];
-        if (cnt > best) { best = cnt; lo_best = lo; }
-    }
-    return lo_best;
 }
 
 template <int D, int NS>
@@ -2165,6 +2171,156 @@ static void launch_generic(plk_engine *h, const GenArgs &a, unsigned grid)
 
 #define PLK_PARTIAL_OFF 72      /* d_partial: [0] the sum, [4, 68) second-stage inputs, [72, ...) one partial per workgroup */
 
+/* room for n partial sums behind PLK_PARTIAL_OFF when the sum is wanted: where the kernel writes them, or null */
+static int reserve_partials(plk_engine *h, bool want_sum, unsigned n, dd **partial)
+{
+    *partial = nullptr;
+    if (!want_sum) return PLK_OK;
+    const int rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)n + PLK_PARTIAL_OFF);
+    if (rc == PLK_OK) *partial = h->d_partial + PLK_PARTIAL_OFF;
+    return rc;
+}
+
+/* The launch functions, one per kernel family: fill the argument struct, reserve the partial sums (*npartials of them),
+ * launch on the engine's stream. */
+static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool want_sum, unsigned *npartials)
+{
+    const PlkK4Choice &c = p.k4;
+    const long S = h->S;
+    const int ntiles = (int)((S + p.wg_sites - 1) / p.wg_sites);
+    /* C++ and assembly interpreters: a workgroup per tile.  Pair-table interpreters: one workgroup per CU (two of 512
+     * sites), every workgroup walks the tiles with a grid stride.  Streamed codes: 768 lanes per CU, a wave per 128-site
+     * unit.  One partial sum per tile (per wave of the streamed form). */
+    unsigned grid = (unsigned)ntiles;
+    if (c.variant == PLK_K4_V4S) grid = (unsigned)std::min<long>(((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT + 11) / 12, h->num_cus);
+    else if (c.variant == PLK_K4_V4 || c.variant == PLK_K4_ASM_PT) grid = (unsigned)std::min(ntiles, c.tile == 512 ? 2 * h->num_cus : h->num_cus);
+    *npartials = c.variant == PLK_K4_V4S ? grid * 12 : (unsigned)ntiles;
+    int rc;
+    FusedArgs a;
+    if ((rc = reserve_partials(h, want_sum, *npartials, &a.partial))) return rc;
+    a.S = S; a.Spad = h->Spad; a.C = h->C; a.nops = (int)h->ops.size(); a.nmat = (int)h->mat_edge.size();
+    a.ntips = (int)h->tip_edge.size() + 1; a.nchar = h->nchar; a.nobs = (int)h->obs_nodes.size();
+    a.ops = h->d_fops; a.PS = h->d_PS; a.tip = h->d_tip;
+    a.codes = h->d_codes; a.obs_nodes = h->d_obs_nodes; a.defs = h->d_defs;
+    a.cat_prior = h->d_cat_prior; a.root_w = h->d_root_w; a.w = h->d_w;
+    a.site_ll = d_out;
+    a.root_mode = h->root_mode; a.first_row = h->fu.first_row;
+    if (p.pair_tables) {
+        const PlkFusedPT &f = h->fpt;
+        FusedPTArgs pa;
+        pa.f = a;
+        pa.f.nmat = (int)f.mat_edge.size(); pa.f.ntips = f.units; pa.f.nobs = (int)f.row_node.size();
+        pa.words = h->d_words_pt; pa.row_nodes = h->d_row_nodes; pa.nwords = (int)(c.variant == PLK_K4_ASM_PT ? f.words.size() : h->fv4.words.size());
+        pa.first_unit = f.first_unit; pa.first_row = f.first_row; pa.second_row = f.second_row; pa.ntiles = ntiles;
+        pa.warm = c.warm;
+        if (c.variant == PLK_K4_V4S) {
+            FusedV4SArgs sa;
+            sa.pt = pa;
+            sa.pt.nwords = (int)h->fv4s.stride;
+            sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
+            sa.sync = c.sync;
+            hipLaunchKernelGGL(k_ll_fused4_v4s<768>, dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+        } else if (c.variant == PLK_K4_V4) {
+            FusedV4Args va;
+            va.pt = pa; va.first_y = h->fv4.first_y; va.first_z = h->fv4.first_z; va.second_z = h->fv4.second_z;
+            if (c.tile == 1536) hipLaunchKernelGGL(k_ll_fused4_v4<768>, dim3(grid), dim3(p.block), p.lds, h->stream, va);
+            else hipLaunchKernelGGL(k_ll_fused4_v4<512>, dim3(grid), dim3(p.block), p.lds, h->stream, va);
+        } else if (c.tile == 1024) hipLaunchKernelGGL(k_ll_fused4_asm_pt<1024>, dim3(grid), dim3(p.block), p.lds, h->stream, pa);
+        else hipLaunchKernelGGL(k_ll_fused4_asm_pt<512>, dim3(grid), dim3(p.block), p.lds, h->stream, pa);
+        return PLK_OK;
+    }
+    if (c.variant == PLK_K4_ASM) {
+        FusedAsmArgs aa;
+        aa.f = a; aa.words = h->d_words;
+        aa.first_tip = h->fu.asm_first_tip; aa.first_row = h->fu.asm_first_row; aa.second_row = h->fu.asm_second_row;
+        aa.pack4 = c.pack4;
+        if (c.D == 4) hipLaunchKernelGGL(k_ll_fused4_asm<4>, dim3(grid), dim3(p.block), p.lds, h->stream, aa);
+        else hipLaunchKernelGGL(k_ll_fused4_asm<8>, dim3(grid), dim3(p.block), p.lds, h->stream, aa);
+        return PLK_OK;
+    }
+    if (c.NS == 2) {
+        if (c.D == 4) launch_fused<4, 2>(h, a, grid, p.lds);
+        else launch_fused<8, 2>(h, a, grid, p.lds);
+    } else {
+        if (c.D == 4) launch_fused<4, 1>(h, a, grid, p.lds);
+        else if (c.D == 8) launch_fused<8, 1>(h, a, grid, p.lds);
+        else launch_fused<16, 1>(h, a, grid, p.lds);
+    }
+    return PLK_OK;
+}
+
+static int launch_ll_vec(plk_engine *h, const LlPlan &p, double *d_out, bool want_sum, unsigned *npartials)
+{
+    const long S = h->S;
+    const int K = h->K;
+    const unsigned grid = (unsigned)((S + p.wg_sites - 1) / p.wg_sites);
+    *npartials = grid;
+    int rc;
+    VecArgs a;
+    if ((rc = reserve_partials(h, want_sum, grid, &a.partial))) return rc;
+    if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)std::max(h->slots_needed, 1) * K * S))) return rc;
+    a.S = S; a.Spad = h->Spad; a.k = h->k; a.C = h->C; a.nops = (int)h->ops.size(); a.ntips = (int)h->tip_edge.size(); a.nchar = h->nchar;
+    a.root_mode = h->root_mode; a.ops = h->d_mops; a.PS = h->d_PS; a.tip = h->d_tip; a.codes = h->d_codes;
+    a.obs_nodes = h->d_obs_nodes; a.first_slot = h->mfma_first_slot; a.first_row = h->mfma_first_row; a.second_row = h->vec_second_row;
+    a.obs_nodes2 = nullptr; a.units = 0;
+    if (p.pair_tables) {
+        const int nrows = (int)h->fpt.row_node.size();
+        a.nops = (int)h->vpt.ops.size(); a.obs_nodes = h->d_row_nodes; a.obs_nodes2 = h->d_row_nodes + nrows; a.units = h->fpt.units;
+        a.first_slot = 0; a.first_row = h->vpt.first_row;
+    }
+    a.cat_prior = h->d_cat_prior; a.root_w = h->d_root_w; a.w = h->d_w; a.slots = h->d_slots; a.site_ll = d_out;
+    a.reg_lo = p.vec_reg_lo;
+    if (p.vec_rs && K == 16) hipLaunchKernelGGL((k_ll_vec_rs<16, 3>), dim3(grid), dim3(p.block), 0, h->stream, a);
+    else if (p.vec_rs) hipLaunchKernelGGL((k_ll_vec_rs<20, 3>), dim3(grid), dim3(p.block), 0, h->stream, a);
+    else if (K == 16) hipLaunchKernelGGL(k_ll_vec<16>, dim3(grid), dim3(p.block), 0, h->stream, a);
+    else if (K == 20) hipLaunchKernelGGL(k_ll_vec<20>, dim3(grid), dim3(p.block), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_ll_vec<32>, dim3(grid), dim3(p.block), 0, h->stream, a);
+    return PLK_OK;
+}
+
+static int launch_ll_mfma(plk_engine *h, const LlPlan &p, double *d_out, bool want_sum, unsigned *npartials)
+{
+    const long S = h->S;
+    const int T = p.mfma_T, R = 4 * T, kk4 = (h->k + 3) / 4;
+    const unsigned grid = (unsigned)((S + p.wg_sites - 1) / p.wg_sites);
+    *npartials = grid;
+    int rc;
+    MfmaArgs a;
+    if ((rc = reserve_partials(h, want_sum, grid, &a.partial))) return rc;
+    const long slot_stride = (long)grid * p.wg_sites * 4;
+    if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)std::max(h->slots_needed, 1) * R * slot_stride))) return rc;
+    a.S = S; a.Spad = h->Spad; a.k = h->k; a.kk4 = kk4; a.C = h->C; a.nops = (int)h->ops.size(); a.ntips = (int)h->tip_edge.size();
+    a.nchar = h->nchar; a.root_mode = h->root_mode; a.ops = h->d_mops; a.frag = h->d_frag; a.tip = h->d_tip;
+    a.obs_nodes = h->d_obs_nodes; a.nobs = (int)h->obs_nodes.size();
+    a.first_slot = h->mfma_first_slot; a.first_row = h->mfma_first_row; a.first_mv = h->mfma_first_mv;
+    a.codes = h->d_codes; a.cat_prior = h->d_cat_prior; a.root_wd = h->d_root_wd; a.w = h->d_w;
+    a.slots = h->d_slots; a.slot_stride = slot_stride; a.site_ll = d_out;
+    if (p.mfma_ns2 && T == 3) hipLaunchKernelGGL(k_ll_mfma_ns2<3>, dim3(grid), dim3(p.block), p.lds, h->stream, a);
+    else if (p.mfma_ns2) hipLaunchKernelGGL(k_ll_mfma_ns2<4>, dim3(grid), dim3(p.block), p.lds, h->stream, a);
+    else if (T == 1) hipLaunchKernelGGL(k_ll_mfma<1>, dim3(grid), dim3(p.block), p.lds, h->stream, a);
+    else if (T == 2) hipLaunchKernelGGL(k_ll_mfma<2>, dim3(grid), dim3(p.block), p.lds, h->stream, a);
+    else if (T == 3) hipLaunchKernelGGL(k_ll_mfma_occ4<3>, dim3(grid), dim3(p.block), p.lds, h->stream, a);
+    else hipLaunchKernelGGL(k_ll_mfma_occ4<4>, dim3(grid), dim3(p.block), p.lds, h->stream, a);
+    return PLK_OK;
+}
+
+static int launch_ll_generic(plk_engine *h, const LlPlan &p, double *d_out, bool want_sum, unsigned *npartials)
+{
+    const long S = h->S;
+    const unsigned grid = (unsigned)((S + p.wg_sites - 1) / p.wg_sites);
+    *npartials = grid;
+    int rc;
+    GenArgs a;
+    if ((rc = reserve_partials(h, want_sum, grid, &a.partial))) return rc;
+    if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)std::max(h->slots_needed, 1) * h->k * S))) return rc;
+    a.S = S; a.Spad = h->Spad; a.k = h->k; a.C = h->C; a.nops = (int)h->ops.size(); a.nchar = h->nchar;
+    a.pat_mode = h->pat_mode; a.root_mode = h->root_mode; a.ops = h->d_ops; a.PS = h->d_PS;
+    a.codes = h->d_codes; a.defs = h->d_defs; a.B = h->d_B; a.cat_prior = h->d_cat_prior;
+    a.root_w = h->d_root_w; a.w = h->d_w; a.slots = h->d_slots; a.site_ll = d_out;
+    dispatch_K(h->K, [&](auto Kc) { launch_generic<decltype(Kc)::value>(h, a, grid); });
+    return PLK_OK;
+}
+
 /* sum_dev != null: the {hi, lo} sum is left in device memory (2 doubles) and nothing is copied or waited for */
 static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_out, double *sum_dev, bool async)
 {
@@ -2172,14 +2328,12 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    /* the plan with its formats, K1, the P-dependent tables */
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
-    const bool fused = use_fused(h);
-    /* trees with so many observed nodes that their staged code rows do not fit in LDS take the generic kernel */
-    const bool vec = !fused && use_vec(h), mfma = !fused && !vec && use_mfma(h) && mfma_ll_lds_bytes(h) <= PLK_LDS_LIMIT;
-    const long kind = fused ? 1 : (vec ? 4 : (mfma ? 3 : 2));
-    if (h->fmt_dirty || kind != h->fmt_kind) { if ((rc = upload_formats(h, kind))) return rc; }
+    if (h->fmt_dirty) { if ((rc = upload_formats(h))) return rc; }
     if (h->model_dirty) { if ((rc = run_expm(h, true, false))) return rc; }      /* K1 without dP; for k = 4 it writes the stream and tip tables too */
-    if (h->tables_dirty) { if ((rc = build_tables(h, kind))) return rc; }
+    if (h->tables_dirty) { if ((rc = build_tables(h))) return rc; }
+    const LlPlan &p = h->plan;
     const bool want_sum = sum_out || sum_dev;
     const long S = h->S;
     double *d_out = nullptr;
@@ -2187,215 +2341,31 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
         if (where == PLK_DEVICE) d_out = site_ll_out;
         else { if ((rc = dev_reserve(h, &h->d_site_ll, &h->site_ll_cap, (size_t)S))) return rc; d_out = h->d_site_ll; }
     }
-    unsigned grid;
     const int evi = h->evk_next;
     h->evk_next = (evi + 1) & 63;
     if ((rc = evk_resolve(h, evi))) return rc;           /* only waits when 64 evaluations are queued */
     HIPCHK(h, hipEventRecord(h->evk[evi][0], h->stream));
-    h->info_ll_variant = 0; h->info_ll_form = 0;
-    if (fused) {
-        const int NS = fused_sites_per_lane(h);
-        grid = (unsigned)((S + PLK_TILE * NS - 1) / (PLK_TILE * NS));
-        if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)grid + PLK_PARTIAL_OFF))) return rc; }
-        FusedArgs a;
-        a.S = S; a.Spad = h->Spad; a.C = h->C; a.nops = (int)h->ops.size(); a.nmat = (int)h->mat_edge.size();
-        a.ntips = (int)h->tip_edge.size() + 1; a.nchar = h->nchar; a.nobs = (int)h->obs_nodes.size();
-        a.ops = h->d_fops; a.PS = h->d_PS; a.tip = h->d_tip;
-        a.codes = h->d_codes; a.obs_nodes = h->d_obs_nodes; a.defs = h->d_defs;
-        a.cat_prior = h->d_cat_prior; a.root_w = h->d_root_w; a.w = h->d_w;
-        a.site_ll = d_out; a.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
-        a.root_mode = h->root_mode; a.first_row = h->fu.first_row;
-        const size_t lds = plk_fused_lds_bytes(h->pg, h->nchar, PLK_TILE * NS);
-        const bool use_asm = fused_asm_fits(h);
-        const int D = h->slots_needed <= 4 ? 4 : (h->slots_needed <= 8 ? 8 : 16);
-        if (h->fmt_pt) {
-            /* pair-table interpreter: one 1024-site workgroup per CU (or two of 512), every workgroup walks the tiles with a grid stride */
-            const PlkFusedPT &f = h->fpt;
-            const int tile = h->pt_tile_sites;
-            const int ntiles = (int)((S + tile - 1) / tile);
-            int ntiles_out = ntiles;
-            if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)ntiles + PLK_PARTIAL_OFF))) return rc; }
-            const bool strm = h->pt_kind == 2 && h->pt_stream;
-            const size_t lds_pt = strm ? plk_fused_v4s_lds_bytes(f, h->nchar, h->C) : plk_fused_pt_lds_bytes(f, h->nchar, tile);
-            /* the 32-bit program is replayed whatever the form (streamed: no code rows in LDS; its fields are the chain the
-             * streamed words are checked against) */
-            std::string bad = strm ? plk_fused_check_pt(h->N, h->indptr.data(), h->indices.data(), h->pg, f, h->nchar, 1, 0, true, false)
-                                   : plk_fused_check_pt(h->N, h->indptr.data(), h->indices.data(), h->pg, f, h->nchar, tile, lds_pt, h->pt_kind == 2);
-            if (bad.empty() && strm) bad = plk_fused_check_v4s(f, h->fv4s, h->nchar, h->C, h->v4_tip_base, lds_pt);
-            else if (bad.empty() && h->pt_kind == 2) bad = plk_fused_check_v4(f, h->fv4, h->nchar, tile, h->v4_tip_base, lds_pt);
-            if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
-            FusedPTArgs pa;
-            pa.f = a;
-            pa.f.nmat = (int)f.mat_edge.size(); pa.f.ntips = f.units; pa.f.nobs = (int)f.row_node.size();
-            pa.f.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
-            pa.words = h->d_words_pt; pa.row_nodes = h->d_row_nodes; pa.nwords = (int)(h->pt_kind == 2 ? h->fv4.words.size() : f.words.size());
-            pa.first_unit = f.first_unit; pa.first_row = f.first_row; pa.second_row = f.second_row; pa.ntiles = ntiles;
-            pa.warm = (h->opt_pair_tables & 8) ? 0 : 1;      /* + 8: without the scalar-cache warm-up (measurements) */
-            h->info_ll_variant = 5;
-            if (strm) {
-                /* streamed codes: 768 lanes per CU, a wave per 128-site unit, one partial sum per wave */
-                const long nunits = (S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
-                grid = (unsigned)std::min<long>((nunits + 11) / 12, h->num_cus);
-                ntiles_out = (int)grid * 12;
-                if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)ntiles_out + PLK_PARTIAL_OFF))) return rc; }
-                FusedV4SArgs sa;
-                sa.pt = pa; sa.pt.f.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
-                sa.pt.nwords = (int)h->fv4s.stride;
-                sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
-                /* the waves of a workgroup meet before every category (+ 16: before every unit only, + 32: never; measurements,
-                 * DESIGN.md section 4) */
-                sa.sync = (h->opt_pair_tables & 32) ? 0 : (h->opt_pair_tables & 16) ? 1 : 2;
-                hipLaunchKernelGGL(k_ll_fused4_v4s<768>, dim3(grid), dim3(768), lds_pt, h->stream, sa);
-                h->info_ll_variant = 6; h->info_ll_form = 1;
-            } else if (h->pt_kind == 2) {
-                /* two sites per lane: one workgroup of tile / 2 lanes per CU */
-                FusedV4Args va;
-                va.pt = pa; va.first_y = h->fv4.first_y; va.first_z = h->fv4.first_z; va.second_z = h->fv4.second_z;
-                grid = (unsigned)std::min(ntiles, h->num_cus);
-                if (tile == 1536) hipLaunchKernelGGL(k_ll_fused4_v4<768>, dim3(grid), dim3(768), lds_pt, h->stream, va);
-                else hipLaunchKernelGGL(k_ll_fused4_v4<512>, dim3(grid), dim3(512), lds_pt, h->stream, va);
-                h->info_ll_variant = 6;
-            } else if (tile == 1024) {
-                grid = (unsigned)std::min(ntiles, h->num_cus);
-                hipLaunchKernelGGL(k_ll_fused4_asm_pt<1024>, dim3(grid), dim3(1024), lds_pt, h->stream, pa);
-            } else {
-                grid = (unsigned)std::min(ntiles, 2 * h->num_cus);
-                hipLaunchKernelGGL(k_ll_fused4_asm_pt<512>, dim3(grid), dim3(512), lds_pt, h->stream, pa);
-            }
-            grid = (unsigned)ntiles_out;                  /* one partial sum per tile (per wave of the streamed form) */
-        } else if (use_asm) {
-            FusedAsmArgs aa;
-            aa.f = a; aa.words = h->d_words;
-            aa.first_tip = h->fu.asm_first_tip; aa.first_row = h->fu.asm_first_row; aa.second_row = h->fu.asm_second_row;
-            aa.pack4 = h->nchar <= 16 ? 1 : 0;
-            const size_t lds_asm = plk_fused_lds_bytes(h->pg, h->nchar, aa.pack4 ? PLK_TILE / 2 : PLK_TILE);
-            /* replay the interpreter's fetches and LDS addresses on the host before launching (plk_program.h) */
-            const std::string bad = plk_fused_check_asm(h->N, h->pg, h->fu, h->nchar, D, aa.pack4, lds_asm);
-            if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
-            h->info_ll_variant = 1;
-            if (D == 4) hipLaunchKernelGGL(k_ll_fused4_asm<4>, dim3(grid), dim3(PLK_TILE), lds_asm, h->stream, aa);
-            else hipLaunchKernelGGL(k_ll_fused4_asm<8>, dim3(grid), dim3(PLK_TILE), lds_asm, h->stream, aa);
-        } else {
-            h->info_ll_variant = 3;
-            const std::string bad = plk_fused_check_cpp(h->N, h->pg, h->fu, h->nchar, NS == 2 && D == 16 ? 8 : D, NS, lds);
-            if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
-            if (NS == 2) {
-                if (D == 4) launch_fused<4, 2>(h, a, grid, lds);
-                else launch_fused<8, 2>(h, a, grid, lds);
-            } else {
-                if (D == 4) launch_fused<4, 1>(h, a, grid, lds);
-                else if (D == 8) launch_fused<8, 1>(h, a, grid, lds);
-                else launch_fused<16, 1>(h, a, grid, lds);
-            }
-        }
-        h->info_ll_kernel = 1;
-    } else if (vec) {
-        /* 9 <= k <= 32 with compact codes: register-resident vector kernel (plk_vec.h) */
-        const int K = h->K, nops = (int)h->ops.size(), ntips = (int)h->tip_edge.size();
-        grid = (unsigned)((S + VEC_BLOCK - 1) / VEC_BLOCK);
-        if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)grid + PLK_PARTIAL_OFF))) return rc; }
-        const int nslots = std::max(h->slots_needed, 1);
-        if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)nslots * K * S))) return rc;
-        VecArgs a;
-        a.S = S; a.Spad = h->Spad; a.k = h->k; a.C = h->C; a.nops = nops; a.ntips = ntips; a.nchar = h->nchar;
-        a.root_mode = h->root_mode; a.ops = h->d_mops; a.PS = h->d_PS; a.tip = h->d_tip; a.codes = h->d_codes;
-        a.obs_nodes = h->d_obs_nodes; a.first_slot = h->mfma_first_slot; a.first_row = h->mfma_first_row; a.second_row = h->vec_second_row;
-        a.obs_nodes2 = nullptr; a.units = 0;
-        if (h->vec_pt) {
-            const int nrows = (int)h->fpt.row_node.size();
-            a.nops = (int)h->vpt.ops.size(); a.obs_nodes = h->d_row_nodes; a.obs_nodes2 = h->d_row_nodes + nrows; a.units = h->fpt.units;
-            a.first_slot = 0; a.first_row = h->vpt.first_row;
-        }
-        a.cat_prior = h->d_cat_prior; a.root_w = h->d_root_w; a.w = h->d_w; a.slots = h->d_slots; a.site_ll = d_out;
-        a.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
-        /* register stack (PLK_OPT_VEC_REG_STACK, default on): the window of three slots that takes most pushes */
-        const bool rs = h->opt_vec_reg_stack && K <= 20 && h->slots_needed >= 1;
-        a.reg_lo = rs ? vec_reg_window(h) : 0;
-        if (rs && K == 16) hipLaunchKernelGGL((k_ll_vec_rs<16, 3>), dim3(grid), dim3(VEC_BLOCK), 0, h->stream, a);
-        else if (rs) hipLaunchKernelGGL((k_ll_vec_rs<20, 3>), dim3(grid), dim3(VEC_BLOCK), 0, h->stream, a);
-        else if (K == 16) hipLaunchKernelGGL(k_ll_vec<16>, dim3(grid), dim3(VEC_BLOCK), 0, h->stream, a);
-        else if (K == 20) hipLaunchKernelGGL(k_ll_vec<20>, dim3(grid), dim3(VEC_BLOCK), 0, h->stream, a);
-        else hipLaunchKernelGGL(k_ll_vec<32>, dim3(grid), dim3(VEC_BLOCK), 0, h->stream, a);
-        h->info_ll_kernel = 4;
-    } else if (mfma) {
-        /* 9 <= k <= 64 with compact codes: fp64 matrix-core kernel (plk_mfma.h) */
-        const int T = (h->k + 15) / 16, R = 4 * T, kk4 = (h->k + 3) / 4;
-        const int nops = (int)h->ops.size(), ntips = (int)h->tip_edge.size();
-        /* two 16-site groups per wave (PLK_OPT_MFMA_NS2, default on) when the staged code rows of 128 sites fit the LDS */
-        const bool ns2 = h->opt_mfma_ns2 == 1 && T >= 3 && (size_t)T * kk4 * 64 * sizeof(double) + h->obs_nodes.size() * (size_t)(2 * MF_SITES) <= PLK_LDS_LIMIT;
-        const int wg_sites = ns2 ? 2 * MF_SITES : MF_SITES;
-        grid = (unsigned)((S + wg_sites - 1) / wg_sites);
-        if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)grid + PLK_PARTIAL_OFF))) return rc; }
-        const long slot_stride = (long)grid * wg_sites * 4;
-        const int nslots = std::max(h->slots_needed, 1);
-        if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)nslots * R * slot_stride))) return rc;
-        MfmaArgs a;
-        a.S = S; a.Spad = h->Spad; a.k = h->k; a.kk4 = kk4; a.C = h->C; a.nops = nops; a.ntips = ntips;
-        a.nchar = h->nchar; a.root_mode = h->root_mode; a.ops = h->d_mops; a.frag = h->d_frag; a.tip = h->d_tip;
-        a.obs_nodes = h->d_obs_nodes; a.nobs = (int)h->obs_nodes.size();
-        a.first_slot = h->mfma_first_slot; a.first_row = h->mfma_first_row; a.first_mv = h->mfma_first_mv;
-        a.codes = h->d_codes; a.cat_prior = h->d_cat_prior; a.root_wd = h->d_root_wd; a.w = h->d_w;
-        a.slots = h->d_slots; a.slot_stride = slot_stride; a.site_ll = d_out;
-        a.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
-        const size_t lds = ns2 ? (size_t)T * kk4 * 64 * sizeof(double) + h->obs_nodes.size() * (size_t)(2 * MF_SITES) : mfma_ll_lds_bytes(h);
-        if (false) {}
-        else if (ns2 && T == 3) hipLaunchKernelGGL(k_ll_mfma_ns2<3>, dim3(grid), dim3(MF_BLOCK), lds, h->stream, a);
-        else if (ns2) hipLaunchKernelGGL(k_ll_mfma_ns2<4>, dim3(grid), dim3(MF_BLOCK), lds, h->stream, a);
-        else if (T == 1) hipLaunchKernelGGL(k_ll_mfma<1>, dim3(grid), dim3(MF_BLOCK), lds, h->stream, a);
-        else if (T == 2) hipLaunchKernelGGL(k_ll_mfma<2>, dim3(grid), dim3(MF_BLOCK), lds, h->stream, a);
-        else if (T == 3) hipLaunchKernelGGL(k_ll_mfma_occ4<3>, dim3(grid), dim3(MF_BLOCK), lds, h->stream, a);
-        else hipLaunchKernelGGL(k_ll_mfma_occ4<4>, dim3(grid), dim3(MF_BLOCK), lds, h->stream, a);
-        h->info_ll_kernel = 3;
-    } else {
-        grid = (unsigned)((S + GEN_BLOCK - 1) / GEN_BLOCK);
-        if (want_sum) { if ((rc = dev_reserve(h, &h->d_partial, &h->partial_cap, (size_t)grid + PLK_PARTIAL_OFF))) return rc; }
-        const int nslots = std::max(h->slots_needed, 1);
-        if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)nslots * h->k * S))) return rc;
-        GenArgs a;
-        a.S = S; a.Spad = h->Spad; a.k = h->k; a.C = h->C; a.nops = (int)h->ops.size(); a.nchar = h->nchar;
-        a.pat_mode = h->pat_mode; a.root_mode = h->root_mode; a.ops = h->d_ops; a.PS = h->d_PS;
-        a.codes = h->d_codes; a.defs = h->d_defs; a.B = h->d_B; a.cat_prior = h->d_cat_prior;
-        a.root_w = h->d_root_w; a.w = h->d_w; a.slots = h->d_slots; a.site_ll = d_out;
-        a.partial = want_sum ? h->d_partial + PLK_PARTIAL_OFF : nullptr;
-        dispatch_K(h->K, [&](auto Kc) { launch_generic<decltype(Kc)::value>(h, a, grid); });
-        h->info_ll_kernel = 2;
+    unsigned npartials = 0;
+    switch (p.family) {
+    case LL_FUSED4: rc = launch_ll_fused4(h, p, d_out, want_sum, &npartials); break;
+    case LL_VEC: rc = launch_ll_vec(h, p, d_out, want_sum, &npartials); break;
+    case LL_MFMA: rc = launch_ll_mfma(h, p, d_out, want_sum, &npartials); break;
+    default: rc = launch_ll_generic(h, p, d_out, want_sum, &npartials); break;
     }
-    {
-        /* executed fp64 work per site (PLK_INFO_LL_EXEC_FLOPS): products and elementwise multiplies of the program that ran */
-        long nprod = 0, nmul = 0;
-        if (vec && h->vec_pt) {
-            for (const PlkFusedPT::VOp &o : h->fpt.vops) { if (o.code == OP_MATVEC) nprod++; if (o.code == OP_TIP_MUL || o.code == OP_POPMUL) nmul++; }
-        } else if (fused && h->fmt_pt) {
-            nprod = (long)h->fpt.mat_edge.size();
-            for (unsigned w : h->fpt.words) {
-                const unsigned hx = w & 31;
-                if (hx == OP_TIP_MUL || hx == PLK_WORD_TIPMUL_NOWAIT || hx == PLK_WORD_MATVEC_TIPMUL) nmul++;
-                if ((hx >= 16 && hx < 20) || hx >= 28 || (hx >= PLK_WORD_SET_POPMUL && hx < PLK_WORD_SET_POPMUL + 4)) nmul++;
-            }
-        } else {
-            for (const plk_op2 &o : h->ops) {
-                const int code = o.x & 0xff;
-                if (code == OP_MATVEC) nprod++;
-                /* leaf edges: a table row multiplied in (fused, vector and matrix-core kernels) or a full product (generic) */
-                if (code == OP_TIP_MUL || code == OP_NODE_MUL || code == OP_POPMUL) nmul++;
-                if ((code == OP_TIP_SET || code == OP_TIP_MUL) && !fused && !vec && !mfma) { nprod++; if (code == OP_TIP_MUL) nmul++; }
-            }
-        }
-        const long kp = mfma ? (h->k + 15) / 16 * 16 : h->k;
-        h->info_ll_exec_flops = (long)h->C * (nprod * (2 * kp * kp - kp) + nmul * h->k);
-    }
+    if (rc) return rc;
+    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_exec_flops = p.info_exec_flops;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->evk[evi][1], h->stream));
     h->evk_pending[evi] = true;
     if (want_sum) {
-        /* fixed-order double-double sum of the workgroups' partials: up to 64 slices, then one small block */
+        /* fixed-order double-double sum of the partials: up to 64 slices, then one small block */
         dd *out = sum_dev ? reinterpret_cast<dd *>(sum_dev) : h->d_partial;
-        const int g2 = grid > 1024 ? (int)std::min<unsigned>(64u, (grid + 511) / 512) : 1;
+        const int g2 = npartials > 1024 ? (int)std::min<unsigned>(64u, (npartials + 511) / 512) : 1;
         if (g2 > 1) {
-            hipLaunchKernelGGL(k_dd_slices, dim3(g2), dim3(256), 0, h->stream, (int)grid, h->d_partial + PLK_PARTIAL_OFF, h->d_partial + 4);
+            hipLaunchKernelGGL(k_dd_slices, dim3(g2), dim3(256), 0, h->stream, (int)npartials, h->d_partial + PLK_PARTIAL_OFF, h->d_partial + 4);
             hipLaunchKernelGGL(k_dd_final, dim3(1), dim3(64), 0, h->stream, g2, h->d_partial + 4, out);
         } else {
-            hipLaunchKernelGGL(k_dd_final, dim3(1), dim3(256), 0, h->stream, (int)grid, h->d_partial + PLK_PARTIAL_OFF, out);
+            hipLaunchKernelGGL(k_dd_final, dim3(1), dim3(256), 0, h->stream, (int)npartials, h->d_partial + PLK_PARTIAL_OFF, out);
         }
         HIPCHK(h, hipGetLastError());
     }
@@ -3590,7 +3560,7 @@ extern "C" int plk_marginal(plk_engine *h, const int *node_mask, double *site_ou
 /* rate-category posteriors and posterior mean site rates (plk_catpost.h)  */
 /* ---------------------------------------------------------------------- */
 
-/* the k = 4 kernel: what use_fused asks of the C++ interpreter (its LDS image at one site per lane), C terms in registers */
+/* the k = 4 kernel: what plk_k4_choose asks of the C++ interpreter (its LDS image at one site per lane), C terms in registers */
 static bool use_catpost4(const plk_engine *h)
 {
     if (h->opt_force_generic || h->k != 4 || h->pat_mode != 1 || h->C > PLK_CATPOST_REG_C) return false;

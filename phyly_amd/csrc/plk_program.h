@@ -14,6 +14,7 @@
 #define PLK_PROGRAM_H
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -1107,6 +1108,138 @@ static inline std::string plk_fused_check_cpp(int N, const PlkProgram &pg, const
     }
     for (size_t pc = nops; pc < fu.fops.size(); pc++) if ((fu.fops[pc].x & 0xff) != OP_END) return "fused program: padding is not END";
     return "";
+}
+
+/* ------------------------------------------------------------------------------------------------------------ */
+/* which k = 4 ll kernel runs: the one place that decides, for the engine and for the CPU test alike              */
+/* ------------------------------------------------------------------------------------------------------------ */
+
+enum PlkK4Variant { PLK_K4_NONE = 0, PLK_K4_CPP, PLK_K4_ASM, PLK_K4_ASM_PT, PLK_K4_V4, PLK_K4_V4S };
+enum { PLK_K4_LDS_V4S_768 = 0, PLK_K4_LDS_V4_768, PLK_K4_LDS_V4_512 };     /* PlkK4Shape::static_lds */
+
+/* PLK_OPT_PAIR_TABLES: & 7 which pair-table kernel (0 with the whole value 0: none; 1 the default order; 2, 3, 5, 6 one
+ * kernel and tile, forced; 7 the streamed form wherever it fits), + 8 without the scalar-cache warm-up, + 16 / + 32 the
+ * waves of the streamed form meet before every unit only / never (default: before every category).  The + bits are for
+ * measurements. */
+struct PlkPairTablesOpt { bool on; int mode, warm, sync; };
+static inline PlkPairTablesOpt plk_pair_tables_opt(long v)
+{
+    return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2};
+}
+
+struct PlkK4Shape {
+    int nchar, C;
+    long S;
+    int num_cus;
+    long pair_tables, fused_asm, sites_per_lane;     /* the option values as set */
+    size_t static_lds[3];                            /* of k_ll_fused4_v4s<768>, k_ll_fused4_v4<768>, k_ll_fused4_v4<512> */
+};
+
+struct PlkK4Choice {
+    PlkK4Variant variant = PLK_K4_NONE;              /* PLK_K4_NONE: not fused, another kernel family takes the tree */
+    int tile = 0;                                    /* sites per tile (v4s: per tile of the tile count it is handed) */
+    int NS = 1, D = 4, pack4 = 0;                    /* sites per lane, register stack depth, two codes per staged byte */
+    int block = 0;                                   /* lanes per workgroup */
+    size_t lds = 0;                                  /* dynamic LDS of the launch */
+    unsigned tip_base = 0;                           /* v4 / v4s: LDS address of the table image = static LDS of the kernel */
+    int warm = 1, sync = 2;                          /* pair-table kernels: the measurement bits of PLK_OPT_PAIR_TABLES */
+    std::string bad;                                 /* the replay check of the chosen variant's formats; empty: fine */
+};
+
+/*
+ * Order of preference.  Pair tables (option on, assembly allowed, one site per lane asked, <= 4 stack slots, nchar <= 16,
+ * something observed): the streamed form for modes 1 and 7 when every cherry as a table with the tables of all C categories
+ * fits and allow_stream (the engine clears it when the stream itself cannot be allocated); then the candidates of the mode,
+ * each with as many cherries as its LDS limit takes; forced modes 2, 3, 5, 6 have one candidate.  Then the assembly
+ * interpreter, then the C++ interpreter, then PLK_K4_NONE.  Builds the formats of the chosen variant (fu | fpt, fv4, fv4s)
+ * and replays them once (bad).
+ */
+static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, const PlkProgram &pg, const PlkK4Shape &sh, bool allow_stream,
+                                        PlkFused &fu, PlkFusedPT &fpt, PlkFusedV4 &fv4, PlkFusedV4S &fv4s)
+{
+    PlkK4Choice ch;
+    const int nchar = sh.nchar;
+    /* two sites per lane only in the C++ interpreter, and only within 8 stack slots; the assembly interpreter stages 4-bit
+     * codes when there are at most 16 character definitions, which lets it take about twice the taxa of the C++ one */
+    const int NS = sh.sites_per_lane == 2 && pg.slots_needed <= 8 ? 2 : 1, pack4 = nchar <= 16 ? 1 : 0;
+    const size_t lds_asm = plk_fused_lds_bytes(pg, nchar, pack4 ? PLK_TILE / 2 : PLK_TILE), lds_cpp = plk_fused_lds_bytes(pg, nchar, PLK_TILE * NS);
+    const bool asm_fits = NS == 1 && plk_fused_asm_ok(pg) && sh.fused_asm && lds_asm <= PLK_LDS_LIMIT;
+    if (pg.slots_needed > PLK_FUSED_SLOTS || (!asm_fits && lds_cpp > PLK_LDS_LIMIT)) return ch;
+    const PlkPairTablesOpt po = plk_pair_tables_opt(sh.pair_tables);
+    ch.warm = po.warm; ch.sync = po.sync;
+    if (po.on && sh.fused_asm && sh.sites_per_lane != 2 && pg.slots_needed <= 4 && nchar <= 16 && !pg.obs_nodes.empty()) {
+        if ((po.mode == 1 || po.mode == 7) && sh.S > 0 && allow_stream) {
+            /* measured faster than the tile kernels at every shape tried (profiles/ll_k4_stream_ab.json), so no site count
+             * sends the default back to them */
+            plk_fused_pt_build(N, ip, ix, pg, nchar, INT_MAX, fpt, true);
+            const size_t lds = plk_fused_v4s_lds_bytes(fpt, nchar, sh.C), st = sh.static_lds[PLK_K4_LDS_V4S_768];
+            bool any_obs = false;
+            for (const PlkFusedPT::VOp &o : fpt.vops) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) any_obs = true;
+            if (any_obs && lds + st <= plk_pt_lds_limit(1024) && (st + lds) / 32 < 65536 && fpt.units < 2048 && fpt.row_node.size() < 65536) {
+                ch.variant = PLK_K4_V4S; ch.tile = 1536; ch.NS = 2; ch.block = 768; ch.lds = lds; ch.tip_base = (unsigned)st;
+                plk_fused_v4s_words(fpt, nchar, sh.C, ch.tip_base, fv4s);
+                /* the 32-bit program is replayed whatever the form (streamed: no code rows in LDS; its fields are the chain the
+                 * streamed words are checked against) */
+                ch.bad = plk_fused_check_pt(N, ip, ix, pg, fpt, nchar, 1, 0, true, false);
+                if (ch.bad.empty()) ch.bad = plk_fused_check_v4s(fpt, fv4s, nchar, sh.C, ch.tip_base, lds);
+                return ch;
+            }
+        }
+        struct Cand { PlkK4Variant variant; int tile; };
+        std::vector<Cand> cands;
+        switch (po.mode) {
+        case 2: cands = {{PLK_K4_ASM_PT, 1024}}; break;
+        case 3: cands = {{PLK_K4_ASM_PT, 512}}; break;
+        case 5: cands = {{PLK_K4_V4, 1024}}; break;
+        case 6: cands = {{PLK_K4_V4, 1536}}; break;
+        default: {
+            /* 1536-site tiles run 1.3 x as long as 1024-site tiles (109 against 84 us a round at BASELINE config 3) and carry 1.5 x
+             * the sites; every CU runs ceil(tiles / CUs) rounds.  Few sites per GPU (a rank of an 8-way split) can need fewer
+             * round-times with the smaller tile: 1.25M sites are 4 rounds of 1536 (436 us) or 5 rounds of 1024 (420 us). */
+            auto rounds = [&](long tile) { const long nt = (sh.S + tile - 1) / tile; return (double)((nt + sh.num_cus - 1) / sh.num_cus); };
+            if (sh.S > 0 && rounds(1024) * 1.0 < rounds(1536) * 1.3) cands = {{PLK_K4_V4, 1024}, {PLK_K4_V4, 1536}, {PLK_K4_ASM_PT, 1024}, {PLK_K4_ASM_PT, 512}};
+            else cands = {{PLK_K4_V4, 1536}, {PLK_K4_V4, 1024}, {PLK_K4_ASM_PT, 1024}, {PLK_K4_ASM_PT, 512}};
+            break;
+        }
+        }
+        for (const Cand &cd : cands) {
+            const bool v4 = cd.variant == PLK_K4_V4;
+            const long limit = (long)plk_pt_lds_limit(cd.tile);
+            int max_pairs = INT_MAX;
+            for (int attempt = 0; attempt < 3; attempt++) {
+                plk_fused_pt_build(N, ip, ix, pg, nchar, max_pairs, fpt, v4);
+                const long bytes = (long)plk_fused_pt_lds_bytes(fpt, nchar, cd.tile);
+                if (bytes <= limit && fpt.units < 2048 && fpt.row_node.size() < 65536) {
+                    /* v4: two sites per lane, one workgroup of tile / 2 lanes per CU; asm_pt: one site per lane */
+                    ch.variant = cd.variant; ch.tile = cd.tile; ch.NS = v4 ? 2 : 1; ch.block = v4 ? cd.tile / 2 : cd.tile; ch.lds = (size_t)bytes;
+                    ch.bad = plk_fused_check_pt(N, ip, ix, pg, fpt, nchar, cd.tile, ch.lds, v4);
+                    if (v4) {
+                        ch.tip_base = (unsigned)sh.static_lds[cd.tile == 1536 ? PLK_K4_LDS_V4_768 : PLK_K4_LDS_V4_512];
+                        plk_fused_v4_words(fpt, nchar, cd.tile, ch.tip_base, fv4);
+                        if (ch.bad.empty()) ch.bad = plk_fused_check_v4(fpt, fv4, nchar, cd.tile, ch.tip_base, ch.lds);
+                    }
+                    return ch;
+                }
+                if (fpt.npairs == 0) break;
+                /* a cherry as a table costs nchar - 2 more units and one row less than its two leaves */
+                const long per_pair = (long)(nchar - 2) * nchar * 32 - cd.tile;
+                if (per_pair <= 0) break;                       /* tables only shrink the image: nothing to give back */
+                const long drop = (bytes - limit + per_pair - 1) / per_pair;
+                max_pairs = drop >= fpt.npairs ? 0 : fpt.npairs - (int)drop;
+            }
+        }
+    }
+    plk_fused_build(N, pg, fu);
+    ch.tile = PLK_TILE * NS; ch.NS = NS; ch.block = PLK_TILE;
+    ch.D = pg.slots_needed <= 4 ? 4 : (pg.slots_needed <= 8 ? 8 : 16);
+    if (asm_fits) {
+        ch.variant = PLK_K4_ASM; ch.pack4 = pack4; ch.lds = lds_asm;
+        ch.bad = plk_fused_check_asm(N, pg, fu, nchar, ch.D, pack4, lds_asm);
+    } else {
+        ch.variant = PLK_K4_CPP; ch.lds = lds_cpp;
+        ch.bad = plk_fused_check_cpp(N, pg, fu, nchar, ch.D, NS, lds_cpp);
+    }
+    return ch;
 }
 
 /* ------------------------------------------------------------------------------------------------------------ */

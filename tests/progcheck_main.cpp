@@ -11,6 +11,7 @@
  * Before the trees: a table of site-chunk plans (plk_site_chunk) against the rules the drivers used to spell out inline.
  * Prints "ok <trees> <ops>" and exits 0, or the first failure and exits 1.
  */
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -460,10 +461,278 @@ static std::string check_chunk_planner()
     return "";
 }
 
+/* ------------------------------------------------------------------------------------------------------------ */
+/* which k = 4 ll kernel runs (plk_k4_choose): the choice pinned on the CPU                                       */
+/* ------------------------------------------------------------------------------------------------------------ */
+
+/* static LDS of k_ll_fused4_v4s<768>, k_ll_fused4_v4<768>, k_ll_fused4_v4<512> as compiled for gfx950 (the engine asks the runtime) */
+static const size_t K4_STATIC_LDS[3] = {0, 256, 256};
+
+enum { OUT_CPP_D4, OUT_CPP_D8, OUT_CPP_D16, OUT_CPP_NS2, OUT_ASM_D4_P0, OUT_ASM_D4_P1, OUT_ASM_D8_P0, OUT_ASM_D8_P1, OUT_PT_512, OUT_PT_1024,
+       OUT_V4_1024, OUT_V4_1536, OUT_V4S, OUT_NONE, OUT_COUNT };
+static const char *const OUT_NAME[OUT_COUNT] = {"C++ NS 1 D 4", "C++ NS 1 D 8", "C++ NS 1 D 16", "C++ NS 2", "asm D 4 pack4 0", "asm D 4 pack4 1",
+    "asm D 8 pack4 0", "asm D 8 pack4 1", "asm_pt 512", "asm_pt 1024", "v4 1024", "v4 1536", "v4s", "not fused"};
+static long g_outcome[OUT_COUNT];
+/* per PLK_OPT_PAIR_TABLES mode: cases in which a forced mode's own tile kernel did not fit while another tile kernel would
+ * have -- the cases that tell "falls through to the interpreters" from "falls back to another pair-table candidate" */
+static long g_forced_fell_through[8];
+
+struct K4Formats { PlkFused fu; PlkFusedPT fpt; PlkFusedV4 fv4; PlkFusedV4S fv4s; };
+struct K4Cand { PlkK4Variant variant; int tile; };
+
+static bool pt_fields_ok(const PlkFusedPT &f) { return f.units < 2048 && f.row_node.size() < 65536; }
+
+/* Does a tile candidate fit with some number of cherries as tables?  A cherry as a table adds a fixed number of bytes
+ * (of either sign) to the image, so the smallest image has every cherry or none: both ends are tried. */
+static bool pt_cand_fits(const Tree &t, const PlkProgram &pg, int nchar, const K4Cand &cd)
+{
+    const int budgets[2] = {INT_MAX, 0};
+    for (int b = 0; b < 2; b++) {
+        PlkFusedPT f;
+        plk_fused_pt_build(t.N, t.ip.data(), t.ix.data(), pg, nchar, budgets[b], f, cd.variant == PLK_K4_V4);
+        if (plk_fused_pt_lds_bytes(f, nchar, cd.tile) <= plk_pt_lds_limit(cd.tile) && pt_fields_ok(f)) return true;
+    }
+    return false;
+}
+
+static bool stream_fits(const Tree &t, const PlkProgram &pg, int nchar, int C)
+{
+    PlkFusedPT f;
+    plk_fused_pt_build(t.N, t.ip.data(), t.ix.data(), pg, nchar, INT_MAX, f, true);
+    bool any_obs = false;
+    for (const PlkFusedPT::VOp &o : f.vops) any_obs = any_obs || o.code == OP_TIP_SET || o.code == OP_TIP_MUL;
+    const size_t image = K4_STATIC_LDS[PLK_K4_LDS_V4S_768] + plk_fused_v4s_lds_bytes(f, nchar, C);
+    return any_obs && image <= plk_pt_lds_limit(1024) && image / 32 < 65536 && pt_fields_ok(f);
+}
+
+static PlkK4Choice k4_choose(const Tree &t, const PlkProgram &pg, int nchar, int C, long S, long mode, long fasm, long spl, bool allow_stream, K4Formats &F)
+{
+    PlkK4Shape sh = {nchar, C, S, 256, mode, fasm, spl, {K4_STATIC_LDS[0], K4_STATIC_LDS[1], K4_STATIC_LDS[2]}};
+    return plk_k4_choose(t.N, t.ip.data(), t.ix.data(), pg, sh, allow_stream, F.fu, F.fpt, F.fv4, F.fv4s);
+}
+
+/* One tree through the sweep of nchar, C, S, PLK_OPT_PAIR_TABLES, PLK_OPT_FUSED_ASM, PLK_OPT_FUSED_SITES_PER_LANE and
+ * allow_stream (256 CUs).  For every case: the candidates in the engine's order of preference are written out here, each
+ * with its own fit test from the *_lds_bytes functions; the choice must be the first that fits (so no earlier one would
+ * have fitted, and a forced mode gives its kernel and tile or falls through to the interpreters); the chosen variant's
+ * preconditions hold and its replay check, run again here on the formats handed back, is empty. */
+static std::string check_k4_choice(const Tree &t, const std::vector<char> &has, const int *nchars, int n_nchars)
+{
+    const int N = t.N;
+    const int *ip = t.ip.data(), *ix = t.ix.data();
+    PlkProgram pg;
+    plk_program_build(N, ip, ix, t.pre.data(), has.data(), pg);
+    const int slots = pg.slots_needed;
+    const K4Cand tiles[4] = {{PLK_K4_V4, 1536}, {PLK_K4_V4, 1024}, {PLK_K4_ASM_PT, 1024}, {PLK_K4_ASM_PT, 512}};
+    const long modes[7] = {0, 1, 2, 3, 5, 6, 7}, sites[4] = {1, 300, 1250000, 10000000};
+    for (int ni = 0; ni < n_nchars; ni++) {
+        const int nchar = nchars[ni];
+        const bool pt_tree = slots <= 4 && nchar <= 16 && !pg.obs_nodes.empty();
+        bool tile_fits[4] = {false, false, false, false};
+        for (int q = 0; q < 4 && pt_tree; q++) tile_fits[q] = pt_cand_fits(t, pg, nchar, tiles[q]);
+        for (int C = 1; C <= 4; C += 3) {
+            const bool sfits = pt_tree && stream_fits(t, pg, nchar, C);
+            for (long S : sites) for (long mode : modes) for (long fasm = 0; fasm <= 1; fasm++) for (long spl = 0; spl <= 2; spl += 2)
+            for (int allow = 0; allow <= 1; allow++) {
+                const std::string tag = plk_fmt("k4 choice (nchar %ld, C %ld, ", nchar, C) + plk_fmt("S %ld, mode %ld, asm %ld, ", S, mode, fasm) +
+                                        plk_fmt("sites per lane %ld, stream %ld): ", spl, allow);
+                K4Formats F;
+                const PlkK4Choice ch = k4_choose(t, pg, nchar, C, S, mode, fasm, spl, allow != 0, F);
+                /* the interpreters */
+                const int NS = spl == 2 && slots <= 8 ? 2 : 1, pack4 = nchar <= 16 ? 1 : 0;
+                const size_t lds_cpp = plk_fused_lds_bytes(pg, nchar, PLK_TILE * NS), lds_asm = plk_fused_lds_bytes(pg, nchar, pack4 ? PLK_TILE / 2 : PLK_TILE);
+                const bool asm_fits = NS == 1 && fasm && plk_fused_asm_ok(pg) && lds_asm <= PLK_LDS_LIMIT;
+                const bool fused = slots <= PLK_FUSED_SLOTS && (asm_fits || lds_cpp <= PLK_LDS_LIMIT);
+                /* the order of preference, with what fits */
+                std::vector<K4Cand> order;
+                std::vector<char> fits;
+                if (fused && pt_tree && mode != 0 && fasm && spl != 2) {
+                    if ((mode == 1 || mode == 7) && allow) { order.push_back({PLK_K4_V4S, 1536}); fits.push_back(sfits); }
+                    int pick[4] = {0, 1, 2, 3}, npick = 4;
+                    if (mode == 2) { pick[0] = 2; npick = 1; }
+                    else if (mode == 3) { pick[0] = 3; npick = 1; }
+                    else if (mode == 5) { pick[0] = 1; npick = 1; }
+                    else if (mode == 6) { pick[0] = 0; npick = 1; }
+                    else {
+                        /* 1024-site tiles first when their rounds over 256 CUs cost less than 1.3 x those of 1536-site tiles */
+                        const long r1024 = ((S + 1023) / 1024 + 255) / 256, r1536 = ((S + 1535) / 1536 + 255) / 256;
+                        if (10 * r1024 < 13 * r1536) std::swap(pick[0], pick[1]);
+                    }
+                    for (int q = 0; q < npick; q++) { order.push_back(tiles[pick[q]]); fits.push_back(tile_fits[pick[q]]); }
+                }
+                if (fused) { order.push_back(asm_fits ? K4Cand{PLK_K4_ASM, PLK_TILE} : K4Cand{PLK_K4_CPP, PLK_TILE * NS}); fits.push_back(1); }
+                order.push_back({PLK_K4_NONE, 0}); fits.push_back(1);
+                size_t first = 0;
+                while (!fits[first]) first++;
+                if (ch.variant != order[first].variant || ch.tile != order[first].tile)
+                    return tag + plk_fmt("variant %ld at tile %ld chosen, ", ch.variant, ch.tile) + plk_fmt("the order of preference gives variant %ld at tile %ld", order[first].variant, order[first].tile);
+                if (mode == 2 || mode == 3 || mode == 5 || mode == 6) {
+                    const K4Cand forced = tiles[mode == 2 ? 2 : mode == 3 ? 3 : mode == 5 ? 1 : 0];
+                    const bool pt_variant = ch.variant == PLK_K4_ASM_PT || ch.variant == PLK_K4_V4 || ch.variant == PLK_K4_V4S;
+                    if (pt_variant && (ch.variant != forced.variant || ch.tile != forced.tile)) return tag + "a forced mode ran another pair-table kernel";
+                    if (order.size() > 2 && !fits[0] && (tile_fits[0] || tile_fits[1] || tile_fits[2] || tile_fits[3])) g_forced_fell_through[mode]++;
+                }
+                if (!ch.bad.empty()) return tag + ch.bad;
+                /* preconditions and replay of the chosen variant, from the formats handed back */
+                std::string bad;
+                int out = OUT_NONE;
+                if (ch.variant == PLK_K4_CPP) {
+                    const int D = slots <= 4 ? 4 : slots <= 8 ? 8 : 16;
+                    if (ch.D != D || ch.NS != NS || ch.block != PLK_TILE || ch.lds != lds_cpp || lds_cpp > PLK_LDS_LIMIT || (NS == 2 && (spl != 2 || slots > 8))) return tag + "C++ interpreter: preconditions";
+                    bad = plk_fused_check_cpp(N, pg, F.fu, nchar, D, NS, lds_cpp);
+                    out = NS == 2 ? OUT_CPP_NS2 : D == 4 ? OUT_CPP_D4 : D == 8 ? OUT_CPP_D8 : OUT_CPP_D16;
+                } else if (ch.variant == PLK_K4_ASM) {
+                    const int D = slots <= 4 ? 4 : 8;
+                    if (ch.D != D || ch.NS != 1 || ch.pack4 != pack4 || ch.block != PLK_TILE || ch.lds != lds_asm || lds_asm > PLK_LDS_LIMIT || slots > 8 || !fasm || (spl == 2 && slots <= 8))
+                        return tag + "assembly interpreter: preconditions";
+                    bad = plk_fused_check_asm(N, pg, F.fu, nchar, D, pack4, lds_asm);
+                    out = (D == 4 ? OUT_ASM_D4_P0 : OUT_ASM_D8_P0) + pack4;
+                } else if (ch.variant == PLK_K4_ASM_PT || ch.variant == PLK_K4_V4) {
+                    const bool v4 = ch.variant == PLK_K4_V4;
+                    const size_t lds = plk_fused_pt_lds_bytes(F.fpt, nchar, ch.tile);
+                    if (slots > 4 || nchar > 16 || !fasm || spl == 2 || mode == 0 || !plk_pt_tile_ok(ch.tile) || (v4 ? ch.tile == 512 : ch.tile == 1536) || ch.lds != lds ||
+                        lds > plk_pt_lds_limit(ch.tile) || !pt_fields_ok(F.fpt) || ch.block != (v4 ? ch.tile / 2 : ch.tile) || ch.NS != (v4 ? 2 : 1) || ch.D != 4) return tag + "pair-table tile kernel: preconditions";
+                    bad = plk_fused_check_pt(N, ip, ix, pg, F.fpt, nchar, ch.tile, lds, v4);
+                    if (v4) {
+                        const unsigned base = (unsigned)K4_STATIC_LDS[ch.tile == 1536 ? PLK_K4_LDS_V4_768 : PLK_K4_LDS_V4_512];
+                        if (ch.tip_base != base) return tag + "v4: table base";
+                        if (bad.empty()) bad = plk_fused_check_v4(F.fpt, F.fv4, nchar, ch.tile, base, lds);
+                    }
+                    out = v4 ? (ch.tile == 1024 ? OUT_V4_1024 : OUT_V4_1536) : (ch.tile == 512 ? OUT_PT_512 : OUT_PT_1024);
+                } else if (ch.variant == PLK_K4_V4S) {
+                    const size_t lds = plk_fused_v4s_lds_bytes(F.fpt, nchar, C), st = K4_STATIC_LDS[PLK_K4_LDS_V4S_768];
+                    if (slots > 4 || nchar > 16 || !fasm || spl == 2 || (mode != 1 && mode != 7) || !allow || S < 1 || ch.lds != lds || ch.tip_base != st ||
+                        lds + st > plk_pt_lds_limit(1024) || !pt_fields_ok(F.fpt) || ch.block != 768 || ch.tile != 1536 || F.fpt.npairs < 0) return tag + "streamed form: preconditions";
+                    bad = plk_fused_check_pt(N, ip, ix, pg, F.fpt, nchar, 1, 0, true, false);
+                    if (bad.empty()) bad = plk_fused_check_v4s(F.fpt, F.fv4s, nchar, C, (unsigned)st, lds);
+                } else if (slots <= PLK_FUSED_SLOTS && (lds_cpp <= PLK_LDS_LIMIT || asm_fits)) return tag + "not fused although an interpreter fits";
+                if (ch.variant == PLK_K4_V4S) out = OUT_V4S;
+                if (!bad.empty()) return tag + "replay: " + bad;
+                g_outcome[out]++;
+            }
+        }
+    }
+    return "";
+}
+
+static bool tree_from_parents(const std::vector<int> &parent, Tree &t)       /* parent[i] of node i >= 1, node 0 the root */
+{
+    const int N = (int)parent.size();
+    std::vector<int> ea(N - 1), eb(N - 1);
+    for (int i = 1; i < N; i++) { ea[i - 1] = parent[i]; eb[i - 1] = i; }
+    return make_tree(N, ea, eb, t);
+}
+
+/* n leaves, one joining per level (nodes: 0 the root, odd i a leaf under i - 1 or, the last two, the cherry) */
+static void caterpillar_tree(int n, Tree &t)
+{
+    std::vector<int> parent(2 * n - 1, 0);
+    for (int i = 1; i < 2 * n - 1; i++) parent[i] = i % 2 ? i - 1 : i - 2;
+    tree_from_parents(parent, t);
+}
+
+static void balanced_tree(int leaves, Tree &t)
+{
+    std::vector<int> parent(2 * leaves - 1, 0);
+    for (int i = 1; i < 2 * leaves - 1; i++) parent[i] = (i - 1) / 2;
+    tree_from_parents(parent, t);
+}
+
+/* the irregular tree of the GPU tests' k = 4 models "irregular" and "wide" (tests/helpers.py), with data on nodes 17 and 18 */
+static void irregular_tree(Tree &t, std::vector<char> &has)
+{
+    const int e[23][2] = {{13, 14}, {13, 15}, {13, 12}, {14, 16}, {14, 4}, {14, 5}, {16, 6}, {16, 17}, {17, 7}, {17, 18}, {18, 2}, {18, 3},
+                          {15, 19}, {19, 8}, {19, 20}, {20, 9}, {20, 21}, {21, 10}, {21, 22}, {22, 11}, {22, 23}, {23, 0}, {23, 1}};
+    std::vector<int> ea(23), eb(23);
+    for (int i = 0; i < 23; i++) { ea[i] = e[i][0]; eb[i] = e[i][1]; }
+    make_tree(24, ea, eb, t);
+    has.assign(24, 0);
+    has[17] = has[18] = 1;
+}
+
+/* (shape, options) -> (PLK_INFO_LL_KERNEL is 1 throughout) variant, form, sites per tile: the shapes of the GPU tests
+ * test_gpu_k4_variants.py, test_gpu_fused_asm.py and test_gpu_k4_stream.py, written from the selection code as it was
+ * spread over the engine and confirmed on the GPU against that engine (profiles/ll_plan_refactor_ab.json); the rows without
+ * the stream stand for a failed allocation of it, which no option asks for: those are from the code alone */
+static std::string check_k4_table()
+{
+    enum { CAT8, BAL32, BAL64, IRREG };
+    struct Row { int tree, nchar, C; long S, mode, fasm, spl; bool allow; PlkK4Variant variant; int tile; };
+    const Row rows[] = {
+        {CAT8, 5, 4, 300, 1, 1, 0, true, PLK_K4_V4S, 1536},        /* the default: streamed codes */
+        {CAT8, 5, 4, 300, 7, 1, 0, true, PLK_K4_V4S, 1536},
+        {CAT8, 5, 4, 300, 1, 1, 0, false, PLK_K4_V4, 1024},        /* no stream: one round of either tile, the smaller first */
+        {CAT8, 5, 4, 10000000, 1, 1, 0, false, PLK_K4_V4, 1536},   /* 26 rounds of 1536 (x 1.3 = 33.8) against 39 of 1024 */
+        {CAT8, 5, 4, 1250000, 1, 1, 0, false, PLK_K4_V4, 1024},    /* 4 rounds of 1536 (5.2) against 5 of 1024 */
+        {CAT8, 5, 4, 300, 6, 1, 0, true, PLK_K4_V4, 1536},
+        {CAT8, 5, 4, 300, 5, 1, 0, true, PLK_K4_V4, 1024},
+        {CAT8, 5, 4, 300, 2, 1, 0, true, PLK_K4_ASM_PT, 1024},
+        {CAT8, 5, 4, 300, 3, 1, 0, true, PLK_K4_ASM_PT, 512},
+        {CAT8, 5, 4, 300, 0, 1, 0, true, PLK_K4_ASM, 256},
+        {CAT8, 5, 4, 300, 0, 0, 0, true, PLK_K4_CPP, 256},
+        {CAT8, 5, 4, 300, 1, 0, 0, true, PLK_K4_CPP, 256},         /* pair tables need the assembly option */
+        {CAT8, 5, 4, 300, 1, 1, 2, true, PLK_K4_CPP, 512},         /* two sites per lane: the C++ interpreter only */
+        {CAT8, 16, 4, 129, 7, 1, 0, true, PLK_K4_V4S, 1536},
+        {CAT8, 4, 1, 129, 7, 1, 0, true, PLK_K4_V4S, 1536},
+        {BAL32, 16, 2, 129, 7, 1, 0, true, PLK_K4_V4, 1024},       /* 128 KB of tables per category: two do not fit, a tile kernel */
+        {BAL32, 16, 2, 129, 6, 1, 0, true, PLK_K4_V4, 1536},
+        {BAL32, 5, 1, 300, 1, 1, 0, true, PLK_K4_V4S, 1536},
+        {BAL32, 5, 1, 300, 0, 1, 0, true, PLK_K4_ASM, 256},
+        {BAL64, 5, 4, 300, 1, 1, 0, true, PLK_K4_ASM, 256},        /* 5 stack slots: no pair tables */
+        {BAL64, 5, 4, 300, 1, 0, 0, true, PLK_K4_CPP, 256},
+        {BAL64, 5, 4, 300, 1, 1, 2, true, PLK_K4_CPP, 512},
+        {IRREG, 7, 4, 300, 1, 1, 0, true, PLK_K4_V4S, 1536},
+        {IRREG, 7, 4, 300, 6, 1, 0, true, PLK_K4_V4, 1536},
+        {IRREG, 17, 2, 300, 1, 1, 0, true, PLK_K4_ASM, 256},       /* 17 definitions: no pair tables, 8-bit staged codes */
+        {IRREG, 17, 2, 300, 1, 0, 0, true, PLK_K4_CPP, 256},
+    };
+    Tree trees[4];
+    std::vector<char> has[4];
+    caterpillar_tree(8, trees[CAT8]); balanced_tree(32, trees[BAL32]); balanced_tree(64, trees[BAL64]);
+    irregular_tree(trees[IRREG], has[IRREG]);
+    for (int q = 0; q < 3; q++) has[q].assign(trees[q].N, 0);
+    int r = 0;
+    for (const Row &w : rows) {
+        const Tree &t = trees[w.tree];
+        PlkProgram pg;
+        plk_program_build(t.N, t.ip.data(), t.ix.data(), t.pre.data(), has[w.tree].data(), pg);
+        K4Formats F;
+        const PlkK4Choice ch = k4_choose(t, pg, w.nchar, w.C, w.S, w.mode, w.fasm, w.spl, w.allow, F);
+        if (ch.variant != w.variant || ch.tile != w.tile || !ch.bad.empty())
+            return plk_fmt("k4 table row %ld: variant %ld at tile %ld", r, ch.variant, ch.tile) + plk_fmt(", expected variant %ld at tile %ld ", w.variant, w.tile) + ch.bad;
+        r++;
+    }
+    return "";
+}
+
+/* the sweep over the seeded random trees' subset is run from main; here the constructed trees and the outcome counts */
+static std::string check_k4_constructed()
+{
+    const int nchars[4] = {4, 5, 16, 17};
+    std::string bad;
+    Tree t;
+    /* 90 leaves with 16 definitions: 1024-site tiles fit, 512- and 1536-site tiles do not (forced modes 3 and 6 fall through) */
+    const int cats[6] = {2, 8, 40, 90, 300, 2000}, bals[4] = {8, 32, 64, 256};
+    for (int n : cats) { caterpillar_tree(n, t); bad = check_k4_choice(t, std::vector<char>(t.N, 0), nchars, 4); if (!bad.empty()) return plk_fmt("caterpillar %ld: ", n) + bad; }
+    for (int n : bals) { balanced_tree(n, t); bad = check_k4_choice(t, std::vector<char>(t.N, 0), nchars, 4); if (!bad.empty()) return plk_fmt("balanced %ld: ", n) + bad; }
+    /* k_ll_fused4<16, 1> needs more than 8 stack slots and an LDS image that still fits: the tree of the GPU tests' "deep"
+     * workload (tests/helpers.py, deep_workload: the full binary tree over 512 unary nodes with one leaf each, stack need 9)
+     * with its ONE character definition, outside the nchar values of the sweep */
+    const int one[1] = {1};
+    std::vector<int> parent(1535, 0);
+    for (int i = 1; i < 1023; i++) parent[i] = (i - 1) / 2;
+    for (int i = 0; i < 512; i++) parent[1023 + i] = 511 + i;
+    tree_from_parents(parent, t);
+    bad = check_k4_choice(t, std::vector<char>(t.N, 0), one, 1);
+    if (!bad.empty()) return "deep tree, one definition: " + bad;
+    return "";
+}
+
 int main(int argc, char **argv)
 {
     long ntrees = 0;
     { const std::string bad = check_chunk_planner(); if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; } }
+    { const std::string bad = check_k4_table(); if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; } }
     if (argc > 1) {
         FILE *f = fopen(argv[1], "r");
         if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
@@ -519,7 +788,8 @@ int main(int argc, char **argv)
         std::vector<char> has(N, 0);
         const int pdata = iter % 3 == 0 ? 0 : (iter % 3 == 1 ? 30 : 100);
         for (int a = 0; a < N; a++) has[a] = t.ip[a + 1] > t.ip[a] && rnd(100) < pdata;
-        const std::string bad = check_tree(t, has, nchars[rnd(8)]);
+        std::string bad = check_tree(t, has, nchars[rnd(8)]);
+        if (bad.empty() && iter % 40 == 3) { const int k4_nchars[4] = {4, 5, 16, 17}; bad = check_k4_choice(t, has, k4_nchars, 4); }
         if (!bad.empty()) { fprintf(stderr, "iteration %d (shape %d, N = %d): %s\n", iter, shape, N, bad.c_str()); return 1; }
         ntrees++;
     }
@@ -534,6 +804,20 @@ int main(int argc, char **argv)
         const std::string bad = check_tree(t, has, 5);
         if (!bad.empty()) { fprintf(stderr, "balanced depth %d: %s\n", d, bad.c_str()); return 1; }
         ntrees++;
+    }
+    /* the k = 4 choice on constructed trees, then: every outcome of the choice was reached (the sweep cannot pass vacuously) */
+    { const std::string bad = check_k4_constructed(); if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; } }
+    for (int q = 0; q < OUT_COUNT; q++) {
+        fprintf(stderr, "k4 choice: %-16s %ld\n", OUT_NAME[q], g_outcome[q]);
+        if (!g_outcome[q]) { fprintf(stderr, "k4 choice: outcome \"%s\" was never chosen\n", OUT_NAME[q]); return 1; }
+    }
+    /* ... and so was a forced mode whose tile does not fit while another would.  Modes 3 (512-site tiles) and 6 (1536) have
+     * such cases.  Modes 2 and 5 (1024 sites) cannot: the image of a 1536-site tile is larger under the same limit, twice the
+     * image of a 512-site tile under half the limit is no smaller than that of a 1024-site tile, and the other 1024-site kernel
+     * has the same image -- should a case turn up after all, it has to be required here too. */
+    for (int mode : {2, 3, 5, 6}) {
+        fprintf(stderr, "k4 choice: forced mode %d fell through past a fitting tile kernel %ld times\n", mode, g_forced_fell_through[mode]);
+        if ((g_forced_fell_through[mode] == 0) == (mode == 3 || mode == 6)) { fprintf(stderr, "k4 choice: forced mode %d: fall-through count\n", mode); return 1; }
     }
     printf("ok %ld %ld\n", ntrees, g_ops);
     return 0;

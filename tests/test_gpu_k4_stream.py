@@ -215,3 +215,79 @@ def test_stale_state(eng):
     wl2.setup_engine(eng)
     eng.set_patterns_codes(codes2, wl.defs)              # a new tree drops the patterns
     same(wl2, codes2, None, "new topology")
+
+
+# (option, value) steps of test_stale_plan: every option the ll plan reads, set and set back to its default
+def _plan_steps():
+    from phyly_amd import engine as E
+    return ((E.OPT_PAIR_TABLES, 0), (E.OPT_PAIR_TABLES, 5), (E.OPT_PAIR_TABLES, 7), (E.OPT_PAIR_TABLES, 1),
+            (E.OPT_FUSED_ASM, 0), (E.OPT_FUSED_ASM, 1), (E.OPT_FUSED_NS, 2), (E.OPT_FUSED_NS, 0),
+            (E.OPT_FORCE_GENERIC, 1), (E.OPT_FORCE_GENERIC, 0), (E.OPT_MFMA, 2), (E.OPT_MFMA, 1),
+            (E.OPT_MFMA_NS2, 1), (E.OPT_MFMA_NS2, 0), (E.OPT_VEC_REG_STACK, 0), (E.OPT_VEC_REG_STACK, 1))
+
+
+def _plan_case(name):
+    """k4: a partial tile and a partial 128-site unit; k20: vector <-> matrix-core; k61: two 128-site workgroups with two
+    16-site groups per wave, the second nearly empty"""
+    from helpers import family_workload
+    if name == "k4":
+        wl = _workload(caterpillar(8), seed=41)
+        return wl, _codes(wl, 300, seed=3)
+    wl = family_workload(20 if name == "k20" else 61)
+    return wl, wl.random_codes(200 if name == "k20" else 130, seed=5)
+
+
+def _answer(e):
+    from phyly_amd import engine as E
+    site, (hi, lo) = e.ll()
+    return site.copy(), hi, lo, (e.info(E.INFO_LL_KERNEL), e.info(E.INFO_LL_VARIANT), e.info(E.INFO_LL_FORM))
+
+
+@pytest.mark.parametrize("case", ["k4", "k20", "k61"])
+def test_stale_plan(case):
+    """one live engine, every plan-feeding option toggled and back: after each toggle it answers bit for bit as an engine
+    created with that option, and reports the same kernel, variant and form.  PLK_OPT_MFMA_NS2 and PLK_OPT_VEC_REG_STACK pick
+    kernels that give the same bits and the same three info values as their alternatives, so for those two a setter that forgot
+    to mark the plan stale would not be seen here: what this pins for them is that the toggle leaves the answer right."""
+    from phyly_amd import engine as E
+    wl, codes = _plan_case(case)
+
+    def setup(e):
+        wl.setup_engine(e)
+        e.set_patterns_codes(codes, wl.defs)
+
+    fresh = {}
+    defaults = {E.OPT_PAIR_TABLES: 1, E.OPT_FUSED_ASM: 1, E.OPT_FUSED_NS: 0, E.OPT_FORCE_GENERIC: 0, E.OPT_MFMA: 1, E.OPT_MFMA_NS2: 0,
+                E.OPT_VEC_REG_STACK: 1}
+
+    def fresh_answer(state):
+        key = tuple(sorted((o, v) for o, v in state.items() if v != defaults[o]))      # a new engine has the defaults
+        if key not in fresh:
+            e = E.Engine(0)
+            try:
+                setup(e)
+                for opt, val in key:
+                    e.set_option(opt, val)
+                fresh[key] = _answer(e)
+            finally:
+                e.close()
+        return fresh[key]
+
+    live = E.Engine(0)
+    try:
+        setup(live)
+        _answer(live)
+        state, kernels = {}, set()
+        for opt, val in _plan_steps():
+            live.set_option(opt, val)
+            state[opt] = val
+            got, want = _answer(live), fresh_answer(state)
+            assert np.all(np.isfinite(got[0])), (case, opt, val)
+            assert got[3] == want[3], (case, opt, val, got[3], want[3])
+            assert np.array_equal(got[0], want[0]) and got[1] == want[1] and got[2] == want[2], (case, opt, val)
+            kernels.add(got[3])
+        # the toggles did move the plan: a test on one kernel throughout would say nothing
+        # (k4: streamed, v4 tile, assembly, C++, generic; k20: vector, matrix-core, generic; k61: matrix-core, generic)
+        assert len(kernels) >= {"k4": 5, "k20": 3, "k61": 2}[case], (case, kernels)
+    finally:
+        live.close()

@@ -12,7 +12,7 @@ that these models tell a wrong kernel from a right one.
 Oracle values (binary128, precise = 2) are built once per model.  Site counts are one past every tile size (256, 512,
 1024, 1536) with a ragged last wave; a model runs the sizes its variants can tile.  Every case asserts the kernel, the
 variant and the up-pass path it ran on (PLK_INFO_LL_KERNEL, PLK_INFO_LL_VARIANT, PLK_INFO_PAIR_TABLES,
-PLK_INFO_UPDOWN_KERNEL, PLK_INFO_UP4_PATH) against what build_fused_pt, fused_asm_fits, use_fused and run_updown4
+PLK_INFO_UPDOWN_KERNEL, PLK_INFO_UP4_PATH) against what plk_k4_choose (plk_program.h) and run_updown4
 prescribe for the model, so an option or dispatch change cannot quietly move a case off the path its name claims.
 
 Tolerances and weights are those of tests/test_gpu_kernel_families.py."""
@@ -58,9 +58,9 @@ def _pt(model):
 def _ll_cases(model):
     """-> [(name, options, layout, ll kernel, variant, pair tables > 0)]: the option tuples of test_gpu_fused_asm._both
     (and PLK_OPT_PAIR_TABLES = 6, the 1536-site tile), two sites per lane, forced generic, the dense layout.
-    build_fused_pt: pair tables need PLK_OPT_FUSED_ASM, one site per lane, <= 4 slots, <= 16 definitions; option 1 / 5 / 6
+    plk_k4_choose: pair tables need PLK_OPT_FUSED_ASM, one site per lane, <= 4 slots, <= 16 definitions; option 1 / 5 / 6
     give the two-sites-per-lane interpreter (variant 6), 2 / 3 the one-site one (variant 5).  Without them
-    fused_asm_fits gives the assembly interpreter (variant 1; up to 8 slots, one site per lane), else the C++ one (3)."""
+    then the assembly interpreter where it fits (variant 1; up to 8 slots, one site per lane), else the C++ one (3)."""
     from phyly_amd import engine as E
     pt = _pt(model)
     out = []

@@ -6,7 +6,12 @@ The engine refuses to launch a kernel whose program, LDS image or register-stack
   * 6000 seeded random trees of every shape (chains, stars, caterpillars, complete binary / ternary, random
     multifurcating, 2..3500 nodes, data on internal nodes, 1..256 character definitions) with negative controls,
   * the trees and definition counts of the seeded random JSON queries of tests/test_gpu_differential.py as the host
-    layer hands them to the engine once probability arrays are compacted to codes (every distinct row a definition).
+    layer hands them to the engine once probability arrays are compacted to codes (every distinct row a definition),
+  * the choice of the k = 4 ll kernel (plk_k4_choose): a sweep over every 40th random tree, caterpillars and balanced trees,
+    nchar 4 / 5 / 16 / 17, C 1 / 4, S 1 .. 10M, every PLK_OPT_PAIR_TABLES mode, PLK_OPT_FUSED_ASM and
+    PLK_OPT_FUSED_SITES_PER_LANE value, with and without the stream -- the choice is the first candidate of the engine's
+    order of preference that fits, its preconditions hold, its replay is clean, every outcome is reached at least once --
+    and a fixed table of the shapes the GPU tests use.
 """
 import os
 import random
