@@ -157,6 +157,13 @@ int plk_set_stream(plk_engine *h, void *hip_stream);
  * site_edge_out: NULL or [S][E] doubles, host; unrequested edges get 0.
  * edge_sums_out: NULL or [E][2] double-double sums of w_s * d_{s,e}; a site of weight exactly 0 adds nothing, also
  * where its derivatives are not finite (likelihood 0).
+ *
+ * Nodes with many factors: plk_deriv, plk_marginal, plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens,
+ * plk_mixture_sens, plk_second_order and plk_hess keep one rescaling factor per node.  On a tree with a node that takes
+ * more than 32 edge factors at once (33 leaf children, or three children over 16 edges each) they first measure the
+ * node products on the device; where one has no entry of at least 2^-969 at some site they return PLK_E_ARG, the
+ * diagnostic naming the query and the node, and the engine stays usable.  With ordinary branch lengths nothing is refused.
+ * plk_ll and plk_cat_posterior rescale inside such a node and always answer.
  */
 int plk_deriv(plk_engine *h, const int *edge_mask,
               double *site_edge_out, double *edge_sums_out);

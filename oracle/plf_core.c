@@ -295,17 +295,23 @@ int orc_prepare(int k, const double *rate_matrix,
     for (size_t i = 0; i < kk; i++) Qn_out[i] = (double)Q[i];
     if (Qn_q_out) memcpy(Qn_q_out, Q, kk * sizeof(q128));
     /* transition matrices */
-    q128 *A = malloc(kk * sizeof(q128)), *X = malloc(kk * sizeof(q128));
-    for (int c = 0; c < C; c++)
-        for (int e = 0; e < E; e++) {
-            q128 s = rates[c] * (q128)edge_rates_csr[e];
-            for (size_t i = 0; i < kk; i++) A[i] = Q[i] * s;
-            q_expm(k, A, X);
-            double *dst = P_out + ((size_t)c * E + e) * kk;
-            for (size_t i = 0; i < kk; i++) dst[i] = (double)X[i];
-            if (P_q_out) memcpy((q128 *)P_q_out + ((size_t)c * E + e) * kk, X, kk * sizeof(q128));
-        }
-    free(A); free(X); free(Q); free(pi); free(rates);
+    /* one exponential per (category, edge), each on its own: shared out over the threads (the values do not depend on it) */
+#pragma omp parallel
+    {
+        q128 *A = malloc(kk * sizeof(q128)), *X = malloc(kk * sizeof(q128));
+#pragma omp for collapse(2) schedule(dynamic)
+        for (int c = 0; c < C; c++)
+            for (int e = 0; e < E; e++) {
+                q128 s = rates[c] * (q128)edge_rates_csr[e];
+                for (size_t i = 0; i < kk; i++) A[i] = Q[i] * s;
+                q_expm(k, A, X);
+                double *dst = P_out + ((size_t)c * E + e) * kk;
+                for (size_t i = 0; i < kk; i++) dst[i] = (double)X[i];
+                if (P_q_out) memcpy((q128 *)P_q_out + ((size_t)c * E + e) * kk, X, kk * sizeof(q128));
+            }
+        free(A); free(X);
+    }
+    free(Q); free(pi); free(rates);
     return C;
 }
 

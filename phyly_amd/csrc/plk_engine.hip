@@ -971,6 +971,82 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_ll_generic(GenArgs a)
     }
 }
 
+/*
+ * Dynamic range of the passes that store node vectors, on a tree with a node that is rescaled inside (PlkProgram::mid_scales).
+ * Those passes keep one factor per node, so they skip the OP_SCALE ops inside a node (op_mid) and see the node's whole
+ * product at the OP_SCALE after its last child.  This kernel walks the program the same way and raises *flag where such a
+ * product, or the root vector, has no entry of at least 2^-969 in some category at some site: below that magnitude an entry
+ * within 2^-53 of the largest can be subnormal, and the stored vectors are no longer good to the stated bars.  The matrices
+ * are read by edge (PS = [C][E][K*K], transposed).  No output but the flag.
+ */
+template <int K>
+__global__ __launch_bounds__(GEN_BLOCK) void k_range_check(GenArgs a, int E, const int *op_edge, const int *op_mid, int *flag)
+{
+    __shared__ double xs[K][GEN_BLOCK];
+    const int tid = threadIdx.x;
+    const long s = (long)blockIdx.x * GEN_BLOCK + tid;
+    const bool valid = s < a.S;
+    const long sc = valid ? s : a.S - 1;
+    bool low = false;
+    for (int c = 0; c < a.C; c++) {
+        double cur[K];
+#pragma unroll
+        for (int i = 0; i < K; i++) cur[i] = 1.0;
+        for (int pc = 0; pc < a.nops; pc++) {
+            const int ox = as_uniform(reinterpret_cast<const int *>(a.ops))[2 * pc], oy = as_uniform(reinterpret_cast<const int *>(a.ops))[2 * pc + 1];
+            const int code = ox & 0xff;
+            if (code == OP_MATVEC || code == OP_TIP_SET || code == OP_TIP_MUL) {
+                if (code == OP_MATVEC) {
+#pragma unroll
+                    for (int j = 0; j < K; j++) xs[j][tid] = cur[j];
+                } else {
+                    gen_load_obs<K>(a, oy, sc, tid, xs);
+                }
+                const double *M = a.PS + ((size_t)c * E + as_uniform(op_edge)[pc]) * K * K;
+                double acc[K];
+#pragma unroll
+                for (int i = 0; i < K; i++) acc[i] = 0.0;
+                for (int j = 0; j < a.k; j++) {
+                    const double x = xs[j][tid];
+                    const double *col = M + j * K;
+#pragma unroll
+                    for (int i = 0; i < K; i++) acc[i] = fma(col[i], x, acc[i]);
+                }
+#pragma unroll
+                for (int i = 0; i < K; i++) cur[i] = code == OP_TIP_MUL ? cur[i] * acc[i] : acc[i];
+            } else if (code == OP_PUSH) {
+                double *sp = a.slots + (size_t)oy * a.k * a.S + sc;
+#pragma unroll
+                for (int i = 0; i < K; i++)
+                    if (i < a.k && valid) sp[(size_t)i * a.S] = cur[i];
+            } else if (code == OP_POPMUL) {
+                const double *sp = a.slots + (size_t)oy * a.k * a.S + sc;
+#pragma unroll
+                for (int i = 0; i < K; i++)
+                    if (i < a.k) cur[i] *= valid ? sp[(size_t)i * a.S] : 1.0;
+            } else if (code == OP_NODE_MUL) {
+                gen_load_obs<K>(a, oy, sc, tid, xs);
+#pragma unroll
+                for (int i = 0; i < K; i++)
+                    if (i < a.k) cur[i] *= xs[i][tid];
+            } else if (code == OP_SCALE && !as_uniform(op_mid)[pc]) {
+                double m = 0.0;
+#pragma unroll
+                for (int i = 0; i < K; i++) m = fmax(m, cur[i]);
+                if (!(m >= 0x1p-969)) low = true;
+                const int e = frexp_exp(m);
+#pragma unroll
+                for (int i = 0; i < K; i++) cur[i] = ldexp(cur[i], -e);
+            }
+        }
+        double m = 0.0;
+#pragma unroll
+        for (int i = 0; i < K; i++) m = fmax(m, cur[i]);
+        if (!(m >= 0x1p-969)) low = true;
+    }
+    if (low && valid) *flag = 1;
+}
+
 #include "plk_catpost.h"
 
 /* ====================================================================== */
@@ -2594,6 +2670,60 @@ static int updown_finish(plk_engine *h, double *sums_out, const std::vector<long
     return PLK_OK;
 }
 
+template <int K>
+static void launch_range_check(plk_engine *h, const GenArgs &a, unsigned grid, const int *op_edge, const int *op_mid, int *flag)
+{
+    hipLaunchKernelGGL(k_range_check<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, h->E, op_edge, op_mid, flag);
+}
+
+/*
+ * The passes that store node vectors (derivatives, marginals, edge expectations, pair sums, mixture gradients, second
+ * order) keep ONE power-of-two factor per node (SC) and multiply all of a node's children before they look at the
+ * magnitude; the program's OP_SCALE ops inside a node are not taken there (plk_chain_build).  On a tree that has such a
+ * node (PlkProgram::mid_scales, e.g. a root over three deep subtrees, or 33 leaf children) the products are measured
+ * first (k_range_check, one extra traversal without output): with ordinary branch lengths they stay far inside the
+ * double range and the query runs as on any tree; where one falls below 2^-969 the query is refused, not miscomputed.
+ * Trees without such a node -- every tree whose nodes have at most two children -- pay nothing.  P is current here.
+ */
+static int check_stored_range(plk_engine *h, const char *who)
+{
+    int rc;
+    if (h->prog_dirty && (rc = build_program(h))) return rc;
+    const PlkProgram &pg = h->pg;
+    if (pg.mid_scales == 0 || pg.ops.empty()) return PLK_OK;
+    const int k = h->k, K = h->K, C = h->C, E = h->E;
+    const long S = h->S;
+    const size_t strm = ((size_t)C * E * K * K + 31) / 32 * 32;
+    if ((rc = dev_reserve(h, &h->d_uvmat, &h->uvmat_cap, strm))) return rc;
+    if ((rc = dev_reserve(h, &h->d_slots, &h->slots_cap, (size_t)std::max(pg.slots_needed, 1) * k * S))) return rc;
+    hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(K * K >= 256 ? 256 : 64), 0, h->stream, k, K, 0, h->d_P, h->d_uvmat);
+    IntPack pack;
+    std::vector<int> mid(pg.op_mid.begin(), pg.op_mid.end()), edge(pg.op_edge);
+    for (int &e : edge) if (e < 0) e = 0;                   /* ops without an edge read no matrix */
+    const size_t o_ops = pack.put(reinterpret_cast<const int *>(pg.ops.data()), 2 * pg.ops.size());
+    const size_t o_edge = pack.put(edge.data(), edge.size()), o_mid = pack.put(mid.data(), mid.size());
+    if ((rc = pack.upload(h))) return rc;
+    int *d_flag = pack.flag(h);
+    HIPCHK(h, hipMemsetAsync(d_flag, 0, sizeof(int), h->stream));
+    GenArgs a = {};
+    a.S = S; a.Spad = h->Spad; a.k = k; a.C = C; a.nops = (int)pg.ops.size(); a.nchar = h->nchar;
+    a.pat_mode = h->pat_mode; a.root_mode = h->root_mode; a.ops = reinterpret_cast<const int2 *>(h->d_u4pack + o_ops); a.PS = h->d_uvmat;
+    a.codes = h->d_codes; a.defs = h->d_defs; a.B = h->d_B; a.slots = h->d_slots;
+    const unsigned grid = (unsigned)((S + GEN_BLOCK - 1) / GEN_BLOCK);
+    dispatch_K(K, [&](auto Kc) { launch_range_check<decltype(Kc)::value>(h, a, grid, h->d_u4pack + o_edge, h->d_u4pack + o_mid, d_flag); });
+    HIPCHK(h, hipGetLastError());
+    int low = 0;
+    HIPCHK(h, hipMemcpyAsync(&low, d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!low) return PLK_OK;
+    const int nd = pg.wide_node;
+    h->err = std::string(who) + ": the product of the children of a node leaves the double range (largest entry below 2^-969 at some site; "
+             "node " + std::to_string(nd) + " with " + std::to_string(h->indptr[nd + 1] - h->indptr[nd]) + " children is the first that takes more than " +
+             std::to_string(PLK_SCALE_RUN) + " edge factors at once): this query keeps one rescaling factor per node and refuses such data "
+             "(the log likelihood and category posterior queries rescale inside the node and answer)";
+    return PLK_E_ARG;
+}
+
 template <int T>
 static void launch_updown_mfma(plk_engine *h, const MUpArgs &a, const MDownProg &pg, unsigned grid, size_t lds, bool deriv, bool marg, bool nodes)
 {
@@ -3115,6 +3245,8 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
+    if ((rc = check_stored_range(h, ps ? (ps->mix_D ? "plk_mixture_sens" : "plk_edge_pair_sums/plk_rate_matrix_sens")
+                                       : marg ? (deriv ? "plk_deriv/plk_marginal" : "plk_marginal") : d_M_in ? "plk_edge_expect" : "plk_deriv"))) return rc;
     if (!d_M_in && !ps && (rc = ensure_dP(h))) return rc;
     const double *d_M = d_M_in ? d_M_in : h->d_dP;
     if (!ps) h->info_up4_path = 0;
@@ -4170,6 +4302,7 @@ extern "C" int plk_second_order(plk_engine *h, double *grad_sums_out /* [E][2] o
     if ((rc = ensure_dP(h))) return rc;
     const int E = h->E;
     if (E == 0) return PLK_OK;
+    if ((rc = check_stored_range(h, "plk_second_order/plk_hess"))) return rc;
     std::vector<long double> Hrow((size_t)E * E, 0.0L), G((size_t)E * E, 0.0L), gsum((size_t)E, 0.0L);
     if (use_hess4(h)) { h->info_updown_kernel = 5; rc = second_order_k4(h, Hrow, G, grad_sums_out ? gsum.data() : nullptr); }
     else { h->info_updown_kernel = 2; rc = second_order_generic(h, Hrow, G, grad_sums_out ? gsum.data() : nullptr); }

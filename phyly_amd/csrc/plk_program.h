@@ -49,42 +49,63 @@ struct PlkProgram {
     std::vector<int> op_edge;          /* CSR edge per op or -1 */
     std::vector<int> tip_edge;         /* CSR edge per tip slot */
     std::vector<char> scale_node;      /* N: node vectors rescaled here (every >= 16 accumulated edges) */
+    std::vector<char> mid_scale_node;  /* N: nodes with an OP_SCALE between two of their children (more than PLK_SCALE_RUN factors) */
+    int mid_scales = 0;                /* number of such nodes; 0 on every tree whose nodes have at most two children */
+    int wide_node = -1;                /* the first of them in program order, for messages */
+    std::vector<char> op_mid;          /* per op: 1 for an OP_SCALE inside a node (the passes that store node vectors skip those) */
     std::vector<int> obs_nodes;        /* nodes whose code rows the fused kernels stage, in order of first use */
     int slots_needed = 0;              /* Sethi-Ullman number of the tree = depth of the waiting-vector stack */
 };
+
+/* most edge factors a vector takes between two rescalings: a node is rescaled once 16 have accumulated, so the product of
+ * two children holds at most 2 * 16 */
+#define PLK_SCALE_RUN 32
 
 /*
  * Post-order program of a rooted tree in CSR form (preorder[0] = root, parents first).  Internal children are
  * visited in order of decreasing stack need, so the stack depth is the tree's Sethi-Ullman number (<= log2 of the
  * leaf count for binary trees).  node_has_data[a] != 0 for internal nodes whose observation row is not all ones.
+ *
+ * Rescaling: a node's vector is rescaled after its last child once 16 or more edge factors have accumulated since the
+ * last rescaling below it (scale_node).  Under a node with many children that alone leaves the run unbounded, so an
+ * OP_SCALE is also placed INSIDE a node, before the child whose factors would take the run past PLK_SCALE_RUN
+ * (mid_scale_node).  A node whose run stays within PLK_SCALE_RUN gets none: every tree whose nodes have at most two
+ * children has the program it had before the rule existed.
  */
 static inline void plk_program_build(int N, const int *ip, const int *ix, const int *preorder,
                                      const char *node_has_data, PlkProgram &pg)
 {
     std::vector<int> need(N, 0), since(N, 0);
     pg.scale_node.assign(N, 0);
+    pg.mid_scale_node.assign(N, 0);
+    pg.mid_scales = 0; pg.wide_node = -1;
     std::vector<std::vector<int>> ichild(N); /* internal children (CSR edge idx), sorted by need desc */
     for (int u = N - 1; u >= 0; u--) {
         const int a = preorder[u];
         if (ip[a + 1] == ip[a]) continue;
         std::vector<int> &ic = ichild[a];
-        int acc = 0;
-        for (int idx = ip[a]; idx < ip[a + 1]; idx++) {
-            const int b = ix[idx];
-            acc += since[b] + 1;
-            if (ip[b + 1] > ip[b]) ic.push_back(idx);
-        }
+        for (int idx = ip[a]; idx < ip[a + 1]; idx++)
+            if (ip[ix[idx] + 1] > ip[ix[idx]]) ic.push_back(idx);
         std::stable_sort(ic.begin(), ic.end(), [&](int x, int y) { return need[ix[x]] > need[ix[y]]; });
         int nd = 0;
         for (size_t i = 0; i < ic.size(); i++) nd = std::max(nd, need[ix[ic[i]]] + (i > 0 ? 1 : 0));
         need[a] = nd;
-        if (acc >= 16) { pg.scale_node[a] = 1; acc = 0; }
+        /* the run of factors in the order of emission below: first internal child, leaves, further internal children */
+        int acc = 0;
+        auto merge = [&](int add) { if (acc + add > PLK_SCALE_RUN) { acc = 0; pg.mid_scale_node[a] = 1; } acc += add; };
+        if (!ic.empty()) merge(since[ix[ic[0]]] + 1);
+        for (int idx = ip[a]; idx < ip[a + 1]; idx++) if (ip[ix[idx] + 1] == ip[ix[idx]]) merge(1);
+        for (size_t i = 1; i < ic.size(); i++) merge(since[ix[ic[i]]] + 1);
+        if (pg.mid_scale_node[a]) pg.mid_scales++;
+        /* a node rescaled inside is always rescaled after its last child too: the passes that store node vectors, which skip
+         * the inner ones, then look at its magnitude there */
+        if (acc >= 16 || pg.mid_scale_node[a]) { pg.scale_node[a] = 1; acc = 0; }
         since[a] = acc;
     }
     const int root = preorder[0];
     pg.slots_needed = need[root];
 
-    pg.ops.clear(); pg.op_edge.clear(); pg.tip_edge.clear(); pg.obs_nodes.clear();
+    pg.ops.clear(); pg.op_edge.clear(); pg.tip_edge.clear(); pg.obs_nodes.clear(); pg.op_mid.clear();
     std::vector<int> obs_row(N, -1);
     auto obs = [&](int node) {
         if (obs_row[node] < 0) { obs_row[node] = (int)pg.obs_nodes.size(); pg.obs_nodes.push_back(node); }
@@ -92,27 +113,38 @@ static inline void plk_program_build(int N, const int *ip, const int *ix, const 
     };
     auto emit = [&](int code, int tslot, int arg, int edge) {
         plk_op2 o; o.x = code | (tslot << 8); o.y = arg;
-        pg.ops.push_back(o); pg.op_edge.push_back(edge);
+        pg.ops.push_back(o); pg.op_edge.push_back(edge); pg.op_mid.push_back(0);
     };
     /* iterative post-order emission; frame = (node, depth, stage) */
-    struct Frame { int a, depth, stage; bool started; };
+    struct Frame { int a, depth, stage; bool started; int run; };   /* run: factors in cur since its last OP_SCALE */
     std::vector<Frame> stk;
-    stk.push_back({root, 0, 0, false});
+    stk.push_back({root, 0, 0, false, 0});
+    /* OP_SCALE inside node a, before the child that brings `add` factors (the rule of merge() above) */
+    auto mid_scale = [&](Frame &f, int add) {
+        if (f.run + add > PLK_SCALE_RUN) {
+            emit(OP_SCALE, 0, f.a, -1);
+            pg.op_mid.back() = 1;
+            f.run = 0;
+            if (pg.wide_node < 0) pg.wide_node = f.a;
+        }
+        f.run += add;
+    };
     while (!stk.empty()) {
         Frame &f = stk.back();
         const int a = f.a;
         const std::vector<int> &ic = ichild[a];
         if (f.stage == 0) {
             f.stage = 1;
-            if (!ic.empty()) { const Frame nf = {ix[ic[0]], f.depth, 0, false}; stk.push_back(nf); continue; }
+            if (!ic.empty()) { const Frame nf = {ix[ic[0]], f.depth, 0, false, 0}; stk.push_back(nf); continue; }
         }
         if (f.stage == 1) {
-            if (!ic.empty()) { emit(OP_MATVEC, 0, 0, ic[0]); f.started = true; }
+            if (!ic.empty()) { emit(OP_MATVEC, 0, 0, ic[0]); f.started = true; f.run = since[ix[ic[0]]] + 1; }
             for (int idx = ip[a]; idx < ip[a + 1]; idx++) {
                 const int b = ix[idx];
                 if (ip[b + 1] > ip[b]) continue;
                 const int t = (int)pg.tip_edge.size();
                 pg.tip_edge.push_back(idx);
+                mid_scale(f, 1);
                 emit(f.started ? OP_TIP_MUL : OP_TIP_SET, t, b, idx);
                 obs(b);
                 f.started = true;
@@ -126,9 +158,10 @@ static inline void plk_program_build(int N, const int *ip, const int *ix, const 
                 emit(OP_POPMUL, 0, f.depth, -1);
             }
             if (i < (int)ic.size()) {
+                mid_scale(f, since[ix[ic[i]]] + 1);
                 emit(OP_PUSH, 0, f.depth, -1);
                 f.stage++;
-                const Frame nf = {ix[ic[i]], f.depth + 1, 0, false};
+                const Frame nf = {ix[ic[i]], f.depth + 1, 0, false, 0};
                 stk.push_back(nf);      /* invalidates f */
                 continue;
             }
@@ -156,8 +189,8 @@ static inline std::string plk_program_check(int N, const int *ip, const int *ix,
 {
     const int E = N - 1;
     const int nops = (int)pg.ops.size();
-    if ((int)pg.op_edge.size() != nops) return "program: op_edge size";
-    if ((int)pg.scale_node.size() != N) return "program: scale_node size";
+    if ((int)pg.op_edge.size() != nops || (int)pg.op_mid.size() != nops) return "program: op_edge size";
+    if ((int)pg.scale_node.size() != N || (int)pg.mid_scale_node.size() != N) return "program: scale_node size";
     if (pg.slots_needed < 0) return "program: negative stack depth";
     std::vector<int> edge_seen(std::max(E, 1), 0), tip_seen(pg.tip_edge.size(), 0);
     std::vector<char> slot_full(std::max(pg.slots_needed, 1), 0);
@@ -191,7 +224,7 @@ static inline std::string plk_program_check(int N, const int *ip, const int *ix,
             if (y < 0 || y >= N || ip[y + 1] == ip[y] || !node_has_data[y] || !have_cur) return plk_fmt("program: op %ld: bad NODE_MUL", pc);
             break;
         case OP_SCALE:
-            if (y < 0 || y >= N || !pg.scale_node[y] || !have_cur) return plk_fmt("program: op %ld: bad SCALE", pc);
+            if (y < 0 || y >= N || !(pg.scale_node[y] || pg.mid_scale_node[y]) || !have_cur) return plk_fmt("program: op %ld: bad SCALE", pc);
             break;
         default:
             return plk_fmt("program: op %ld: unknown opcode %ld", pc, code);
@@ -1340,7 +1373,8 @@ static inline void plk_chain_build(int N, const PlkProgram &pg, int mode, const 
             if (mode >= 1 && skip_store && skip_store[indices[o.y]]) o.z = -1;      /* this child's vector is not stored */
             if (mode == 2) o.w = edge_int[o.y];
         } else if (code == OP_SCALE && mode >= 1 && node_scale) {
-            o.y = node_scale[pg.ops[pc].y];
+            /* one stored factor per node: the OP_SCALE inside a node is not taken (y = -1), the one after its last child is */
+            o.y = pc < pg.op_mid.size() && pg.op_mid[pc] ? -1 : node_scale[pg.ops[pc].y];
         }
         ch.ops[pc] = o;
     }

@@ -5,7 +5,8 @@
  * usage: progcheck                      seeded random trees of every shape the engine accepts
  *        progcheck <file>               trees from a file, one per line: "N nchar  a0 b0 a1 b1 ... | h0 h1 ... hN-1"
  *                                       (edges parent child in user order; h = 1 for nodes that carry data)
- * For every tree: program build + invariants, fused formats for every kernel variant the engine could launch
+ * For every tree: program build + invariants, the rescaling bound (at most PLK_SCALE_RUN edge factors between two OP_SCALE,
+ * and the end-of-node rule's program wherever that rule keeps the bound by itself), fused formats for every kernel variant the engine could launch
  * (assembly interpreter with 4-bit and 8-bit codes, C++ interpreter with one and two sites per lane), the chained
  * programs of the three down passes; and negative controls (corrupted words must be refused).
  * Before the trees: a table of site-chunk plans (plk_site_chunk) against the rules the drivers used to spell out inline.
@@ -15,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <random>
 #include <string>
 #include <vector>
@@ -42,6 +44,112 @@ static bool make_tree(int N, const std::vector<int> &ea, const std::vector<int> 
 }
 
 static long g_ops = 0;
+
+/* ------------------------------------------------------------------------------------------------------------ */
+/* dynamic range: how many edge factors a vector takes between two rescalings                                     */
+/* ------------------------------------------------------------------------------------------------------------ */
+
+/* Replays the program and counts, for cur and for every stack slot, the edge factors multiplied in since the vector's last
+ * OP_SCALE: MATVEC, TIP_SET and TIP_MUL add one, POPMUL adds the popped count, SCALE resets.  Returns the largest count any
+ * vector reaches.  (The interpreters look at a vector's magnitude at OP_SCALE only, so this is what bounds its range.) */
+static int max_unscaled_run(const PlkProgram &pg)
+{
+    std::vector<int> slot(std::max(pg.slots_needed, 1), 0);
+    int cur = 0, worst = 0;
+    for (size_t pc = 0; pc < pg.ops.size(); pc++) {
+        const int code = pg.ops[pc].x & 0xff, y = pg.ops[pc].y;
+        if (code == OP_TIP_SET) cur = 1;
+        else if (code == OP_TIP_MUL || code == OP_MATVEC) cur += 1;
+        else if (code == OP_PUSH) { slot[y] = cur; cur = 0; }
+        else if (code == OP_POPMUL) cur += slot[y];
+        else if (code == OP_SCALE) cur = 0;
+        worst = std::max(worst, cur);
+    }
+    return worst;
+}
+
+/* The rescaling rule before OP_SCALE could stand inside a node, restated: a node is marked once 16 or more edges have
+ * accumulated over ALL its children, and its one OP_SCALE follows its last op.  Same traversal, same op order. */
+static void program_build_end_of_node_rule(const Tree &t, const std::vector<char> &has, PlkProgram &pg)
+{
+    const int N = t.N;
+    const int *ip = t.ip.data(), *ix = t.ix.data();
+    std::vector<int> need(N, 0), since(N, 0);
+    pg.scale_node.assign(N, 0); pg.mid_scale_node.assign(N, 0); pg.mid_scales = 0; pg.wide_node = -1; pg.op_mid.clear();
+    std::vector<std::vector<int>> ichild(N);
+    for (int u = N - 1; u >= 0; u--) {
+        const int a = t.pre[u];
+        if (ip[a + 1] == ip[a]) continue;
+        std::vector<int> &ic = ichild[a];
+        int acc = 0;
+        for (int idx = ip[a]; idx < ip[a + 1]; idx++) { acc += since[ix[idx]] + 1; if (ip[ix[idx] + 1] > ip[ix[idx]]) ic.push_back(idx); }
+        std::stable_sort(ic.begin(), ic.end(), [&](int x, int y) { return need[ix[x]] > need[ix[y]]; });
+        for (size_t i = 0; i < ic.size(); i++) need[a] = std::max(need[a], need[ix[ic[i]]] + (i > 0 ? 1 : 0));
+        if (acc >= 16) { pg.scale_node[a] = 1; acc = 0; }
+        since[a] = acc;
+    }
+    pg.slots_needed = need[t.pre[0]];
+    pg.ops.clear(); pg.op_edge.clear(); pg.tip_edge.clear(); pg.obs_nodes.clear();
+    std::vector<char> staged(N, 0);
+    auto obs = [&](int node) { if (!staged[node]) { staged[node] = 1; pg.obs_nodes.push_back(node); } };
+    auto emit = [&](int code, int tslot, int arg, int edge) { pg.ops.push_back(plk_op2{code | (tslot << 8), arg}); pg.op_edge.push_back(edge); pg.op_mid.push_back(0); };
+    std::function<void(int, int)> go = [&](int a, int depth) {
+        const std::vector<int> &ic = ichild[a];
+        bool started = false;
+        if (!ic.empty()) { go(ix[ic[0]], depth); emit(OP_MATVEC, 0, 0, ic[0]); started = true; }
+        for (int idx = ip[a]; idx < ip[a + 1]; idx++) {
+            const int b = ix[idx];
+            if (ip[b + 1] > ip[b]) continue;
+            const int ts = (int)pg.tip_edge.size();
+            pg.tip_edge.push_back(idx);
+            emit(started ? OP_TIP_MUL : OP_TIP_SET, ts, b, idx);
+            obs(b);
+            started = true;
+        }
+        for (size_t i = 1; i < ic.size(); i++) {
+            emit(OP_PUSH, 0, depth, -1);
+            go(ix[ic[i]], depth + 1);
+            emit(OP_MATVEC, 0, 0, ic[i]);
+            emit(OP_POPMUL, 0, depth, -1);
+        }
+        if (has[a]) { emit(OP_NODE_MUL, 0, a, -1); obs(a); }
+        if (pg.scale_node[a]) emit(OP_SCALE, 0, a, -1);
+    };
+    go(t.pre[0], 0);
+}
+
+static bool same_program(const PlkProgram &p, const PlkProgram &q)
+{
+    if (p.ops.size() != q.ops.size() || p.op_edge != q.op_edge || p.tip_edge != q.tip_edge || p.scale_node != q.scale_node ||
+        p.obs_nodes != q.obs_nodes || p.slots_needed != q.slots_needed) return false;
+    for (size_t i = 0; i < p.ops.size(); i++) if (p.ops[i].x != q.ops[i].x || p.ops[i].y != q.ops[i].y) return false;
+    return true;
+}
+
+static long g_mid_scaled = 0, g_same_as_before = 0;
+
+/* The bound of the rescaling rule on one tree: no vector takes more than PLK_SCALE_RUN factors between two rescalings; and
+ * wherever the end-of-node rule alone keeps that bound -- every tree whose nodes have at most two children among them -- the
+ * program is that rule's program op for op, with no OP_SCALE inside a node. */
+static std::string check_scale_runs(const Tree &t, const std::vector<char> &has, const PlkProgram &pg)
+{
+    const int run = max_unscaled_run(pg);
+    if (run > PLK_SCALE_RUN) return plk_fmt("rescaling: a vector takes %ld factors between two rescalings (bound %ld)", run, PLK_SCALE_RUN);
+    int max_deg = 0;
+    for (int a = 0; a < t.N; a++) max_deg = std::max(max_deg, t.ip[a + 1] - t.ip[a]);
+    PlkProgram old;
+    program_build_end_of_node_rule(t, has, old);
+    const int old_run = max_unscaled_run(old);
+    if (max_deg <= 2 && old_run > PLK_SCALE_RUN) return "rescaling: the end-of-node rule exceeds its own bound on a tree of degree two";
+    if (old_run <= PLK_SCALE_RUN) {
+        if (pg.mid_scales != 0 || pg.wide_node >= 0 || !same_program(pg, old)) return "rescaling: the program differs from the end-of-node rule's although that rule keeps the bound";
+        g_same_as_before++;
+    } else {
+        if (pg.mid_scales < 1 || pg.wide_node < 0 || !pg.mid_scale_node[pg.wide_node]) return "rescaling: the end-of-node rule exceeds the bound but no node is rescaled inside";
+        g_mid_scaled++;
+    }
+    return "";
+}
 
 /* Invariants of PlkStorageMaps: edge_tip / edge_int partition the edges; node_int >= 0 exactly for the nodes with children;
  * node_scale >= 0 only on a stored node the program rescales; every index is dense and increasing; the counts and the
@@ -80,6 +188,8 @@ static std::string check_tree(const Tree &t, const std::vector<char> &has, int n
     plk_program_build(N, t.ip.data(), t.ix.data(), t.pre.data(), has.data(), pg);
     g_ops += (long)pg.ops.size();
     std::string bad = plk_program_check(N, t.ip.data(), t.ix.data(), t.pre.data(), has.data(), pg);
+    if (!bad.empty()) return bad;
+    bad = check_scale_runs(t, has, pg);
     if (!bad.empty()) return bad;
     /* storage indices: the function the down / up drivers call, and its invariants; everything below runs on these maps */
     const int E = N - 1;
@@ -728,6 +838,75 @@ static std::string check_k4_constructed()
     return "";
 }
 
+/* The rescaling bound on constructed wide nodes, each through every check of check_tree, and the negative control: on the
+ * m-leaf star the end-of-node rule lets the root vector take all m factors, and the replay says so. */
+static std::string check_scale_constructed()
+{
+    Tree t;
+    std::string bad;
+    auto run_case = [&](const std::vector<int> &parent, const char *what, int wide, bool data_on_wide) -> std::string {
+        if (!tree_from_parents(parent, t)) return std::string(what) + ": not a tree";
+        std::vector<char> has(t.N, 0);
+        if (data_on_wide) has[wide] = 1;
+        PlkProgram pg;
+        plk_program_build(t.N, t.ip.data(), t.ix.data(), t.pre.data(), has.data(), pg);
+        if (!pg.mid_scale_node[wide] || pg.mid_scales < 1) return std::string(what) + ": the wide node is not rescaled inside";
+        const std::string b = check_tree(t, has, 5);
+        return b.empty() ? b : std::string(what) + ": " + b;
+    };
+    /* a star of 1000 leaves */
+    if (!(bad = run_case(std::vector<int>(1001, 0), "star of 1000", 0, false)).empty()) return bad;
+    /* a root with 40 leaf children and 40 internal children (cherries) */
+    {
+        std::vector<int> parent(1 + 40 + 40 + 80, 0);
+        for (int i = 0; i < 80; i++) parent[81 + i] = 41 + i / 2;
+        if (!(bad = run_case(parent, "40 leaves and 40 cherries under one node", 0, true)).empty()) return bad;
+    }
+    /* a caterpillar of 8 leaves whose node at depth 3 (node 6) also has 60 leaf children and 6 cherries, and below them a
+     * unary node */
+    {
+        std::vector<int> parent(15, 0);
+        for (int i = 1; i < 15; i++) parent[i] = i % 2 ? i - 1 : i - 2;
+        for (int i = 0; i < 60; i++) parent.push_back(6);
+        const int c0 = (int)parent.size();
+        for (int i = 0; i < 6; i++) parent.push_back(6);
+        for (int i = 0; i < 12; i++) parent.push_back(c0 + i / 2);
+        const int un = (int)parent.size();
+        parent.push_back(6);       /* unary node ... */
+        parent.push_back(un);      /* ... over one leaf */
+        if (!(bad = run_case(parent, "wide node at depth 3 of a caterpillar", 6, true)).empty()) return bad;
+    }
+    /* the benign shapes of tests/test_gpu_polytomy.py are rescaled inside too: a 40-leaf star, and a root over three 8-leaf
+     * caterpillars (every other node binary; runs of 16 + 16 + 16) */
+    if (!(bad = run_case(std::vector<int>(41, 0), "star of 40", 0, false)).empty()) return bad;
+    {
+        std::vector<int> parent(1, 0);
+        for (int c = 0; c < 3; c++) {
+            const int top = (int)parent.size();
+            parent.push_back(0);
+            for (int i = 1; i < 15; i++) parent.push_back(top + (i % 2 ? i - 1 : i - 2));
+        }
+        if (!(bad = run_case(parent, "root over three 8-leaf caterpillars", 0, false)).empty()) return bad;
+    }
+    /* stars around the bound: none inside up to PLK_SCALE_RUN leaves, one per PLK_SCALE_RUN leaves beyond */
+    const int ms[] = {2, 16, PLK_SCALE_RUN, PLK_SCALE_RUN + 1, 2 * PLK_SCALE_RUN, 2 * PLK_SCALE_RUN + 1, 70, 300, 1000};
+    for (int m : ms) {
+        tree_from_parents(std::vector<int>(m + 1, 0), t);
+        const std::vector<char> has(t.N, 0);
+        PlkProgram pg, old;
+        plk_program_build(t.N, t.ip.data(), t.ix.data(), t.pre.data(), has.data(), pg);
+        program_build_end_of_node_rule(t, has, old);
+        int nscale = 0;
+        for (const plk_op2 &o : pg.ops) nscale += (o.x & 0xff) == OP_SCALE;
+        const int inside = (m - 1) / PLK_SCALE_RUN, want = inside + (inside > 0 || m >= 16 ? 1 : 0);
+        if (nscale != want) return plk_fmt("star of %ld: %ld OP_SCALE, expected %ld", m, nscale, want);
+        if (max_unscaled_run(pg) != std::min(m, PLK_SCALE_RUN)) return plk_fmt("star of %ld: run of %ld", m, max_unscaled_run(pg));
+        /* negative control */
+        if (max_unscaled_run(old) != m) return plk_fmt("negative control: the replay reports %ld on the end-of-node program of the %ld-leaf star", max_unscaled_run(old), m);
+    }
+    return "";
+}
+
 int main(int argc, char **argv)
 {
     long ntrees = 0;
@@ -805,6 +984,9 @@ int main(int argc, char **argv)
         if (!bad.empty()) { fprintf(stderr, "balanced depth %d: %s\n", d, bad.c_str()); return 1; }
         ntrees++;
     }
+    { const std::string bad = check_scale_constructed(); if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; } }
+    fprintf(stderr, "rescaling: %ld trees with an OP_SCALE inside a node, %ld with the end-of-node rule's program\n", g_mid_scaled, g_same_as_before);
+    if (g_mid_scaled < 20 || g_same_as_before < 3000) { fprintf(stderr, "rescaling: the sweep does not reach both kinds of tree\n"); return 1; }
     /* the k = 4 choice on constructed trees, then: every outcome of the choice was reached (the sweep cannot pass vacuously) */
     { const std::string bad = check_k4_constructed(); if (!bad.empty()) { fprintf(stderr, "%s\n", bad.c_str()); return 1; } }
     for (int q = 0; q < OUT_COUNT; q++) {

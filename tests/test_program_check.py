@@ -5,6 +5,11 @@ The engine refuses to launch a kernel whose program, LDS image or register-stack
 (PLK_E_ARG); this test runs the same builder + replays over
   * 6000 seeded random trees of every shape (chains, stars, caterpillars, complete binary / ternary, random
     multifurcating, 2..3500 nodes, data on internal nodes, 1..256 character definitions) with negative controls,
+  * the rescaling rule on every one of them and on constructed wide nodes (a star of 1000 leaves, 40 leaves and 40 cherries
+    under one node, a wide node at depth 3 of a caterpillar): a replay counts the edge factors each vector takes between
+    two OP_SCALE and finds at most PLK_SCALE_RUN = 32; wherever the end-of-node rule (restated in the driver) keeps that
+    bound by itself -- every tree whose nodes have at most two children -- the program is that rule's, op for op; and
+    the replay reports m on the end-of-node program of the m-leaf star (negative control),
   * the trees and definition counts of the seeded random JSON queries of tests/test_gpu_differential.py as the host
     layer hands them to the engine once probability arrays are compacted to codes (every distinct row a definition),
   * the choice of the k = 4 ll kernel (plk_k4_choose): a sweep over every 40th random tree, caterpillars and balanced trees,
@@ -15,6 +20,7 @@ The engine refuses to launch a kernel whose program, LDS image or register-stack
 """
 import os
 import random
+import re
 import subprocess
 
 import pytest
@@ -41,6 +47,9 @@ def test_random_trees_every_variant(binary):
     assert r.returncode == 0, r.stderr[-3000:]
     tag, trees, ops = r.stdout.split()
     assert tag == "ok" and int(trees) >= 6000 and int(ops) > 100000
+    # the rescaling check met both kinds of tree: rescaled inside a node, and unchanged from the end-of-node rule
+    m = re.search(r"rescaling: (\d+) trees with an OP_SCALE inside a node, (\d+) with the end-of-node rule's program", r.stderr)
+    assert m and int(m.group(1)) >= 20 and int(m.group(2)) >= 3000, r.stderr[-3000:]
 
 
 def test_differential_generator_inputs(binary, tmp_path):
