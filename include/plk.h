@@ -403,9 +403,14 @@ enum {
                                        expectations, and the pair-sum and mixture-gradient passes): 4, 8 or 16 = k_down_fused4<D>
                                        with a register stack of that depth, 0 = k_down_store4 (the staged code rows do not fit
                                        the LDS, or the tree needs more than 16 slots) or no such query yet */
-    PLK_INFO_LL_FORM = 19           /* form of the last ll evaluation's k = 4 pair-table kernel: 1 = streamed codes with the tables
+    PLK_INFO_LL_FORM = 19,          /* form of the last ll evaluation's k = 4 pair-table kernel: 1 = streamed codes with the tables
                                        of all categories resident in LDS (k_ll_fused4_v4s; PLK_INFO_LL_VARIANT reports 6),
                                        0 = a tile kernel or another family */
+    PLK_INFO_LL_FOLD = 20           /* op stream of the last ll evaluation's streamed kernel (0 for every other kernel), bit fields:
+                                       bit 0 = the folded op stream ran, bit 1 = the first chunks of a unit were held across the
+                                       categories, bits 4-7 = stack slots d whose MATVEC + POPMUL + SCALE handler the stream
+                                       dispatches, bits 8-15 = SCALE ops left with a dispatch of their own, bits 16-23 / 24-30 =
+                                       observation ops of one category with ADVANCE_0 / ADVANCE_1 folded in (saturating) */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -440,7 +445,11 @@ enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PE
                                LDS (k_ll_fused4_v4s) wherever C x table bytes fit the LDS and the stream fits device
                                memory, otherwise as 1; the default takes that form under the same conditions.  + 8: without the
                                scalar-cache warm-up; streamed form, + 16: its waves meet before every unit instead of every
-                               category, + 32: never (measurements) */,
+                               category, + 32: never (measurements); + 64: the streamed form without the folded op
+                               stream and without the held first chunks (the checked stream as it is built, ADVANCE and SCALE
+                               ops dispatched on their own, every category requesting the unit's first three chunks itself:
+                               the kernel as it was before the fold, and what runs when the fold does not replay);
+                               + 128: without the held chunks only, + 256: without the fold only (measurements) */,
        PLK_OPT_VEC_REG_STACK = 7 /* 1 (default): the vector kernels (9 <= k <= 20) keep the three busiest stack slots in
                                registers (2 waves per SIMD); 0: every waiting vector goes through HBM slots (round 2) */,
        PLK_OPT_MFMA_NS2 = 8 /* 1: the matrix-core ll kernel for 33 <= k <= 64 gives a wave two groups of 16 sites (every staged

@@ -64,6 +64,8 @@ struct LlPlan {
     bool vec_rs = false;                 /* LL_VEC: register stack, and its window of three slots */
     int vec_reg_lo = 0;
     long info_variant = 0, info_form = 0, info_exec_flops = 0;     /* PLK_INFO_LL_VARIANT, _FORM, _LL_EXEC_FLOPS */
+    bool fold = false, held = false;     /* streamed form: the folded op stream is the one uploaded; first chunks held */
+    long info_fold = 0;                  /* PLK_INFO_LL_FOLD */
 };
 
 struct plk_engine {
@@ -114,6 +116,7 @@ struct plk_engine {
      * tables_dirty: the P-dependent tables (matrix stream, tip tables, A fragments) are older than P */
     bool prog_dirty = true, fmt_dirty = true, tables_dirty = true;
     LlPlan plan;                         /* which ll kernel runs, and how: written by upload_formats, valid while !fmt_dirty */
+    bool k4_held_ok = false;             /* k_ll_fused4_v4s<768, true> can be described and has the static LDS of <768, false> */
     size_t k4_static_lds[3] = {};        /* PlkK4Shape::static_lds, asked of the runtime once (k4_static_lds_known) */
     hipError_t k4_static_lds_err[3] = {};
     bool k4_static_lds_known = false;
@@ -130,6 +133,7 @@ struct plk_engine {
     PlkFusedV4 fv4;                      /* 64-bit ops of the two-sites-per-lane interpreter */
     PlkVecPT vpt;                        /* the vector ll kernel's program on pair tables */
     PlkFusedV4S fv4s;                    /* streamed codes (k_ll_fused4_v4s): one op stream per category */
+    PlkFusedV4SFold fv4s_fold;           /* ... and its folded form, the one the kernel runs unless PLK_OPT_PAIR_TABLES + 64 / + 256 */
     unsigned *d_cstream = nullptr; size_t cstream_cap = 0;   /* the code stream (plk_stream_dword), built by upload_formats */
     int *d_obs_row = nullptr;            /* staged row per observation of the program */
     int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [2][rows] staged-row nodes; [4][ntab] unit, edge, leaf edges of a pair */
@@ -187,7 +191,7 @@ struct plk_engine {
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
-    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
+    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
 static std::string g_create_error;
@@ -1564,6 +1568,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_DOWN4_KERNEL: *out = h->info_down4_kernel; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
     case PLK_INFO_LL_FORM: *out = h->info_ll_form; return PLK_OK;
+    case PLK_INFO_LL_FOLD: *out = h->info_ll_fold; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && h->plan.pair_tables ? h->plan.npairs : 0; return PLK_OK;
     case PLK_INFO_STACK_SLOTS: *out = h->slots_needed; return PLK_OK;
@@ -1968,6 +1973,10 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
             if (h->k4_static_lds_err[i] == hipSuccess) h->k4_static_lds[i] = fa.sharedSizeBytes;
             else (void)hipGetLastError();
         }
+        /* the held-chunks instantiation of the streamed kernel shares the plan's table base: it runs only if it has the same static LDS */
+        hipFuncAttributes fh;
+        if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true>) != hipSuccess) (void)hipGetLastError();
+        else h->k4_held_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
         h->k4_static_lds_known = true;
     }
     PlkK4Shape sh = {h->nchar, h->C, h->S, h->num_cus, h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
@@ -1988,6 +1997,19 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     p.block = c.block; p.wg_sites = c.tile; p.lds = c.lds;
     p.info_variant = c.variant == PLK_K4_CPP ? 3 : c.variant == PLK_K4_ASM ? 1 : c.variant == PLK_K4_ASM_PT ? 5 : 6;
     p.info_form = c.variant == PLK_K4_V4S ? 1 : 0;
+    p.fold = false; p.held = c.variant == PLK_K4_V4S && c.held && h->k4_held_ok; p.info_fold = p.held ? 2 : 0;
+    if (c.variant == PLK_K4_V4S && c.fold) {
+        /* the folded stream is derived from the checked one and replayed against it; a fold that does not replay is not
+         * run: the checked stream is, and the engine's error text says why */
+        plk_fused_v4s_fold(h->fv4s, h->fv4s_fold);
+        const std::string bad = plk_fused_check_v4s_fold(h->fv4s, h->fv4s_fold);
+        if (bad.empty()) {
+            const PlkFusedV4SFold &fo = h->fv4s_fold;
+            p.fold = true;
+            p.info_fold |= 1 | (long)(fo.scale_slots & 15) << 4 | (long)std::min(fo.standalone_scale, 255) << 8 |
+                           (long)std::min(fo.nadv[0], 255) << 16 | (long)std::min(fo.nadv[1], 127) << 24;
+        } else h->err = "internal: " + bad + " (the unfolded op stream runs)";
+    }
     const int ntips = (int)h->tip_edge.size();
     if (c.variant == PLK_K4_CPP || c.variant == PLK_K4_ASM) {
         /* int4 ops of the C++ interpreter, 32-bit op words of the assembly interpreter, compact matrix list */
@@ -2015,7 +2037,7 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
      * are built from the unrounded P after it (k_build_tables_pt) */
     const PlkFusedPT &f = h->fpt;
     p.pair_tables = true; p.npairs = f.npairs;
-    const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? h->fv4s.words : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
+    const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? (p.fold ? h->fv4s_fold.words : h->fv4s.words) : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
     if ((rc = dev_upload(h, &h->d_words_pt, words.data(), words.size()))) return rc;
     /* d_obs_row before the pair-table lists: the order in which these buffers were first allocated when the kernels were
      * measured (with it after them, the streamed kernel at 1.25M sites of BASELINE config 3 ran 0.3 % longer) */
@@ -2292,10 +2314,11 @@ static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool 
         if (c.variant == PLK_K4_V4S) {
             FusedV4SArgs sa;
             sa.pt = pa;
-            sa.pt.nwords = (int)h->fv4s.stride;
+            sa.pt.nwords = (int)(p.fold ? h->fv4s_fold.stride : h->fv4s.stride);
             sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
             sa.sync = c.sync;
-            hipLaunchKernelGGL(k_ll_fused4_v4s<768>, dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            if (p.held) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            else hipLaunchKernelGGL((k_ll_fused4_v4s<768, false>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
         } else if (c.variant == PLK_K4_V4) {
             FusedV4Args va;
             va.pt = pa; va.first_y = h->fv4.first_y; va.first_z = h->fv4.first_z; va.second_z = h->fv4.second_z;
@@ -2429,7 +2452,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     default: rc = launch_ll_generic(h, p, d_out, want_sum, &npartials); break;
     }
     if (rc) return rc;
-    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_exec_flops = p.info_exec_flops;
+    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_exec_flops = p.info_exec_flops;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->evk[evi][1], h->stream));
     h->evk_pending[evi] = true;

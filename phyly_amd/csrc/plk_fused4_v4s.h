@@ -18,6 +18,13 @@
  * from the current dword (v_bfe_u32) and keeps two chunks in flight; per site the arithmetic is k_ll_fused4_v4's, instruction
  * for instruction, so site log likelihoods are bit-identical.  The sum differs in the order of its double-double terms
  * only: a wave keeps one running sum over its units (static assignment: reproducible) and writes one partial.
+ *
+ * Two things remove dispatches and one stall without touching that arithmetic (both off under PLK_OPT_PAIR_TABLES + 64):
+ * the op stream the kernel runs is the FOLDED one (plk_fused_v4s_fold in plk_program.h: an ADVANCE rides in the
+ * observation handler after it, a SCALE in the MATVEC + POPMUL before it; replayed against the checked stream before it is
+ * uploaded), and the HELD instantiation loads a unit's first three chunks once per unit instead of once per category --
+ * the next unit's while this unit's log and store run -- so that no category starts with all twelve waves of the CU waiting
+ * on the same three loads behind the barrier.
  */
 #ifndef PLK_FUSED4_V4S_H
 #define PLK_FUSED4_V4S_H
@@ -47,25 +54,36 @@ __global__ __launch_bounds__(256) void k_build_code_stream(const uint8_t *__rest
         site < (size_t)Spad ? plk_stream_site_dword(codes, (size_t)Spad, site, obs_row, nobs, row_nodes, nrows, nchar, chunk) : 0u;
 }
 
+/* HELD: the unit's first three chunks (c0 the current dword pair, c1 and c2 the two "in flight") are operands, loaded by
+ * the kernel once per unit; otherwise the statement requests them itself, in every category */
+template <bool HELD>
 __device__ __forceinline__ void fused_run_program_v4s(double &lha, double &lhb, int &ea, int &eb, const void *ops, const void *mstream,
                                                        const void *strm, unsigned voff, unsigned y0,
-                                                       double w0, double w1, double w2, double w3)
+                                                       double w0, double w1, double w2, double w3,
+                                                       unsigned long long c0, unsigned long long c1, unsigned long long c2)
 {
     int al, ah, bl, bh;
 #ifdef PLK_EXP_EMPTY
     al = bl = 0; ah = bh = 0x3ff00000; ea = eb = 0;
 #else
-    asm volatile(PLK_V4S_PROGRAM
-                 : [al] "=v"(al), [ah] "=v"(ah), [bl] "=v"(bl), [bh] "=v"(bh), [ea] "=v"(ea), [eb] "=v"(eb)
-                 : [voff] "v"(voff), [ops] "s"(ops), [mstream] "s"(mstream), [strm] "s"(strm), [y0] "s"(y0),
-                   [w0] "s"(w0), [w1] "s"(w1), [w2] "s"(w2), [w3] "s"(w3)
-                 : PLK_V4S_CLOBBERS);
+    if constexpr (HELD)
+        asm volatile(PLK_V4S_PROGRAM_HELD
+                     : [al] "=v"(al), [ah] "=v"(ah), [bl] "=v"(bl), [bh] "=v"(bh), [ea] "=v"(ea), [eb] "=v"(eb)
+                     : [voff] "v"(voff), [ops] "s"(ops), [mstream] "s"(mstream), [strm] "s"(strm), [y0] "s"(y0),
+                       [w0] "s"(w0), [w1] "s"(w1), [w2] "s"(w2), [w3] "s"(w3), [c0] "v"(c0), [c1] "v"(c1), [c2] "v"(c2)
+                     : PLK_V4S_CLOBBERS);
+    else
+        asm volatile(PLK_V4S_PROGRAM
+                     : [al] "=v"(al), [ah] "=v"(ah), [bl] "=v"(bl), [bh] "=v"(bh), [ea] "=v"(ea), [eb] "=v"(eb)
+                     : [voff] "v"(voff), [ops] "s"(ops), [mstream] "s"(mstream), [strm] "s"(strm), [y0] "s"(y0),
+                       [w0] "s"(w0), [w1] "s"(w1), [w2] "s"(w2), [w3] "s"(w3)
+                     : PLK_V4S_CLOBBERS);
 #endif
     lha = __hiloint2double(ah, al);
     lhb = __hiloint2double(bh, bl);
 }
 
-template <int THREADS>
+template <int THREADS, bool HELD = false>
 __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
 {
     constexpr int NW = THREADS / 64;
@@ -100,6 +118,21 @@ __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
     /* every wave makes the same number of passes (va.sync: the waves of the workgroup meet before every unit / category, so
      * that they read the same category's matrices and op words through the scalar cache at the same time) */
     const long stride = (long)gridDim.x * NW, passes = (nunits + stride - 1) / stride;
+    /* HELD: chunks 0 .. 2 of a unit are the same bytes in every category.  They are requested once per unit -- the next
+     * unit's before this unit's epilogue, the first unit's here -- and every category's prologue copies them.  A wave whose
+     * next unit does not exist requests nothing: no load goes past the stream (a unit has at least three chunks). */
+    unsigned long long c0 = 0, c1 = 0, c2 = 0;
+    auto request = [&](long unit) {
+        /* uniform base + the lane's 32-bit offset, formed here: a per-lane 64-bit address kept across the interpreter costs
+         * the two registers that decide between 168 VGPRs and a spill */
+        unsigned off = (unsigned)lane * 8u;
+        asm volatile("" : "+v"(off));
+        const char *p = reinterpret_cast<const char *>(va.stream + (size_t)unit * (size_t)va.chunks * PLK_V4S_UNIT) + off;
+        c0 = *reinterpret_cast<const unsigned long long *>(p);
+        c1 = *reinterpret_cast<const unsigned long long *>(p + PLK_V4S_CHUNK_BYTES);
+        c2 = *reinterpret_cast<const unsigned long long *>(p + 2 * PLK_V4S_CHUNK_BYTES);
+    };
+    if (HELD && (long)blockIdx.x * NW + wave < nunits) request((long)blockIdx.x * NW + wave);
     for (long pass = 0; pass < passes; pass++) {
         const long u = pass * stride + (long)blockIdx.x * NW + wave;
         const bool active = u < nunits;
@@ -121,8 +154,8 @@ __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
             }
             double lhs[2];
             int esc[2];
-            fused_run_program_v4s(lhs[0], lhs[1], esc[0], esc[1], ops, ps, strm, (unsigned)lane * 8u, va.first_y + (unsigned)c * cat32,
-                                  rw0, rw1, rw2, rw3);
+            fused_run_program_v4s<HELD>(lhs[0], lhs[1], esc[0], esc[1], ops, ps, strm, (unsigned)lane * 8u, va.first_y + (unsigned)c * cat32,
+                                        rw0, rw1, rw2, rw3, c0, c1, c2);
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const double lh = lhs[j];
@@ -134,6 +167,8 @@ __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
                 }
             }
         }
+        /* the next unit's first chunks travel while this unit's log, store and sum run */
+        if (HELD && u + stride < nunits) request(u + stride);
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const long s = u * PLK_V4S_UNIT + j * 64 + lane;

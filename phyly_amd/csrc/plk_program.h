@@ -1005,6 +1005,165 @@ static inline std::string plk_fused_check_v4s(const PlkFusedPT &fu, const PlkFus
 }
 
 /*
+ * The FOLDED op stream of k_ll_fused4_v4s: the checked stream above with fewer dispatches.  An ADVANCE_k op is removed and
+ * the observation op after it goes to handler PLK_V4S_FOLD_ADV + 2 j + k (j = plk_v4s_obs_index of its handler: the same
+ * arithmetic, ADVANCE_k, then the same extraction); a SCALE op after MATVEC + POPMUL slot d is removed and that op goes to
+ * handler PLK_V4S_FOLD_SCALE + d.  A SCALE after any other op keeps its own dispatch.  The result is cut into blocks of
+ * 7 ops and a REFILL again (two spare blocks), so a REFILL between the two ops of a pair does not stop the fold.  The
+ * fields of the ops are not touched: stream layout, byte offsets and table fields are the checked stream's.
+ */
+#define PLK_V4S_FOLD_ADV 36
+#define PLK_V4S_FOLD_SCALE 60
+
+struct PlkV4SOp { unsigned h, hi; };           /* handler index, field dword */
+
+static inline int plk_v4s_obs_index(unsigned hidx)
+{
+    if (hidx == OP_TIP_SET) return 0;
+    if (hidx == OP_TIP_MUL) return 1;
+    if (hidx == PLK_WORD_TIPMUL_NOWAIT) return 2;
+    if (hidx == PLK_WORD_MATVEC_TIPMUL) return 3;
+    if (hidx >= PLK_WORD_SET_POPMUL && hidx < PLK_WORD_SET_POPMUL + 4) return 4 + (int)(hidx - PLK_WORD_SET_POPMUL);
+    if (hidx >= PLK_WORD_SET_PUSH && hidx < PLK_WORD_SET_PUSH + 4) return 8 + (int)(hidx - PLK_WORD_SET_PUSH);
+    return -1;
+}
+static inline unsigned plk_v4s_obs_handler(int j)
+{
+    static const unsigned first[4] = {OP_TIP_SET, OP_TIP_MUL, PLK_WORD_TIPMUL_NOWAIT, PLK_WORD_MATVEC_TIPMUL};
+    return j < 4 ? first[j] : j < 8 ? PLK_WORD_SET_POPMUL + (unsigned)(j - 4) : PLK_WORD_SET_PUSH + (unsigned)(j - 8);
+}
+
+/* the ops of one category's stream up to (without) its END, REFILL ops left out; false: no END, or a handler offset off its grid */
+static inline bool plk_v4s_stream_ops(const unsigned *wd, size_t stride, std::vector<PlkV4SOp> &ops)
+{
+    ops.clear();
+    for (size_t i = 0; i < stride / 2; i++) {
+        if (i % 8 == 7) continue;
+        const unsigned lo = wd[2 * i];
+        if (lo % PLK_V4_HANDLER_BYTES != 0) return false;
+        if (lo / PLK_V4_HANDLER_BYTES == OP_END) return true;
+        ops.push_back(PlkV4SOp{lo / PLK_V4_HANDLER_BYTES, wd[2 * i + 1]});
+    }
+    return false;
+}
+
+static inline void plk_v4s_fold_ops(const std::vector<PlkV4SOp> &in, std::vector<PlkV4SOp> &out)
+{
+    out.clear();
+    int pending = -1;                                     /* kind of the ADVANCE waiting for its observation op */
+    for (const PlkV4SOp &op : in) {
+        if (pending >= 0) {
+            const int j = plk_v4s_obs_index(op.h);
+            if (j >= 0) { out.push_back(PlkV4SOp{(unsigned)(PLK_V4S_FOLD_ADV + 2 * j + pending), op.hi}); pending = -1; continue; }
+            out.push_back(PlkV4SOp{(unsigned)(PLK_V4S_ADVANCE + pending), 0u});
+            pending = -1;
+        }
+        if (op.h == (unsigned)PLK_V4S_ADVANCE || op.h == (unsigned)PLK_V4S_ADVANCE + 1) { pending = (int)(op.h - PLK_V4S_ADVANCE); continue; }
+        if (op.h == OP_SCALE && !out.empty() && out.back().h >= 28 && out.back().h < 32) { out.back().h += PLK_V4S_FOLD_SCALE - 28; continue; }
+        out.push_back(op);
+    }
+    if (pending >= 0) out.push_back(PlkV4SOp{(unsigned)(PLK_V4S_ADVANCE + pending), 0u});
+}
+
+/* what a folded op list executes, one handler's work per entry: the list plk_v4s_fold_ops was given, if it is a fold of one */
+static inline void plk_v4s_unfold_ops(const std::vector<PlkV4SOp> &in, std::vector<PlkV4SOp> &out)
+{
+    out.clear();
+    for (const PlkV4SOp &op : in) {
+        if (op.h >= PLK_V4S_FOLD_ADV && op.h < PLK_V4S_FOLD_SCALE) {
+            out.push_back(PlkV4SOp{(unsigned)PLK_V4S_ADVANCE + ((op.h - PLK_V4S_FOLD_ADV) & 1), 0u});
+            out.push_back(PlkV4SOp{plk_v4s_obs_handler((int)(op.h - PLK_V4S_FOLD_ADV) / 2), op.hi});
+        } else if (op.h >= PLK_V4S_FOLD_SCALE && op.h < PLK_V4S_FOLD_SCALE + 4) {
+            out.push_back(PlkV4SOp{28u + (op.h - PLK_V4S_FOLD_SCALE), op.hi});
+            out.push_back(PlkV4SOp{(unsigned)OP_SCALE, 0u});
+        } else out.push_back(op);
+    }
+}
+
+/* blocks of 7 ops + REFILL (A in even blocks, B in odd ones), the END, END padding, two spare blocks */
+static inline size_t plk_v4s_block_stride(size_t nops) { return ((nops + 1 + 6) / 7 + 2) * 16; }
+static inline void plk_v4s_block_ops(const std::vector<PlkV4SOp> &ops, unsigned *o, size_t stride)
+{
+    size_t src = 0;
+    for (size_t b = 0; b < stride / 16; b++)
+        for (int j = 0; j < 8; j++, o += 2) {
+            o[0] = o[1] = 0u;
+            if (j == 7) { o[0] = (unsigned)((b & 1) ? PLK_V4_REFILL_B : PLK_V4_REFILL_A) * PLK_V4_HANDLER_BYTES; continue; }
+            if (src < ops.size()) { o[0] = ops[src].h * PLK_V4_HANDLER_BYTES; o[1] = ops[src].hi; }
+            else o[0] = (unsigned)OP_END * PLK_V4_HANDLER_BYTES;
+            src++;
+        }
+}
+
+struct PlkFusedV4SFold {
+    std::vector<unsigned> words;       /* C streams of stride dwords, as PlkFusedV4S::words */
+    size_t stride = 0;
+    int nadv[2] = {0, 0};              /* folded ADVANCE_0 / ADVANCE_1 of one category */
+    int standalone_adv = 0, standalone_scale = 0;
+    unsigned scale_slots = 0;          /* bit d: MATVEC + POPMUL slot d + SCALE occurs */
+};
+
+/* vs: a stream plk_fused_check_v4s has accepted */
+static inline void plk_fused_v4s_fold(const PlkFusedV4S &vs, PlkFusedV4SFold &fo)
+{
+    fo = PlkFusedV4SFold();
+    std::vector<PlkV4SOp> ops, folded;
+    for (int c = 0; c < vs.C; c++) {
+        if (!plk_v4s_stream_ops(&vs.words[(size_t)c * vs.stride], vs.stride, ops)) { fo = PlkFusedV4SFold(); return; }
+        plk_v4s_fold_ops(ops, folded);
+        if (c == 0) {
+            fo.stride = plk_v4s_block_stride(folded.size());
+            fo.words.assign((size_t)vs.C * fo.stride, 0u);
+            for (const PlkV4SOp &op : folded) {
+                if (op.h >= PLK_V4S_FOLD_ADV && op.h < PLK_V4S_FOLD_SCALE) fo.nadv[(op.h - PLK_V4S_FOLD_ADV) & 1]++;
+                else if (op.h >= PLK_V4S_FOLD_SCALE && op.h < PLK_V4S_FOLD_SCALE + 4) fo.scale_slots |= 1u << (op.h - PLK_V4S_FOLD_SCALE);
+                else if (op.h == OP_SCALE) fo.standalone_scale++;
+                else if (op.h == (unsigned)PLK_V4S_ADVANCE || op.h == (unsigned)PLK_V4S_ADVANCE + 1) fo.standalone_adv++;
+            }
+        } else if (plk_v4s_block_stride(folded.size()) != fo.stride) { fo = PlkFusedV4SFold(); return; }
+        plk_v4s_block_ops(folded, &fo.words[(size_t)c * fo.stride], fo.stride);
+    }
+}
+
+/* Replays the folded stream against the checked one: every block ends in its REFILL (A, B, A, ... from A), handler offsets
+ * are on the grid and inside the table, an END is reached with two whole blocks after its block and nothing but END
+ * after it, and the ops, unfolded, are the checked stream's ops exactly -- handlers in order (so a folded ADVANCE has the
+ * kind of the op it replaces, and a + SCALE variant stands where a SCALE followed), table fields and bit offsets. */
+static inline std::string plk_fused_check_v4s_fold(const PlkFusedV4S &vs, const PlkFusedV4SFold &fo)
+{
+    if (fo.stride % 16 != 0 || fo.stride < 48 || fo.words.size() != (size_t)vs.C * fo.stride) return "v4s fold: word count";
+    std::vector<PlkV4SOp> want, got, un;
+    for (int c = 0; c < vs.C; c++) {
+        const unsigned *wd = &fo.words[(size_t)c * fo.stride];
+        const size_t nblocks = fo.stride / 16;
+        long end_block = -1;
+        got.clear();
+        for (size_t b = 0; b < nblocks; b++)
+            for (int j = 0; j < 8; j++) {
+                const unsigned lo = wd[(b * 8 + j) * 2], hi = wd[(b * 8 + j) * 2 + 1];
+                if (lo % PLK_V4_HANDLER_BYTES != 0 || lo >= (unsigned)PLK_V4_HANDLER_SLOTS * PLK_V4_HANDLER_BYTES) return plk_fmt("v4s fold: handler offset in block %ld", (long)b);
+                const unsigned hidx = lo / PLK_V4_HANDLER_BYTES;
+                if (j == 7) {
+                    if (hidx != (unsigned)((b & 1) ? PLK_V4_REFILL_B : PLK_V4_REFILL_A) || hi != 0) return plk_fmt("v4s fold: block %ld does not end in its REFILL op", (long)b);
+                    continue;
+                }
+                if (hidx == (unsigned)PLK_V4_REFILL_A || hidx == (unsigned)PLK_V4_REFILL_B) return plk_fmt("v4s fold: REFILL op inside block %ld", (long)b);
+                if (end_block >= 0) { if (hidx != OP_END || hi != 0) return "v4s fold: ops after END"; continue; }
+                if (hidx == OP_END) { if (hi != 0) return "v4s fold: stray fields in END"; end_block = (long)b; continue; }
+                got.push_back(PlkV4SOp{hidx, hi});
+            }
+        if (end_block < 0) return "v4s fold: no END";
+        if ((size_t)end_block + 2 >= nblocks) return "v4s fold: fewer than two spare blocks after the END";
+        if (!plk_v4s_stream_ops(&vs.words[(size_t)c * vs.stride], vs.stride, want)) return "v4s fold: the checked stream has no END";
+        plk_v4s_unfold_ops(got, un);
+        if (un.size() != want.size()) return plk_fmt("v4s fold: %ld ops unfolded, the checked stream has %ld", (long)un.size(), (long)want.size());
+        for (size_t i = 0; i < un.size(); i++)
+            if (un[i].h != want[i].h || un[i].hi != want[i].hi) return plk_fmt("v4s fold: unfolded op %ld is not the checked stream's", (long)i);
+    }
+    return "";
+}
+
+/*
  * The vector ll kernel (k_ll_vec, plk_vec.h) on the pair-table program: int4 ops
  *   observation (TIP_SET / TIP_MUL)  x = opcode, y = first row of the op's table (unit * nchar: the kernel adds the code),
  *                                    w = staged row of the NEXT observation op (cyclic)
@@ -1152,12 +1311,14 @@ enum { PLK_K4_LDS_V4S_768 = 0, PLK_K4_LDS_V4_768, PLK_K4_LDS_V4_512 };     /* Pl
 
 /* PLK_OPT_PAIR_TABLES: & 7 which pair-table kernel (0 with the whole value 0: none; 1 the default order; 2, 3, 5, 6 one
  * kernel and tile, forced; 7 the streamed form wherever it fits), + 8 without the scalar-cache warm-up, + 16 / + 32 the
- * waves of the streamed form meet before every unit only / never (default: before every category).  The + bits are for
- * measurements. */
-struct PlkPairTablesOpt { bool on; int mode, warm, sync; };
+ * waves of the streamed form meet before every unit only / never (default: before every category), + 64 the streamed form
+ * as it was before the folded op stream and the held first chunks (the checked stream unfolded, every category requests
+ * the unit's first three chunks itself), + 128 / + 256 without the held chunks only / without the fold only.  The + bits
+ * are for measurements. */
+struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held; };
 static inline PlkPairTablesOpt plk_pair_tables_opt(long v)
 {
-    return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2};
+    return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2, (v & (64 | 256)) ? 0 : 1, (v & (64 | 128)) ? 0 : 1};
 }
 
 struct PlkK4Shape {
@@ -1176,6 +1337,7 @@ struct PlkK4Choice {
     size_t lds = 0;                                  /* dynamic LDS of the launch */
     unsigned tip_base = 0;                           /* v4 / v4s: LDS address of the table image = static LDS of the kernel */
     int warm = 1, sync = 2;                          /* pair-table kernels: the measurement bits of PLK_OPT_PAIR_TABLES */
+    int fold = 1, held = 1;                          /* v4s: folded op stream, first chunks held across the categories */
     std::string bad;                                 /* the replay check of the chosen variant's formats; empty: fine */
 };
 
@@ -1199,7 +1361,7 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
     const bool asm_fits = NS == 1 && plk_fused_asm_ok(pg) && sh.fused_asm && lds_asm <= PLK_LDS_LIMIT;
     if (pg.slots_needed > PLK_FUSED_SLOTS || (!asm_fits && lds_cpp > PLK_LDS_LIMIT)) return ch;
     const PlkPairTablesOpt po = plk_pair_tables_opt(sh.pair_tables);
-    ch.warm = po.warm; ch.sync = po.sync;
+    ch.warm = po.warm; ch.sync = po.sync; ch.fold = po.fold; ch.held = po.held;
     if (po.on && sh.fused_asm && sh.sites_per_lane != 2 && pg.slots_needed <= 4 && nchar <= 16 && !pg.obs_nodes.empty()) {
         if ((po.mode == 1 || po.mode == 7) && sh.S > 0 && allow_stream) {
             /* measured faster than the tile kernels at every shape tried (profiles/ll_k4_stream_ab.json), so no site count

@@ -45,6 +45,12 @@ observation ops do not sit in LDS rows, they arrive packed four to a dword from 
   handlers 34 + k (k < 2) ADVANCE_k: wait for the older of the two chunks in flight, make it the current dword and
   request the chunk after next into its register pair.  The op stream holds an ADVANCE before the observation op that
   extracts the first byte of a new dword, kinds alternating from 0.
+  FOLDED handlers (plk_v4s_fold_ops in plk_program.h retargets ops of the checked stream at them; each is the text of
+  the two handlers it stands for under one dispatch, so what a site computes does not change):
+  36 + 2 j + k   observation handler OBS_HANDLERS[j] with ADVANCE_k between its arithmetic and its extraction
+  60 + d         MATVEC + POPMUL slot d, then SCALE
+  Two prologues over one handler table: PLK_V4S_PROLOGUE requests the unit's first three chunks itself and waits for the
+  first; PLK_V4S_PROLOGUE_HELD copies them from three 64-bit operands that the kernel loaded once per unit.
 """
 import os
 
@@ -179,21 +185,34 @@ REFILL_A, REFILL_B = 32, 33
 ADVANCE0 = 34
 
 
+OBS_HANDLERS = (0, 1, 3, 4, 12, 13, 14, 15, 20, 21, 22, 23)     # in the order of their folded variants
+FOLD_ADV0 = 36                # 36 + 2 j + k: OBS_HANDLERS[j] with ADVANCE_k before its extraction
+FOLD_SCALE0 = 60              # 60 + d: MATVEC + POPMUL slot d, then SCALE
+
+
+def obs_handlers(tipnext):
+    """the observation handlers (OBS_HANDLERS) without their dispatch; tipnext: the prefetch of the next observation"""
+    h = {}
+    h[0] = ["s_waitcnt lgkmcnt(0)"] + tipset() + tipnext()
+    h[1] = ["s_waitcnt lgkmcnt(0)"] + tipmul() + tipnext()
+    h[3] = tipmul() + tipnext()
+    h[4] = matvec() + tipmul() + tipnext()
+    for d in range(4):
+        h[12 + d] = ["s_waitcnt lgkmcnt(0)"] + setpop(d) + tipnext()
+        h[20 + d] = ["s_waitcnt lgkmcnt(0)"] + setpush(d) + tipnext()
+    assert tuple(sorted(h)) == OBS_HANDLERS
+    return h
+
+
 def handlers(streamed=False):
     tipnext = tipnext_s if streamed else globals()["tipnext"]
-    h = {}
-    h[0] = ["s_waitcnt lgkmcnt(0)"] + tipset() + tipnext() + RET
-    h[1] = ["s_waitcnt lgkmcnt(0)"] + tipmul() + tipnext() + RET
+    h = {idx: body + RET for idx, body in obs_handlers(tipnext).items()}
     h[2] = matvec() + RET
-    h[3] = tipmul() + tipnext() + RET
-    h[4] = matvec() + tipmul() + tipnext() + RET
     h[6] = scale() + RET
     h[7] = ["s_branch .Ldone_%="]
     for d in range(4):
         h[8 + d] = push(d) + RET
-        h[12 + d] = ["s_waitcnt lgkmcnt(0)"] + setpop(d) + tipnext() + RET
         h[16 + d] = popmul(d) + RET
-        h[20 + d] = ["s_waitcnt lgkmcnt(0)"] + setpush(d) + tipnext() + RET
         h[24 + d] = matvec(slot_regs(d, 0), slot_regs(d, 1)) + RET
         h[28 + d] = matvec() + popmul(d) + RET
     adv = ["s_add_u32 s20, s20, 0x40", "s_addc_u32 s21, s21, 0"]
@@ -202,10 +221,16 @@ def handlers(streamed=False):
     if streamed:
         for k in range(2):
             h[ADVANCE0 + k] = advance(k) + RET
+            # folded: the handler's own arithmetic, then ADVANCE_k, then its extraction, which reads the new current dword
+            for j, (idx, body) in enumerate(sorted(obs_handlers(lambda: advance(k) + tipnext_s()).items())):
+                h[FOLD_ADV0 + 2 * j + k] = body + RET
+        for d in range(4):
+            h[FOLD_SCALE0 + d] = matvec() + popmul(d) + scale() + RET
     return h
 
 
-def emit(streamed=False):
+def emit(streamed=False, held=False):
+    """-> (prologue up to the dispatch of the first op, handler table and epilogue)"""
     L = []           # (text, is_label)
 
     def ins(lines):
@@ -217,7 +242,16 @@ def emit(streamed=False):
     for i in range(4):
         pro += ["v_mov_b32 v%d, 0" % (XA + 2 * i), "v_mov_b32 v%d, 0x3ff00000" % (XA + 2 * i + 1),
                 "v_mov_b32 v%d, 0" % (XB + 2 * i), "v_mov_b32 v%d, 0x3ff00000" % (XB + 2 * i + 1)]
-    if streamed:
+    if held:
+        # the first three chunks are operands: the kernel requested them once per unit (the compiler waits for them before the
+        # statement, which costs time in the unit's first category only).  Vector memory operations of the kernel may still be
+        # in flight here and none of the statement's own is: ADVANCE's s_waitcnt vmcnt(1) assumes two loads of its own in
+        # flight, and fewer of them, or older operations in front of them (the counter retires in order), only make it wait
+        # for less or for more than the chunk it needs, never for too little
+        pro += ["v_mov_b32 v76, %[voff]", "s_mov_b64 s[34:35], %[strm]",
+                "v_mov_b64 v[74:75], %[c0]", "v_mov_b64 %s, %%[c1]" % pair(RING[0]), "v_mov_b64 %s, %%[c2]" % pair(RING[1]),
+                "s_add_u32 s34, s34, 0x%x" % (3 * CHUNK_BYTES), "s_addc_u32 s35, s35, 0"]
+    elif streamed:
         # the first three chunks: the current dword and the two in flight; no older vector memory operation may be counted
         pro += ["s_waitcnt vmcnt(0)", "v_mov_b32 v76, %[voff]", "s_mov_b64 s[34:35], %[strm]",
                 "global_load_dwordx2 v[74:75], v76, s[34:35]",
@@ -232,7 +266,7 @@ def emit(streamed=False):
     if streamed:
         # prefetch chain start: the first observation's code is byte 0 of chunk 0, its values
         pro += ["s_getpc_b64 s[24:25]", ".Lpcref_%=:", "s_add_u32 s26, s24, .Lh0_%=-.Lpcref_%=", "s_addc_u32 s25, s25, 0",
-                "s_waitcnt vmcnt(2)",
+                ] + ([] if held else ["s_waitcnt vmcnt(2)"]) + [
                 "v_bfe_u32 v72, v74, 0, 8", "v_bfe_u32 v73, v75, 0, 8",
                 "v_add_lshl_u32 v72, v72, %[y0], 5", "v_add_lshl_u32 v73, v73, %[y0], 5",
                 "ds_read_b128 v[56:59], v72", "ds_read_b128 v[60:63], v72 offset:16",
@@ -251,6 +285,7 @@ def emit(streamed=False):
             "s_waitcnt lgkmcnt(0)"]
     ins(pro)
     ins(RET)           # the first op
+    npro = len(L)
     # ---- handlers ----
     h = handlers(streamed)
     ins([".p2align 15", ".Lh0_%=:"])
@@ -267,7 +302,7 @@ def emit(streamed=False):
             ins(["v_fma_f64 %s, %%[w%d], %s, %s" % (pair(t), i, pair(x + 2 * i), pair(t))])
     ins(["v_mov_b32 %%[al], v%d" % TA, "v_mov_b32 %%[ah], v%d" % (TA + 1), "v_mov_b32 %%[bl], v%d" % TB, "v_mov_b32 %%[bh], v%d" % (TB + 1)])
     ins(["v_mov_b32 %[ea], v78", "v_mov_b32 %[eb], v79", "s_nop 1"])
-    return L
+    return L[:npro], L[npro:]
 
 
 def c_string(lines):
@@ -284,7 +319,7 @@ def c_string(lines):
 
 
 def main():
-    lines = emit()
+    lines = sum(emit(), [])
     # size check: every handler must fit its slot (also checked on the object by tools/asm_layout_check.py)
     sizes = {"v_mul_f64": 8, "v_fma_f64": 8, "v_mov_b64": 4, "v_mov_b32": 4, "v_max_u32": 4, "v_max3_u32": 8, "v_lshrrev_b32": 4,
              "v_sub_u32": 8, "v_ldexp_f64": 8, "v_add3_u32": 8, "v_add_lshl_u32": 8, "v_lshl_add_u32": 8, "ds_read_b128": 8,
@@ -325,8 +360,9 @@ def main():
         f.write(hdr)
     print("wrote", path, "(%d asm lines)" % len(lines))
     # ---- streamed codes ----
-    lines = emit(True)
-    assert not any(t.startswith("@HALF ") for t in lines)
+    pro, lines = emit(True)
+    held = emit(True, True)[0]
+    assert not any(t.startswith("@HALF ") for t in pro + held + lines)
     vregs += ["v%d" % r for r in range(RING[0], RING[1] + 2)]
     hdr = '''/* GENERATED by tools/gen_fused4_v4.py -- do not edit; change the generator and run it again.
  *
@@ -337,21 +373,36 @@ def main():
 
 #define PLK_V4S_ADVANCE %d
 #define PLK_V4S_CHUNK_BYTES %d
+#define PLK_V4S_FOLD_ADV %d
+#define PLK_V4S_FOLD_SCALE %d
 
-#define PLK_V4S_PROGRAM \\
+/* prologue that requests the unit's first three chunks itself */
+#define PLK_V4S_PROLOGUE \\
 %s
         ""
+
+/* prologue that takes them from the operands c0, c1, c2 */
+#define PLK_V4S_PROLOGUE_HELD \\
+%s
+        ""
+
+#define PLK_V4S_TABLE \\
+%s
+        ""
+
+#define PLK_V4S_PROGRAM PLK_V4S_PROLOGUE PLK_V4S_TABLE
+#define PLK_V4S_PROGRAM_HELD PLK_V4S_PROLOGUE_HELD PLK_V4S_TABLE
 
 #define PLK_V4S_CLOBBERS "memory", "scc", "vcc", \\
         %s, \\
         %s
 
 #endif
-''' % (ADVANCE0, CHUNK_BYTES, c_string(lines), ", ".join('"%s"' % v for v in vregs), ", ".join('"%s"' % s for s in sregs))
+''' % (ADVANCE0, CHUNK_BYTES, FOLD_ADV0, FOLD_SCALE0, c_string(pro), c_string(held), c_string(lines), ", ".join('"%s"' % v for v in vregs), ", ".join('"%s"' % s for s in sregs))
     path = os.path.join(os.path.dirname(path), "plk_fused4_v4s_asm.h")
     with open(path, "w") as f:
         f.write(hdr)
-    print("wrote", path, "(%d asm lines)" % len(lines))
+    print("wrote", path, "(%d asm lines)" % len(pro + held + lines))
 
 
 if __name__ == "__main__":
