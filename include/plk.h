@@ -32,6 +32,11 @@
  * independent (one per GPU / per process rank).  There is no CPU fallback: if
  * no gfx950 device is usable, plk_create fails.
  *
+ * The engine keeps tables, matrix streams and work buffers from one call to the next and recomputes what a call made
+ * stale.  None of that shows: every query gives the same bits whatever ran on the engine before it -- other queries,
+ * changes of rates, model, patterns, weights, tree or options and back, a fit, a refused call -- as on a new engine that
+ * was brought to the same tree, model, patterns, weights and options and ran nothing else (tests/test_gpu_query_order.py).
+ *
  * Edge indices at this boundary are CSR edge indices (position in
  * `indices`), as in the reference's cross_site_ws; the host layer maps user
  * edge order <-> CSR order (src/csr_graph.c:29-46).
@@ -117,14 +122,17 @@ int plk_check_model_values(int k, int C, int E, const double *Qn, const double *
 
 /* Observations, compact form: codes[N][S] (site index fastest, one byte per
  * node per site) + definitions defs[nchar][k] (host).  `where` says whether
- * `codes` is a host or a device pointer; the engine copies it either way. */
+ * `codes` is a host or a device pointer; the engine copies it either way.
+ * New patterns (either form) drop the site weights of the previous ones: all weights are 1 until the next
+ * plk_set_site_weights. */
 int plk_set_patterns_codes(plk_engine *h, long S, const uint8_t *codes, int where,
                            int nchar, const double *defs);
 
-/* Observations, dense form: B[N][k][S] doubles (site index fastest). */
+/* Observations, dense form: B[N][k][S] doubles (site index fastest).  Drops the site weights, as the compact form does. */
 int plk_set_patterns_dense(plk_engine *h, long S, const double *B, int where);
 
-/* Optional per-site weights for the aggregated outputs (NULL = all 1).
+/* Optional per-site weights for the aggregated outputs (NULL = all 1): S doubles for the patterns the engine holds.
+ * They last until the next plk_set_site_weights or the next plk_set_patterns_*, which drops them.
  * A weight of exactly 0 still evaluates the site; selection is the caller's.  In the sums of plk_ll, plk_deriv and
  * plk_marginal a weight of exactly 0 drops the site's term whatever the term is: a site of likelihood 0 (ll -inf,
  * derivatives and marginals inf or NaN) under weight 0 leaves those sums equal to the sums of the alignment without the
@@ -163,6 +171,8 @@ int plk_set_stream(plk_engine *h, void *hip_stream);
  * more than 32 edge factors at once (33 leaf children, or three children over 16 edges each) they first measure the
  * node products on the device; where one has no entry of at least 2^-969 at some site they return PLK_E_ARG, the
  * diagnostic naming the query and the node, and the engine stays usable.  With ordinary branch lengths nothing is refused.
+ * A product that is exactly 0 because every entry took a factor of exactly 0 (the rate-0 category under children that show
+ * different states) has not left the range and is not refused.
  * plk_ll and plk_cat_posterior rescale inside such a node and always answer.
  */
 int plk_deriv(plk_engine *h, const int *edge_mask,
@@ -185,7 +195,7 @@ int plk_marginal(plk_engine *h, const int *node_mask,
  * post_sums_out: NULL or [C][2]; rate_sum_out: NULL or [2]: double-double sums over sites of w_s post[s][c] and
  * w_s rate[s].  A category of prior 0 has posterior exactly 0.  A site of likelihood 0 gets NaN in post and rate (-inf in
  * site_ll); when sums are asked for and such a site has a non-zero weight the call fails with PLK_E_ARG ("site likelihood
- * zero").  plk_ll and every other query give the same bits whether or not this call ran in between.
+ * zero").
  * plk_cat_posterior_ll is the same call with the by-products: site_ll_out NULL or [S] host, ll_sum_out NULL or [2].
  */
 int plk_cat_posterior(plk_engine *h, double *post_out, double *rate_out, double *post_sums_out, double *rate_sum_out);
@@ -226,7 +236,7 @@ int plk_edge_expect_multi(plk_engine *h, int nL, const double *L_hi, const doubl
  * sum is fixed (two calls give the same bits).  Preconditions as for plk_deriv; edge_mask: NULL (all) or E ints.
  * W_out: [C][E][k][k][2] double-double entries in CSR edge order, masked edges exactly 0; root_out: NULL or [C][k][2].
  * A site of likelihood 0 with a non-zero weight makes the call fail with PLK_E_ARG ("site likelihood zero"); with weight
- * 0 it contributes nothing.  Other queries give the same bits whether or not this call ran in between.
+ * 0 it contributes nothing.
  */
 int plk_edge_pair_sums(plk_engine *h, const int *edge_mask, double *W_out, double *root_out);
 
@@ -267,7 +277,6 @@ int plk_rate_matrix_chain(int k, const double *rate_matrix, int divisor_mode, do
  * plk_edge_pair_sums, whose preconditions and zero-likelihood behaviour apply (PLK_E_ARG, "site likelihood zero").
  * prior_out, rate_out: [C][2] double-double.  Identities: sum_c p_c prior_out[c] = sum_s w_s;
  * sum_c r_c rate_out[c] = sum_e t_e (edge sums of plk_deriv); p_c prior_out[c] = post_sums[c] of plk_cat_posterior.
- * Other queries give the same bits whether or not this call ran in between.
  */
 int plk_mixture_sens(plk_engine *h, double *prior_out, double *rate_out);
 

@@ -980,8 +980,10 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_ll_generic(GenArgs a)
  * Those passes keep one factor per node, so they skip the OP_SCALE ops inside a node (op_mid) and see the node's whole
  * product at the OP_SCALE after its last child.  This kernel walks the program the same way and raises *flag where such a
  * product, or the root vector, has no entry of at least 2^-969 in some category at some site: below that magnitude an entry
- * within 2^-53 of the largest can be subnormal, and the stored vectors are no longer good to the stated bars.  The matrices
- * are read by edge (PS = [C][E][K*K], transposed).  No output but the flag.
+ * within 2^-53 of the largest can be subnormal, and the stored vectors are no longer good to the stated bars.  A product
+ * that is exactly zero because every entry took a factor of exactly 0.0 (the rate-0 category, P = I, under leaves that show
+ * different states) has left no range: `live` keeps one bit per entry, cleared by the first zero factor, and only a product
+ * with a live entry can be low.  The matrices are read by edge (PS = [C][E][K*K], transposed).  No output but the flag.
  */
 template <int K>
 __global__ __launch_bounds__(GEN_BLOCK) void k_range_check(GenArgs a, int E, const int *op_edge, const int *op_mid, int *flag)
@@ -992,10 +994,12 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_range_check(GenArgs a, int E, con
     const bool valid = s < a.S;
     const long sc = valid ? s : a.S - 1;
     bool low = false;
+    const unsigned long long kmask = a.k >= 64 ? ~0ull : (1ull << a.k) - 1;     /* the k entries of a vector (K >= k is padding) */
     for (int c = 0; c < a.C; c++) {
         double cur[K];
 #pragma unroll
         for (int i = 0; i < K; i++) cur[i] = 1.0;
+        unsigned long long live = ~0ull;
         for (int pc = 0; pc < a.nops; pc++) {
             const int ox = as_uniform(reinterpret_cast<const int *>(a.ops))[2 * pc], oy = as_uniform(reinterpret_cast<const int *>(a.ops))[2 * pc + 1];
             const int code = ox & 0xff;
@@ -1018,6 +1022,10 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_range_check(GenArgs a, int E, con
                 }
 #pragma unroll
                 for (int i = 0; i < K; i++) cur[i] = code == OP_TIP_MUL ? cur[i] * acc[i] : acc[i];
+                if (code != OP_TIP_MUL) live = ~0ull;
+#pragma unroll
+                for (int i = 0; i < K; i++)
+                    if (i < a.k && acc[i] == 0.0) live &= ~(1ull << i);
             } else if (code == OP_PUSH) {
                 double *sp = a.slots + (size_t)oy * a.k * a.S + sc;
 #pragma unroll
@@ -1027,17 +1035,24 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_range_check(GenArgs a, int E, con
                 const double *sp = a.slots + (size_t)oy * a.k * a.S + sc;
 #pragma unroll
                 for (int i = 0; i < K; i++)
-                    if (i < a.k) cur[i] *= valid ? sp[(size_t)i * a.S] : 1.0;
+                    if (i < a.k) {
+                        const double x = valid ? sp[(size_t)i * a.S] : 1.0;
+                        cur[i] *= x;
+                        if (x == 0.0) live &= ~(1ull << i);
+                    }
             } else if (code == OP_NODE_MUL) {
                 gen_load_obs<K>(a, oy, sc, tid, xs);
 #pragma unroll
                 for (int i = 0; i < K; i++)
-                    if (i < a.k) cur[i] *= xs[i][tid];
+                    if (i < a.k) {
+                        cur[i] *= xs[i][tid];
+                        if (xs[i][tid] == 0.0) live &= ~(1ull << i);
+                    }
             } else if (code == OP_SCALE && !as_uniform(op_mid)[pc]) {
                 double m = 0.0;
 #pragma unroll
                 for (int i = 0; i < K; i++) m = fmax(m, cur[i]);
-                if (!(m >= 0x1p-969)) low = true;
+                if (!(m >= 0x1p-969) && (live & kmask)) low = true;
                 const int e = frexp_exp(m);
 #pragma unroll
                 for (int i = 0; i < K; i++) cur[i] = ldexp(cur[i], -e);
@@ -1046,7 +1061,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_range_check(GenArgs a, int E, con
         double m = 0.0;
 #pragma unroll
         for (int i = 0; i < K; i++) m = fmax(m, cur[i]);
-        if (!(m >= 0x1p-969)) low = true;
+        if (!(m >= 0x1p-969) && (live & kmask)) low = true;
     }
     if (low && valid) *flag = 1;
 }
