@@ -415,11 +415,17 @@ enum {
     PLK_INFO_LL_FORM = 19,          /* form of the last ll evaluation's k = 4 pair-table kernel: 1 = streamed codes with the tables
                                        of all categories resident in LDS (k_ll_fused4_v4s; PLK_INFO_LL_VARIANT reports 6),
                                        0 = a tile kernel or another family */
+    PLK_INFO_LL_PAIRMUL = 21,       /* pair products in the last ll evaluation's streamed kernel: 0 = the form did not run (another
+                                       kernel, a tree that needs 4 stack slots, PLK_OPT_PAIR_TABLES + 64 / + 128 / + 256 / + 512, or
+                                       a stream that did not replay), else bit 0 = k_ll_fused4_v4s<768, true, true> ran its op stream and bits 8-23 =
+                                       PAIR ops of one category (two table rows multiplied under one dispatch, saturating; can be 0) */
     PLK_INFO_LL_FOLD = 20           /* op stream of the last ll evaluation's streamed kernel (0 for every other kernel), bit fields:
                                        bit 0 = the folded op stream ran, bit 1 = the first chunks of a unit were held across the
                                        categories, bits 4-7 = stack slots d whose MATVEC + POPMUL + SCALE handler the stream
                                        dispatches, bits 8-15 = SCALE ops left with a dispatch of their own, bits 16-23 / 24-30 =
-                                       observation ops of one category with ADVANCE_0 / ADVANCE_1 folded in (saturating) */
+                                       observation ops of one category with ADVANCE_0 / ADVANCE_1 folded in (saturating).  Under
+                                       the pair-product form (PLK_INFO_LL_PAIRMUL) bits 0 and 4-30 describe the folded stream it was
+                                       derived next to: a PAIR op with an ADVANCE counts as the observation op that carried it */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -458,7 +464,11 @@ enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PE
                                stream and without the held first chunks (the checked stream as it is built, ADVANCE and SCALE
                                ops dispatched on their own, every category requesting the unit's first three chunks itself:
                                the kernel as it was before the fold, and what runs when the fold does not replay);
-                               + 128: without the held chunks only, + 256: without the fold only (measurements) */,
+                               + 128: without the held chunks only, + 256: without the fold only (measurements);
+                               + 512: without the pair products of trees within 3 stack slots (k_ll_fused4_v4s<768, true, true>: a second
+                               look-up buffer in the registers of slot 3, two table rows multiplied under one dispatch):
+                               the folded stream with held chunks on k_ll_fused4_v4s, the default before that form
+                               (measurements; + 64 / + 128 / + 256 imply it) */,
        PLK_OPT_VEC_REG_STACK = 7 /* 1 (default): the vector kernels (9 <= k <= 20) keep the three busiest stack slots in
                                registers (2 waves per SIMD); 0: every waiting vector goes through HBM slots (round 2) */,
        PLK_OPT_MFMA_NS2 = 8 /* 1: the matrix-core ll kernel for 33 <= k <= 64 gives a wave two groups of 16 sites (every staged

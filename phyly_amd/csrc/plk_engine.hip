@@ -66,6 +66,8 @@ struct LlPlan {
     long info_variant = 0, info_form = 0, info_exec_flops = 0;     /* PLK_INFO_LL_VARIANT, _FORM, _LL_EXEC_FLOPS */
     bool fold = false, held = false;     /* streamed form: the folded op stream is the one uploaded; first chunks held */
     long info_fold = 0;                  /* PLK_INFO_LL_FOLD */
+    bool pairmul = false;                /* streamed form: the pair-product stream is the one uploaded, k_ll_fused4_v4s<768, true, true> runs it */
+    long info_pairmul = 0;               /* PLK_INFO_LL_PAIRMUL */
 };
 
 struct plk_engine {
@@ -117,6 +119,7 @@ struct plk_engine {
     bool prog_dirty = true, fmt_dirty = true, tables_dirty = true;
     LlPlan plan;                         /* which ll kernel runs, and how: written by upload_formats, valid while !fmt_dirty */
     bool k4_held_ok = false;             /* k_ll_fused4_v4s<768, true> can be described and has the static LDS of <768, false> */
+    bool k4_pair_ok = false;             /* the same for k_ll_fused4_v4s<768, true, true> */
     size_t k4_static_lds[3] = {};        /* PlkK4Shape::static_lds, asked of the runtime once (k4_static_lds_known) */
     hipError_t k4_static_lds_err[3] = {};
     bool k4_static_lds_known = false;
@@ -134,6 +137,7 @@ struct plk_engine {
     PlkVecPT vpt;                        /* the vector ll kernel's program on pair tables */
     PlkFusedV4S fv4s;                    /* streamed codes (k_ll_fused4_v4s): one op stream per category */
     PlkFusedV4SFold fv4s_fold;           /* ... and its folded form, the one the kernel runs unless PLK_OPT_PAIR_TABLES + 64 / + 256 */
+    PlkFusedV4P fv4p;                    /* ... and the pair-product stream of trees within 3 slots (k_ll_fused4_v4s<768, true, true>) */
     unsigned *d_cstream = nullptr; size_t cstream_cap = 0;   /* the code stream (plk_stream_dword), built by upload_formats */
     int *d_obs_row = nullptr;            /* staged row per observation of the program */
     int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [2][rows] staged-row nodes; [4][ntab] unit, edge, leaf edges of a pair */
@@ -191,7 +195,7 @@ struct plk_engine {
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
-    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
+    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_pairmul = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
 static std::string g_create_error;
@@ -1584,6 +1588,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
     case PLK_INFO_LL_FORM: *out = h->info_ll_form; return PLK_OK;
     case PLK_INFO_LL_FOLD: *out = h->info_ll_fold; return PLK_OK;
+    case PLK_INFO_LL_PAIRMUL: *out = h->info_ll_pairmul; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && h->plan.pair_tables ? h->plan.npairs : 0; return PLK_OK;
     case PLK_INFO_STACK_SLOTS: *out = h->slots_needed; return PLK_OK;
@@ -1992,6 +1997,8 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
         hipFuncAttributes fh;
         if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true>) != hipSuccess) (void)hipGetLastError();
         else h->k4_held_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
+        if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true, true>) != hipSuccess) (void)hipGetLastError();
+        else h->k4_pair_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
         h->k4_static_lds_known = true;
     }
     PlkK4Shape sh = {h->nchar, h->C, h->S, h->num_cus, h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
@@ -2025,6 +2032,18 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
                            (long)std::min(fo.nadv[0], 255) << 16 | (long)std::min(fo.nadv[1], 127) << 24;
         } else h->err = "internal: " + bad + " (the unfolded op stream runs)";
     }
+    p.pairmul = false; p.info_pairmul = 0;
+    if (c.variant == PLK_K4_V4S && c.pair && p.fold && p.held && h->k4_pair_ok) {
+        /* derived from the checked stream and replayed against it like the fold.  Where the form does not apply (a table
+         * field beyond its 13 bits, an observation kind without a handler on its buffer) nothing is derived and the folded
+         * stream runs; a derived stream that does not replay is not run either, and the error text says why */
+        plk_fused_v4p_build(h->fv4s, h->fv4p);
+        if (!h->fv4p.words.empty()) {
+            const std::string bad = plk_fused_check_v4p(h->fv4s, h->fv4p);
+            if (bad.empty()) { p.pairmul = true; p.info_pairmul = 1 | (long)std::min(h->fv4p.npair, 65535) << 8; }
+            else h->err = "internal: " + bad + " (the folded op stream runs)";
+        }
+    }
     const int ntips = (int)h->tip_edge.size();
     if (c.variant == PLK_K4_CPP || c.variant == PLK_K4_ASM) {
         /* int4 ops of the C++ interpreter, 32-bit op words of the assembly interpreter, compact matrix list */
@@ -2052,7 +2071,7 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
      * are built from the unrounded P after it (k_build_tables_pt) */
     const PlkFusedPT &f = h->fpt;
     p.pair_tables = true; p.npairs = f.npairs;
-    const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? (p.fold ? h->fv4s_fold.words : h->fv4s.words) : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
+    const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? (p.pairmul ? h->fv4p.words : p.fold ? h->fv4s_fold.words : h->fv4s.words) : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
     if ((rc = dev_upload(h, &h->d_words_pt, words.data(), words.size()))) return rc;
     /* d_obs_row before the pair-table lists: the order in which these buffers were first allocated when the kernels were
      * measured (with it after them, the streamed kernel at 1.25M sites of BASELINE config 3 ran 0.3 % longer) */
@@ -2329,10 +2348,12 @@ static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool 
         if (c.variant == PLK_K4_V4S) {
             FusedV4SArgs sa;
             sa.pt = pa;
-            sa.pt.nwords = (int)(p.fold ? h->fv4s_fold.stride : h->fv4s.stride);
+            sa.pt.nwords = (int)(p.pairmul ? h->fv4p.stride : p.fold ? h->fv4s_fold.stride : h->fv4s.stride);
             sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
             sa.sync = c.sync;
-            if (p.held) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            sa.first_y1 = p.pairmul ? h->fv4p.first_y1[0] : 0u; sa.first_b1 = p.pairmul ? h->fv4p.first_b1 : 0u;
+            if (p.pairmul) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            else if (p.held) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
             else hipLaunchKernelGGL((k_ll_fused4_v4s<768, false>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
         } else if (c.variant == PLK_K4_V4) {
             FusedV4Args va;
@@ -2467,7 +2488,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     default: rc = launch_ll_generic(h, p, d_out, want_sum, &npartials); break;
     }
     if (rc) return rc;
-    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_exec_flops = p.info_exec_flops;
+    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_pairmul = p.info_pairmul; h->info_ll_exec_flops = p.info_exec_flops;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->evk[evi][1], h->stream));
     h->evk_pending[evi] = true;

@@ -25,11 +25,20 @@
  * uploaded), and the HELD instantiation loads a unit's first three chunks once per unit instead of once per category --
  * the next unit's while this unit's log and store run -- so that no category starts with all twelve waves of the CU waiting
  * on the same three loads behind the barrier.
+ *
+ * The PAIR instantiation (k_ll_fused4_v4s<768, true, true>) is the same kernel around a third text of the interpreter (PLK_V4P_PROGRAM_HELD, pair products: programs
+ * within three stack slots).  The registers of stack slot 3 hold a second prefetched table row, the look-up chain runs two
+ * observations ahead, and where a node's two children are both look-ups one PAIR op multiplies the two rows straight into
+ * the vector under construction: eight v_mul_f64 per lane where the folded stream runs two dispatches, eight v_mov_b64 and
+ * the same eight v_mul_f64.  The op stream is plk_fused_v4p_build's (plk_program.h), replayed against the checked stream
+ * before it is uploaded; the operands of every multiply are the ones of the folded stream's, so site log likelihoods are
+ * bit-identical.  PLK_OPT_PAIR_TABLES + 512 runs the folded stream on k_ll_fused4_v4s<768, true> instead.
  */
 #ifndef PLK_FUSED4_V4S_H
 #define PLK_FUSED4_V4S_H
 
 #include "plk_fused4_v4s_asm.h"
+#include "plk_fused4_v4p_asm.h"
 
 struct FusedV4SArgs {
     FusedPTArgs pt;             /* words = C op streams of stride dwords, nwords = stride; row_nodes / first_row / ntiles unused */
@@ -37,6 +46,7 @@ struct FusedV4SArgs {
     int chunks;                 /* chunks of a unit, the spare ones included */
     unsigned first_y;           /* LDS offset / 32 of the first observation's table in category 0 */
     int sync;                   /* workgroup barrier: 1 before every unit, 2 before every category, 0 none */
+    unsigned first_y1, first_b1; /* pair products: table of the second observation in category 0, bit offset of its code */
 };
 
 /* stream[unit][chunk][lane][half]: one thread per dword; sites past S carry code 0 (the code rows are zero padded) */
@@ -56,17 +66,25 @@ __global__ __launch_bounds__(256) void k_build_code_stream(const uint8_t *__rest
 
 /* HELD: the unit's first three chunks (c0 the current dword pair, c1 and c2 the two "in flight") are operands, loaded by
  * the kernel once per unit; otherwise the statement requests them itself, in every category */
-template <bool HELD>
+template <bool HELD, bool PAIR>
 __device__ __forceinline__ void fused_run_program_v4s(double &lha, double &lhb, int &ea, int &eb, const void *ops, const void *mstream,
                                                        const void *strm, unsigned voff, unsigned y0,
                                                        double w0, double w1, double w2, double w3,
-                                                       unsigned long long c0, unsigned long long c1, unsigned long long c2)
+                                                       unsigned long long c0, unsigned long long c1, unsigned long long c2,
+                                                       unsigned y1, unsigned b1)
 {
     int al, ah, bl, bh;
 #ifdef PLK_EXP_EMPTY
     al = bl = 0; ah = bh = 0x3ff00000; ea = eb = 0;
 #else
-    if constexpr (HELD)
+    static_assert(HELD || !PAIR, "the pair-product text has the held prologue only");
+    if constexpr (PAIR)
+        asm volatile(PLK_V4P_PROGRAM_HELD
+                     : [al] "=v"(al), [ah] "=v"(ah), [bl] "=v"(bl), [bh] "=v"(bh), [ea] "=v"(ea), [eb] "=v"(eb)
+                     : [voff] "v"(voff), [ops] "s"(ops), [mstream] "s"(mstream), [strm] "s"(strm), [y0] "s"(y0), [y1] "s"(y1), [b1] "s"(b1),
+                       [w0] "s"(w0), [w1] "s"(w1), [w2] "s"(w2), [w3] "s"(w3), [c0] "v"(c0), [c1] "v"(c1), [c2] "v"(c2)
+                     : PLK_V4S_CLOBBERS);
+    else if constexpr (HELD)
         asm volatile(PLK_V4S_PROGRAM_HELD
                      : [al] "=v"(al), [ah] "=v"(ah), [bl] "=v"(bl), [bh] "=v"(bh), [ea] "=v"(ea), [eb] "=v"(eb)
                      : [voff] "v"(voff), [ops] "s"(ops), [mstream] "s"(mstream), [strm] "s"(strm), [y0] "s"(y0),
@@ -83,7 +101,7 @@ __device__ __forceinline__ void fused_run_program_v4s(double &lha, double &lhb, 
     lhb = __hiloint2double(bh, bl);
 }
 
-template <int THREADS, bool HELD = false>
+template <int THREADS, bool HELD = false, bool PAIR = false>
 __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
 {
     constexpr int NW = THREADS / 64;
@@ -154,8 +172,8 @@ __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
             }
             double lhs[2];
             int esc[2];
-            fused_run_program_v4s<HELD>(lhs[0], lhs[1], esc[0], esc[1], ops, ps, strm, (unsigned)lane * 8u, va.first_y + (unsigned)c * cat32,
-                                        rw0, rw1, rw2, rw3, c0, c1, c2);
+            fused_run_program_v4s<HELD, PAIR>(lhs[0], lhs[1], esc[0], esc[1], ops, ps, strm, (unsigned)lane * 8u, va.first_y + (unsigned)c * cat32,
+                                              rw0, rw1, rw2, rw3, c0, c1, c2, va.first_y1 + (unsigned)c * cat32, va.first_b1);
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const double lh = lhs[j];

@@ -1164,6 +1164,312 @@ static inline std::string plk_fused_check_v4s_fold(const PlkFusedV4S &vs, const 
 }
 
 /*
+ * The PAIR-PRODUCT op stream of k_ll_fused4_v4s<768, true, true> (tools/gen_fused4_v4.py, third emission mode): the checked stream for
+ * programs within PLK_V4P_STACK_SLOTS stack slots.  The registers of slot 3 are a second look-up buffer; the row of
+ * observation n lands in buffer n & 1, its handler consumes that buffer and requests observation min(n + 2, last) into it.
+ * Adjacent (TIP_SET, TIP_MUL) and adjacent (TIP_SET + PUSH d, TIP_SET + POPMUL d) -- at most an ADVANCE between them in the
+ * checked stream -- become one PAIR op: x = P[n] * P[n + 1] from the two buffers (the slot form computes slot = P[n],
+ * x = P[n + 1] * slot and leaves the slot dead: the same product, IEEE multiplication of the two rows commutes), then the
+ * requests of n + 2 and n + 3.  Codes are still extracted in increasing observation order, so the ADVANCEs are the checked
+ * stream's in number and kind.  The extraction that needs a new dword is the one of an observation whose index is a multiple
+ * of 4; two ahead, it falls into the handler of an even observation, before the first extraction of a PAIR of an even one or
+ * between the two of a PAIR of an odd one, and handlers with an ADVANCE inside exist for exactly those cases -- except for
+ * TIP_SET alone and TIP_MUL without wait (binary trees produce neither), whose ADVANCE keeps a dispatch in front of them.
+ * TIP_SET + PUSH slot 0 has its handler on buffer 0 without ADVANCE only.  No property of the program builder is relied on
+ * for that: in the trees tried it is the program's first observation and nothing else (tests/pairmulcheck_main.cpp), and a
+ * stream that asks for it on buffer 1 is simply not derived -- plk_v4p_derive_ops returns false, the engine runs the folded
+ * stream on such a tree and PLK_INFO_LL_PAIRMUL reports 0 (no error text: nothing failed); with an ADVANCE it keeps the
+ * ADVANCE as a dispatch, like the two kinds above.
+ * SCALE after MATVEC + POPMUL folds as in the folded stream.  The table has the 64 slots of the streamed one; handler indices
+ * and the field dword of a PAIR: the generator's text.
+ */
+#define PLK_V4P_STACK_SLOTS 3
+#define PLK_V4P_FOLD_ADV 36
+#define PLK_V4P_PAIR_EVEN 52
+#define PLK_V4P_PAIR_ODD 55
+
+static inline int plk_v4p_obs_index(unsigned hidx)
+{
+    if (hidx == OP_TIP_SET) return 0;
+    if (hidx == OP_TIP_MUL) return 1;
+    if (hidx == PLK_WORD_TIPMUL_NOWAIT) return 2;
+    if (hidx == PLK_WORD_MATVEC_TIPMUL) return 3;
+    if (hidx >= PLK_WORD_SET_POPMUL && hidx < PLK_WORD_SET_POPMUL + PLK_V4P_STACK_SLOTS) return 4 + (int)(hidx - PLK_WORD_SET_POPMUL);
+    if (hidx >= PLK_WORD_SET_PUSH && hidx < PLK_WORD_SET_PUSH + PLK_V4P_STACK_SLOTS) return 7 + (int)(hidx - PLK_WORD_SET_PUSH);
+    return -1;
+}
+static inline unsigned plk_v4p_obs_handler(int j)
+{
+    static const unsigned first[4] = {OP_TIP_SET, OP_TIP_MUL, PLK_WORD_TIPMUL_NOWAIT, PLK_WORD_MATVEC_TIPMUL};
+    return j < 4 ? first[j] : j < 7 ? PLK_WORD_SET_POPMUL + (unsigned)(j - 4) : PLK_WORD_SET_PUSH + (unsigned)(j - 7);
+}
+#define PLK_V4P_NONE 0xffffffffu
+/* handler of observation kind j (plk_v4p_obs_index) on buffer p carrying v = 0 no ADVANCE, 1 + k ADVANCE_k; NONE: no such handler */
+static inline unsigned plk_v4p_obs_slot(int j, int v, int p)
+{
+    static const unsigned odd[10] = {5, 11, 15, 19, 23, 27, 31, PLK_V4P_NONE, 59, 63};
+    static const int folded[10] = {-1, 0, -1, 1, 2, 3, 4, -1, 5, 6};
+    if (j < 0 || j >= 10 || v < 0 || v > 2 || p < 0 || p > 1) return PLK_V4P_NONE;
+    if (v == 0) return p ? odd[j] : plk_v4p_obs_handler(j);
+    return p == 0 && folded[j] >= 0 ? (unsigned)(PLK_V4P_FOLD_ADV + 2 * folded[j] + (v - 1)) : PLK_V4P_NONE;
+}
+/* PAIR handler of an observation of parity p; v = 0 no ADVANCE, 1 + k ADVANCE_k before the first extraction, 3 + k between the two */
+static inline unsigned plk_v4p_pair_slot(int v, int p)
+{
+    if (v == 0) return p ? PLK_V4P_PAIR_ODD : PLK_V4P_PAIR_EVEN;
+    if (p == 0 && (v == 1 || v == 2)) return (unsigned)(PLK_V4P_PAIR_EVEN + v);
+    if (p == 1 && (v == 3 || v == 4)) return (unsigned)(PLK_V4P_PAIR_ODD + v - 2);
+    return PLK_V4P_NONE;
+}
+struct PlkV4PHandler { int kind, j, v, p; };       /* kind: 0 no observation handler, 1 one observation, 2 PAIR */
+static inline PlkV4PHandler plk_v4p_decode(unsigned h)
+{
+    for (int p = 0; p < 2; p++) {
+        for (int v = 0; v < 5; v++) if (plk_v4p_pair_slot(v, p) == h) return PlkV4PHandler{2, -1, v, p};
+        for (int j = 0; j < 10; j++) for (int v = 0; v < 3; v++) if (plk_v4p_obs_slot(j, v, p) == h) return PlkV4PHandler{1, j, v, p};
+    }
+    return PlkV4PHandler{0, -1, 0, 0};
+}
+static inline bool plk_v4p_is_obs(unsigned h) { return plk_v4p_decode(h).kind == 1; }
+static inline bool plk_v4p_is_pair(unsigned h) { return plk_v4p_decode(h).kind == 2; }
+static inline bool plk_v4s_is_advance(unsigned h) { return h == (unsigned)PLK_V4S_ADVANCE || h == (unsigned)PLK_V4S_ADVANCE + 1; }
+/* the two ops of the checked stream a PAIR stands for */
+static inline bool plk_v4p_pairable(unsigned a, unsigned b)
+{
+    if (a == OP_TIP_SET && b == OP_TIP_MUL) return true;
+    return a >= PLK_WORD_SET_PUSH && a < PLK_WORD_SET_PUSH + PLK_V4P_STACK_SLOTS && b == a - PLK_WORD_SET_PUSH + PLK_WORD_SET_POPMUL;
+}
+
+struct PlkFusedV4P {
+    std::vector<unsigned> words;       /* C streams of stride dwords, as PlkFusedV4S::words */
+    size_t stride = 0;
+    std::vector<unsigned> first_y1;    /* per category: LDS offset / 32 of the second observation's table (the prologue's) */
+    unsigned first_b1 = 0;             /* bit offset of the second observation's code in chunk 0 */
+    int npair = 0;                     /* PAIR ops of one category */
+    int pair_adv[2] = {0, 0};          /* of them with an ADVANCE before the first / between the two extractions */
+};
+
+/* one category: in = the checked stream's ops (plk_v4s_stream_ops), first_y = its prologue table field; false: the
+ * stream does not fit the form (a handler of slot 3, a table field beyond 13 bits, an observation count that is not nobs) */
+static inline bool plk_v4p_derive_ops(const std::vector<PlkV4SOp> &in, unsigned first_y, int nobs, std::vector<PlkV4SOp> &out,
+                                      unsigned &y1, unsigned &b1, int &npair, int pair_adv[2])
+{
+    out.clear(); npair = 0; pair_adv[0] = pair_adv[1] = 0;
+    if (nobs < 1) return false;
+    const int last = nobs - 1;
+    std::vector<unsigned> T(nobs, 0u);
+    std::vector<PlkV4SOp> items;
+    T[0] = first_y;
+    int k = 0;
+    for (const PlkV4SOp &op : in) {
+        if (plk_v4s_is_advance(op.h)) continue;
+        items.push_back(op);
+        if (!plk_word_is_obs(op.h)) continue;
+        if (k >= nobs) return false;
+        if (k < last) T[k + 1] = op.hi >> 16;
+        k++;
+    }
+    if (k != nobs) return false;
+    for (unsigned t : T) if (t >= (1u << 13)) return false;
+    int cur = 0, nadv = 0, oi = 0;
+    auto need_adv = [&](int m) { if (m / 4 <= cur) return 0; cur++; return 1 + (nadv++ & 1); };
+    for (size_t i = 0; i < items.size(); i++) {
+        const unsigned h = items[i].h;
+        if (plk_word_is_obs(h)) {
+            const int j = plk_v4p_obs_index(h), p = oi & 1;
+            if (j < 0) return false;
+            if (oi + 1 < nobs && i + 1 < items.size() && plk_v4p_pairable(h, items[i + 1].h)) {
+                const int m1 = std::min(oi + 2, last), m2 = std::min(oi + 3, last);
+                const int a1 = need_adv(m1), a2 = need_adv(m2), v = a1 ? a1 : a2 ? 2 + a2 : 0;
+                if (plk_v4p_pair_slot(v, p) == PLK_V4P_NONE) return false;
+                out.push_back(PlkV4SOp{plk_v4p_pair_slot(v, p), (unsigned)(m1 % 4) | (unsigned)(m2 % 4) << 3 | T[m1] << 5 | T[m2] << 18});
+                npair++; if (a1) pair_adv[0]++; if (a2) pair_adv[1]++;
+                oi += 2; i++;
+            } else {
+                const int m = std::min(oi + 2, last);
+                int a = need_adv(m);
+                /* no handler with this ADVANCE inside: it keeps its dispatch, in front of the op (the op's arithmetic does not read the dword) */
+                if (a && plk_v4p_obs_slot(j, a, p) == PLK_V4P_NONE) { out.push_back(PlkV4SOp{(unsigned)(PLK_V4S_ADVANCE + a - 1), 0u}); a = 0; }
+                if (plk_v4p_obs_slot(j, a, p) == PLK_V4P_NONE) return false;
+                out.push_back(PlkV4SOp{plk_v4p_obs_slot(j, a, p), T[m] << 16 | (unsigned)(8 * (m % 4))});
+                oi++;
+            }
+            continue;
+        }
+        const bool stack_op = (h >= 8 && h < 8 + PLK_V4P_STACK_SLOTS) || (h >= 16 && h < 16 + PLK_V4P_STACK_SLOTS) ||
+                              (h >= 24 && h < 24 + PLK_V4P_STACK_SLOTS) || (h >= 28 && h < 28 + PLK_V4P_STACK_SLOTS);
+        if (h != OP_MATVEC && h != OP_SCALE && !stack_op) return false;
+        if (h == OP_SCALE && !out.empty() && out.back().h >= 28 && out.back().h < 28 + PLK_V4P_STACK_SLOTS) { out.back().h += PLK_V4S_FOLD_SCALE - 28; continue; }
+        out.push_back(PlkV4SOp{h, 0u});
+    }
+    y1 = T[std::min(1, last)]; b1 = (unsigned)(8 * (std::min(1, last) % 4));
+    return true;
+}
+
+/* vs: a stream plk_fused_check_v4s has accepted; vp.words stays empty where the form does not apply */
+static inline void plk_fused_v4p_build(const PlkFusedV4S &vs, PlkFusedV4P &vp)
+{
+    vp = PlkFusedV4P();
+    std::vector<PlkV4SOp> ops, out;
+    std::vector<unsigned> words, y1s;
+    size_t stride = 0;
+    for (int c = 0; c < vs.C; c++) {
+        unsigned y1 = 0, b1 = 0;
+        int npair = 0, pair_adv[2];
+        if (!plk_v4s_stream_ops(&vs.words[(size_t)c * vs.stride], vs.stride, ops)) return;
+        if (!plk_v4p_derive_ops(ops, vs.first_y[c], vs.nobs, out, y1, b1, npair, pair_adv)) return;
+        if (c == 0) {
+            stride = plk_v4s_block_stride(out.size());
+            words.assign((size_t)vs.C * stride, 0u);
+            vp.first_b1 = b1; vp.npair = npair; vp.pair_adv[0] = pair_adv[0]; vp.pair_adv[1] = pair_adv[1];
+        } else if (plk_v4s_block_stride(out.size()) != stride || b1 != vp.first_b1 || npair != vp.npair) { vp = PlkFusedV4P(); return; }
+        plk_v4s_block_ops(out, &words[(size_t)c * stride], stride);
+        y1s.push_back(y1);
+    }
+    vp.words.swap(words); vp.stride = stride; vp.first_y1.swap(y1s);
+}
+
+/* Replays the pair-product stream against the checked one.  Blocks, REFILLs, END and spare blocks as for the folded
+ * stream; every handler is one the 3-slot table has.  Walking both streams in step, with the ADVANCE ops of the checked
+ * one skipped: a non-observation op is the checked stream's op (a + SCALE variant: MATVEC + POPMUL d and the SCALE after
+ * it); an observation handler stands for the checked stream's observation op of the same kind, a PAIR for two adjacent ones
+ * that plk_v4p_pairable accepts -- so, unfolded, the ops are the checked stream's exactly.  The machine state is replayed
+ * with them: a handler of parity p consumes buffer p, which must hold the row of exactly its observation (requested, not
+ * overwritten since, and waited for: every handler but TIP_MUL-without-wait starts with a wait for all outstanding
+ * look-ups, that one needs a waiting handler since the request); every extraction names the byte and the table the checked
+ * stream names for that observation and reads the chunk that is current; folded ADVANCEs alternate in kind from 0, are as
+ * many as the checked stream's and request no chunk past the unit's. */
+static inline std::string plk_fused_check_v4p(const PlkFusedV4S &vs, const PlkFusedV4P &vp)
+{
+    if (vp.stride % 16 != 0 || vp.stride < 48 || vp.words.size() != (size_t)vs.C * vp.stride || (int)vp.first_y1.size() != vs.C) return "v4p stream: word count";
+    const int nobs = vs.nobs, last = nobs - 1;
+    if (nobs < 1 || vs.chunks != plk_stream_chunks(nobs)) return "v4p stream: observation count";
+    std::vector<PlkV4SOp> want, got;
+    std::vector<unsigned> T(nobs);
+    for (int c = 0; c < vs.C; c++) {
+        const unsigned *wd = &vp.words[(size_t)c * vp.stride];
+        const size_t nblocks = vp.stride / 16;
+        long end_block = -1;
+        got.clear();
+        for (size_t b = 0; b < nblocks; b++)
+            for (int j = 0; j < 8; j++) {
+                const unsigned lo = wd[(b * 8 + j) * 2], hi = wd[(b * 8 + j) * 2 + 1];
+                if (lo % PLK_V4_HANDLER_BYTES != 0 || lo >= (unsigned)PLK_V4_HANDLER_SLOTS * PLK_V4_HANDLER_BYTES) return plk_fmt("v4p stream: handler offset in block %ld", (long)b);
+                const unsigned hidx = lo / PLK_V4_HANDLER_BYTES;
+                if (j == 7) {
+                    if (hidx != (unsigned)((b & 1) ? PLK_V4_REFILL_B : PLK_V4_REFILL_A) || hi != 0) return plk_fmt("v4p stream: block %ld does not end in its REFILL op", (long)b);
+                    continue;
+                }
+                if (hidx == (unsigned)PLK_V4_REFILL_A || hidx == (unsigned)PLK_V4_REFILL_B) return plk_fmt("v4p stream: REFILL op inside block %ld", (long)b);
+                if (end_block >= 0) { if (hidx != OP_END || hi != 0) return "v4p stream: ops after END"; continue; }
+                if (hidx == OP_END) { if (hi != 0) return "v4p stream: stray fields in END"; end_block = (long)b; continue; }
+                got.push_back(PlkV4SOp{hidx, hi});
+            }
+        if (end_block < 0) return "v4p stream: no END";
+        if ((size_t)end_block + 2 >= nblocks) return "v4p stream: fewer than two spare blocks after the END";
+        if (!plk_v4s_stream_ops(&vs.words[(size_t)c * vs.stride], vs.stride, want)) return "v4p stream: the checked stream has no END";
+        /* byte and table of every observation, as the checked stream names them */
+        int k = 0, nadv_want = 0;
+        T[0] = vs.first_y[c];
+        for (const PlkV4SOp &op : want) {
+            if (plk_v4s_is_advance(op.h)) { nadv_want++; continue; }
+            if (!plk_word_is_obs(op.h)) continue;
+            if (k >= nobs) return "v4p stream: the checked stream has more observation ops than observations";
+            const int next = std::min(k + 1, last);
+            if ((op.hi & 0xffffu) != (unsigned)(8 * (next % 4)) || (k == last && (op.hi >> 16) != T[last])) return "v4p stream: fields of the checked stream";
+            T[next] = op.hi >> 16;
+            k++;
+        }
+        if (k != nobs) return "v4p stream: the checked stream's observation count";
+        if (vp.first_y1[c] != T[std::min(1, last)] || vp.first_b1 != (unsigned)(8 * (std::min(1, last) % 4))) return "v4p stream: prologue fields of the second observation";
+        /* prologue: chunk 0 current, chunks 1 .. AHEAD in flight; observations 0 and 1 requested and waited for */
+        long buf[2] = {0, std::min(1, last)};
+        bool landed[2] = {true, true};
+        int cur = 0, requested = PLK_V4S_AHEAD, nadv = 0, oi = 0;
+        if (requested >= vs.chunks) return "v4p stream: the prologue reads past the unit";
+        size_t wi = 0;
+        std::string bad;
+        auto skip_adv = [&]() { while (wi < want.size() && plk_v4s_is_advance(want[wi].h)) wi++; };
+        auto advance = [&](int kind) {
+            if (kind != (nadv & 1)) { bad = plk_fmt("v4p stream: ADVANCE %ld of the wrong kind", nadv); return; }
+            cur = requested - (PLK_V4S_AHEAD - 1);
+            requested++;
+            if (requested >= vs.chunks) bad = plk_fmt("v4p stream: ADVANCE %ld reads past the unit's chunks", nadv);
+            nadv++;
+        };
+        auto extract = [&](int m, unsigned byte, unsigned table) {
+            if (!bad.empty()) return;
+            if (byte != (unsigned)(m % 4)) bad = plk_fmt("v4p stream: the request of observation %ld extracts the wrong byte", m);
+            else if (cur != m / 4) bad = plk_fmt("v4p stream: the request of observation %ld extracts from chunk %ld, its code is in chunk %ld", m, cur, m / 4);
+            else if (table != T[m]) bad = plk_fmt("v4p stream: table field of the request of observation %ld", m);
+        };
+        for (size_t g = 0; g < got.size(); g++) {
+            const unsigned h = got[g].h, hi = got[g].hi;
+            const PlkV4PHandler hd = plk_v4p_decode(h);
+            if (plk_v4s_is_advance(h)) {
+                /* an ADVANCE with a dispatch of its own */
+                if (hi != 0) return plk_fmt("v4p stream: stray fields in op %ld", (long)g);
+                advance((int)(h - PLK_V4S_ADVANCE));
+                if (!bad.empty()) return bad;
+                continue;
+            }
+            skip_adv();
+            if (wi >= want.size()) return "v4p stream: more ops than the checked stream";
+            if (hd.kind == 1) {
+                const int j = hd.j, v = hd.v, p = hd.p;
+                if (want[wi].h != plk_v4p_obs_handler(j)) return plk_fmt("v4p stream: op %ld is not the checked stream's", (long)g);
+                wi++;
+                if (oi >= nobs || p != (oi & 1)) return plk_fmt("v4p stream: observation %ld handled on the other buffer", oi);
+                if (j != 2) landed[0] = landed[1] = true;
+                if (buf[p] != oi || !landed[p]) return plk_fmt("v4p stream: buffer %ld does not hold observation %ld", p, oi);
+                if (v) advance(v - 1);
+                const int m = std::min(oi + 2, last);
+                if ((hi & 0xffe7u) != 0) return plk_fmt("v4p stream: stray bits in the fields of observation %ld", oi);
+                extract(m, (hi & 0x18u) >> 3, hi >> 16);
+                if (!bad.empty()) return bad;
+                buf[p] = m; landed[p] = false; oi++;
+            } else if (hd.kind == 2) {
+                const int v = hd.v, p = hd.p;
+                const unsigned a = want[wi].h;
+                wi++;
+                skip_adv();
+                if (wi >= want.size() || !plk_v4p_pairable(a, want[wi].h)) return plk_fmt("v4p stream: PAIR op %ld where the checked stream has no pair of look-ups", (long)g);
+                wi++;
+                if (oi + 1 >= nobs || p != (oi & 1)) return plk_fmt("v4p stream: PAIR of observation %ld on the other buffers", oi);
+                landed[0] = landed[1] = true;
+                if (buf[p] != oi || buf[1 - p] != oi + 1) return plk_fmt("v4p stream: the buffers do not hold observations %ld and %ld", oi, oi + 1);
+                if ((hi & 0x80000004u) != 0) return plk_fmt("v4p stream: stray bits in the fields of the PAIR of observation %ld", oi);
+                const int m1 = std::min(oi + 2, last), m2 = std::min(oi + 3, last);
+                if (v == 1 || v == 2) advance(v - 1);
+                extract(m1, hi & 3u, (hi >> 5) & 0x1fffu);
+                if (v >= 3) advance(v - 3);
+                extract(m2, (hi >> 3) & 3u, (hi >> 18) & 0x1fffu);
+                if (!bad.empty()) return bad;
+                buf[p] = m1; buf[1 - p] = m2; landed[0] = landed[1] = false; oi += 2;
+            } else {
+                if (hi != 0) return plk_fmt("v4p stream: stray fields in op %ld", (long)g);
+                if (h >= PLK_V4S_FOLD_SCALE && h < PLK_V4S_FOLD_SCALE + PLK_V4P_STACK_SLOTS) {
+                    if (want[wi].h != h - PLK_V4S_FOLD_SCALE + 28 || wi + 1 >= want.size() || want[wi + 1].h != OP_SCALE) return plk_fmt("v4p stream: + SCALE variant at op %ld where no SCALE follows", (long)g);
+                    wi += 2;
+                    landed[0] = landed[1] = true;
+                    continue;
+                }
+                const bool matvec = h == OP_MATVEC || (h >= 24 && h < 24 + PLK_V4P_STACK_SLOTS) || (h >= 28 && h < 28 + PLK_V4P_STACK_SLOTS);
+                const bool plain = h == OP_SCALE || (h >= 8 && h < 8 + PLK_V4P_STACK_SLOTS) || (h >= 16 && h < 16 + PLK_V4P_STACK_SLOTS);
+                if (!matvec && !plain) return plk_fmt("v4p stream: op %ld names a handler the 3-slot table does not have", (long)g);
+                if (want[wi].h != h || want[wi].hi != 0) return plk_fmt("v4p stream: op %ld is not the checked stream's", (long)g);
+                wi++;
+                if (matvec) landed[0] = landed[1] = true;
+            }
+        }
+        skip_adv();
+        if (wi != want.size() || oi != nobs) return "v4p stream: END before the checked stream's last op";
+        if (nadv != nadv_want) return "v4p stream: another number of ADVANCEs than the checked stream's";
+    }
+    return "";
+}
+
+/*
  * The vector ll kernel (k_ll_vec, plk_vec.h) on the pair-table program: int4 ops
  *   observation (TIP_SET / TIP_MUL)  x = opcode, y = first row of the op's table (unit * nchar: the kernel adds the code),
  *                                    w = staged row of the NEXT observation op (cyclic)
@@ -1313,12 +1619,14 @@ enum { PLK_K4_LDS_V4S_768 = 0, PLK_K4_LDS_V4_768, PLK_K4_LDS_V4_512 };     /* Pl
  * kernel and tile, forced; 7 the streamed form wherever it fits), + 8 without the scalar-cache warm-up, + 16 / + 32 the
  * waves of the streamed form meet before every unit only / never (default: before every category), + 64 the streamed form
  * as it was before the folded op stream and the held first chunks (the checked stream unfolded, every category requests
- * the unit's first three chunks itself), + 128 / + 256 without the held chunks only / without the fold only.  The + bits
- * are for measurements. */
-struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held; };
+ * the unit's first three chunks itself), + 128 / + 256 without the held chunks only / without the fold only, + 512 without the
+ * pair-product form (the folded stream with held chunks on every tree; that form needs both, so + 64 / + 128 / + 256 turn
+ * it off as well).  The + bits are for measurements. */
+struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held, pair; };
 static inline PlkPairTablesOpt plk_pair_tables_opt(long v)
 {
-    return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2, (v & (64 | 256)) ? 0 : 1, (v & (64 | 128)) ? 0 : 1};
+    return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2, (v & (64 | 256)) ? 0 : 1, (v & (64 | 128)) ? 0 : 1,
+            (v & (64 | 128 | 256 | 512)) ? 0 : 1};
 }
 
 struct PlkK4Shape {
@@ -1338,6 +1646,7 @@ struct PlkK4Choice {
     unsigned tip_base = 0;                           /* v4 / v4s: LDS address of the table image = static LDS of the kernel */
     int warm = 1, sync = 2;                          /* pair-table kernels: the measurement bits of PLK_OPT_PAIR_TABLES */
     int fold = 1, held = 1;                          /* v4s: folded op stream, first chunks held across the categories */
+    int pair = 0;                                    /* v4s: the pair-product form is asked for and the program is within its 3 slots */
     std::string bad;                                 /* the replay check of the chosen variant's formats; empty: fine */
 };
 
@@ -1372,6 +1681,7 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
             for (const PlkFusedPT::VOp &o : fpt.vops) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) any_obs = true;
             if (any_obs && lds + st <= plk_pt_lds_limit(1024) && (st + lds) / 32 < 65536 && fpt.units < 2048 && fpt.row_node.size() < 65536) {
                 ch.variant = PLK_K4_V4S; ch.tile = 1536; ch.NS = 2; ch.block = 768; ch.lds = lds; ch.tip_base = (unsigned)st;
+                ch.pair = po.pair && pg.slots_needed <= PLK_V4P_STACK_SLOTS;
                 plk_fused_v4s_words(fpt, nchar, sh.C, ch.tip_base, fv4s);
                 /* the 32-bit program is replayed whatever the form (streamed: no code rows in LDS; its fields are the chain the
                  * streamed words are checked against) */

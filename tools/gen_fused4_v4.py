@@ -51,6 +51,31 @@ observation ops do not sit in LDS rows, they arrive packed four to a dword from 
   60 + d         MATVEC + POPMUL slot d, then SCALE
   Two prologues over one handler table: PLK_V4S_PROLOGUE requests the unit's first three chunks itself and waits for the
   first; PLK_V4S_PROLOGUE_HELD copies them from three 64-bit operands that the kernel loaded once per unit.
+
+Third emission mode, PAIR PRODUCTS (k_ll_fused4_v4s<768, true, true>, plk_fused4_v4s.h -> plk_fused4_v4p_asm.h): the streamed form for
+programs that need at most 3 stack slots.  The registers of stack slot 3 are a second look-up buffer: the row of
+observation n lands in buffer n & 1 (buffer 0 = v[56:71], buffer 1 = v[130:145]), an observation handler consumes its own
+buffer and requests observation n + 2 into it (the chain is two ahead; the prologue starts it with observations 0 and 1),
+and a PAIR handler forms x = P[n] * P[n + 1] from both buffers with one multiply per state and site -- what TIP_SET n,
+TIP_MUL n + 1 and TIP_SET + PUSH d, TIP_SET + POPMUL d compute with eight moves more -- and requests n + 2 and n + 3.
+What differs from the streamed text above:
+  hi dword  observation ops: the fields name the observation TWO after the op's (clamped to the last one)
+            PAIR ops: bits 1:0 byte of observation n + 2 in its dword, bits 4:3 byte of observation n + 3, bits 17:5 and
+            bits 30:18 LDS offset / 32 of their tables (bits 2 and 31 are zero)
+  The table keeps its 64 slots of 512 bytes (the compiler's branches across the statement stay within their 16-bit reach).
+  Indices 2, 6, 7, 8 + d, 16 + d, 24 + d, 28 + d, 32, 33, 34 + k and 60 + d as above with d < 3: no handler touches slot 3.
+  The extraction that needs a new dword is the one of an observation with an index that is a multiple of 4: two ahead, it
+  falls into the handler of an even observation, the first of a PAIR of an even one or the second of a PAIR of an odd one,
+  so handlers with an ADVANCE inside exist for those parities only.
+  PAIR_OBS_HANDLERS[j] on buffer 0    its index of the streamed table (0, 1, 3, 4, 12 + d, 20 + d)
+  PAIR_OBS_HANDLERS[j] on buffer 1    PAIR_OBS_ODD[j] (5, 11, 15, 19, 23, 27, 31, none, 59, 63)
+  36 + 2 jj + k   observation handler PAIR_OBS_FOLDED[jj] on buffer 0 with ADVANCE_k before its extraction (all but TIP_SET
+                  alone and TIP_MUL without wait, which binary trees do not produce: their ADVANCE keeps its dispatch)
+  TIP_SET + PUSH slot 0 exists on buffer 0 without ADVANCE only: a look-up goes to slot 0 when the stack is empty and no
+  vector is under construction, which in every tree tried is the program's first observation (tests/pairmulcheck_main.cpp
+  finds no other); a program that had it on buffer 1 gets no pair-product stream and runs the folded one.
+  52, 53 + k      PAIR of an even observation: no ADVANCE, ADVANCE_k before the first extraction
+  55, 56 + k      PAIR of an odd observation: no ADVANCE, ADVANCE_k between the two extractions
 """
 import os
 
@@ -89,19 +114,29 @@ def matvec(dst_a=None, dst_b=None):
     return out
 
 
-def tipmul():
+def tipmul(buf=PA):
+    """buf: first register of the look-up buffer (site A; site B 8 registers further)"""
     out = []
     for i in range(4):
-        out.append("v_mul_f64 %s, %s, %s" % (pair(XA + 2 * i), pair(XA + 2 * i), pair(PA + 2 * i)))
-        out.append("v_mul_f64 %s, %s, %s" % (pair(XB + 2 * i), pair(XB + 2 * i), pair(PB + 2 * i)))
+        out.append("v_mul_f64 %s, %s, %s" % (pair(XA + 2 * i), pair(XA + 2 * i), pair(buf + 2 * i)))
+        out.append("v_mul_f64 %s, %s, %s" % (pair(XB + 2 * i), pair(XB + 2 * i), pair(buf + 8 + 2 * i)))
     return out
 
 
-def tipset():
+def tipset(buf=PA):
     out = []
     for i in range(4):
-        out.append("v_mov_b64 %s, %s" % (pair(XA + 2 * i), pair(PA + 2 * i)))
-        out.append("v_mov_b64 %s, %s" % (pair(XB + 2 * i), pair(PB + 2 * i)))
+        out.append("v_mov_b64 %s, %s" % (pair(XA + 2 * i), pair(buf + 2 * i)))
+        out.append("v_mov_b64 %s, %s" % (pair(XB + 2 * i), pair(buf + 8 + 2 * i)))
+    return out
+
+
+def pairmul(first, second):
+    """x = first buffer o second buffer: TIP_SET of the first and TIP_MUL of the second without the copy"""
+    out = []
+    for i in range(4):
+        out.append("v_mul_f64 %s, %s, %s" % (pair(XA + 2 * i), pair(first + 2 * i), pair(second + 2 * i)))
+        out.append("v_mul_f64 %s, %s, %s" % (pair(XB + 2 * i), pair(first + 8 + 2 * i), pair(second + 8 + 2 * i)))
     return out
 
 
@@ -114,13 +149,24 @@ def tipnext():
             "ds_read_u8 v74, v76", "@HALF ds_read_u8 v75, v76"]
 
 
-def tipnext_s():
+def lookup(buf, bits, table):
+    """request the rows of the codes at bit offset `bits` of the current dwords from table `table` into buffer buf"""
+    return ["v_bfe_u32 v72, v74, %s, 8" % bits, "v_bfe_u32 v73, v75, %s, 8" % bits,
+            "v_add_lshl_u32 v72, v72, %s, 5" % table, "v_add_lshl_u32 v73, v73, %s, 5" % table,
+            "ds_read_b128 v[%d:%d], v72" % (buf, buf + 3), "ds_read_b128 v[%d:%d], v72 offset:16" % (buf + 4, buf + 7),
+            "ds_read_b128 v[%d:%d], v73" % (buf + 8, buf + 11), "ds_read_b128 v[%d:%d], v73 offset:16" % (buf + 12, buf + 15)]
+
+
+def tipnext_s(buf=PA):
     # v_bfe_u32 reads bits 4:0 of its offset operand only: the op's field dword serves as it is
-    return ["s_lshr_b32 s28, s23, 16",
-            "v_bfe_u32 v72, v74, s23, 8", "v_bfe_u32 v73, v75, s23, 8",
-            "v_add_lshl_u32 v72, v72, s28, 5", "v_add_lshl_u32 v73, v73, s28, 5",
-            "ds_read_b128 v[56:59], v72", "ds_read_b128 v[60:63], v72 offset:16",
-            "ds_read_b128 v[64:67], v73", "ds_read_b128 v[68:71], v73 offset:16"]
+    return ["s_lshr_b32 s28, s23, 16"] + lookup(buf, "s23", "s28")
+
+
+def pairnext(which, buf):
+    """the two requests of a PAIR op: field layout in the module text"""
+    if which == 0:
+        return ["s_lshl_b32 s28, s23, 3", "s_bfe_u32 s29, s23, 0xd0005"] + lookup(buf, "s28", "s29")
+    return ["s_and_b32 s28, s23, 0x18", "s_lshr_b32 s29, s23, 18"] + lookup(buf, "s28", "s29")
 
 
 RING = (146, 148)             # streamed mode: register pairs of the two chunks in flight
@@ -149,21 +195,21 @@ def popmul(d):
     return out
 
 
-def setpop(d):
+def setpop(d, buf=PA):
     """x = prefetched value o slot d (TIP_SET followed by POPMUL: no copy of the value)"""
     out = []
     for i in range(4):
-        out.append("v_mul_f64 %s, %s, %s" % (pair(XA + 2 * i), pair(PA + 2 * i), pair(slot_regs(d, 0)[i])))
-        out.append("v_mul_f64 %s, %s, %s" % (pair(XB + 2 * i), pair(PB + 2 * i), pair(slot_regs(d, 1)[i])))
+        out.append("v_mul_f64 %s, %s, %s" % (pair(XA + 2 * i), pair(buf + 2 * i), pair(slot_regs(d, 0)[i])))
+        out.append("v_mul_f64 %s, %s, %s" % (pair(XB + 2 * i), pair(buf + 8 + 2 * i), pair(slot_regs(d, 1)[i])))
     return out
 
 
-def setpush(d):
+def setpush(d, buf=PA):
     """slot d = prefetched value (TIP_SET followed by PUSH: the vector under construction is dead after a PUSH)"""
     out = []
     for i in range(4):
-        out.append("v_mov_b64 %s, %s" % (pair(slot_regs(d, 0)[i]), pair(PA + 2 * i)))
-        out.append("v_mov_b64 %s, %s" % (pair(slot_regs(d, 1)[i]), pair(PB + 2 * i)))
+        out.append("v_mov_b64 %s, %s" % (pair(slot_regs(d, 0)[i]), pair(buf + 2 * i)))
+        out.append("v_mov_b64 %s, %s" % (pair(slot_regs(d, 1)[i]), pair(buf + 8 + 2 * i)))
     return out
 
 
@@ -190,17 +236,61 @@ FOLD_ADV0 = 36                # 36 + 2 j + k: OBS_HANDLERS[j] with ADVANCE_k bef
 FOLD_SCALE0 = 60              # 60 + d: MATVEC + POPMUL slot d, then SCALE
 
 
-def obs_handlers(tipnext):
-    """the observation handlers (OBS_HANDLERS) without their dispatch; tipnext: the prefetch of the next observation"""
+def obs_handlers(tipnext, buf=PA, slots=4):
+    """the observation handlers (OBS_HANDLERS) without their dispatch; tipnext: the prefetch of the next observation; buf:
+    the look-up buffer they consume; slots: stack slots they exist for"""
     h = {}
-    h[0] = ["s_waitcnt lgkmcnt(0)"] + tipset() + tipnext()
-    h[1] = ["s_waitcnt lgkmcnt(0)"] + tipmul() + tipnext()
-    h[3] = tipmul() + tipnext()
-    h[4] = matvec() + tipmul() + tipnext()
-    for d in range(4):
-        h[12 + d] = ["s_waitcnt lgkmcnt(0)"] + setpop(d) + tipnext()
-        h[20 + d] = ["s_waitcnt lgkmcnt(0)"] + setpush(d) + tipnext()
-    assert tuple(sorted(h)) == OBS_HANDLERS
+    h[0] = ["s_waitcnt lgkmcnt(0)"] + tipset(buf) + tipnext()
+    h[1] = ["s_waitcnt lgkmcnt(0)"] + tipmul(buf) + tipnext()
+    h[3] = tipmul(buf) + tipnext()
+    h[4] = matvec() + tipmul(buf) + tipnext()
+    for d in range(slots):
+        h[12 + d] = ["s_waitcnt lgkmcnt(0)"] + setpop(d, buf) + tipnext()
+        h[20 + d] = ["s_waitcnt lgkmcnt(0)"] + setpush(d, buf) + tipnext()
+    assert tuple(sorted(h)) == (OBS_HANDLERS if slots == 4 else PAIR_OBS_HANDLERS)
+    return h
+
+
+# ---- pair products: two look-up buffers, the chain two ahead ----
+BUF = (PA, STACK0 + 48)       # buffer 1 = the registers of stack slot 3
+PAIR_SLOTS = 3
+PAIR_OBS_HANDLERS = (0, 1, 3, 4, 12, 13, 14, 20, 21, 22)       # on buffer 0: the streamed table's indices
+PAIR_OBS_ODD = (5, 11, 15, 19, 23, 27, 31, None, 59, 63)       # the same handlers on buffer 1
+PAIR_OBS_FOLDED = (1, 4, 12, 13, 14, 21, 22)                   # 36 + 2 jj + k: on buffer 0 with ADVANCE_k inside
+PAIR_FOLD0 = 36
+PAIR_EVEN0, PAIR_ODD0 = 52, 55
+
+
+def pair_handlers():
+    h = {2: matvec() + RET, 6: scale() + RET, 7: ["s_branch .Ldone_%="]}
+    for d in range(PAIR_SLOTS):
+        h[8 + d] = push(d) + RET
+        h[16 + d] = popmul(d) + RET
+        h[24 + d] = matvec(slot_regs(d, 0), slot_regs(d, 1)) + RET
+        h[28 + d] = matvec() + popmul(d) + RET
+        h[FOLD_SCALE0 + d] = matvec() + popmul(d) + scale() + RET
+    full = handlers(True)
+    for idx in (REFILL_A, REFILL_B, ADVANCE0, ADVANCE0 + 1):
+        h[idx] = full[idx]
+    for p in range(2):
+        obs = obs_handlers(lambda: tipnext_s(BUF[p]), BUF[p], PAIR_SLOTS)
+        for j, idx in enumerate(PAIR_OBS_HANDLERS):
+            if (PAIR_OBS_HANDLERS, PAIR_OBS_ODD)[p][j] is not None:
+                h[(PAIR_OBS_HANDLERS, PAIR_OBS_ODD)[p][j]] = obs[idx] + RET
+    for k in range(2):
+        obs = obs_handlers(lambda: advance(k) + tipnext_s(BUF[0]), BUF[0], PAIR_SLOTS)
+        for jj, idx in enumerate(PAIR_OBS_FOLDED):
+            h[PAIR_FOLD0 + 2 * jj + k] = obs[idx] + RET
+
+    def pair_handler(p, before, between):
+        return (["s_waitcnt lgkmcnt(0)"] + pairmul(BUF[p], BUF[1 - p]) + before + pairnext(0, BUF[p]) + between +
+                pairnext(1, BUF[1 - p]) + RET)
+    h[PAIR_EVEN0] = pair_handler(0, [], [])
+    h[PAIR_ODD0] = pair_handler(1, [], [])
+    for k in range(2):
+        h[PAIR_EVEN0 + 1 + k] = pair_handler(0, advance(k), [])
+        h[PAIR_ODD0 + 1 + k] = pair_handler(1, [], advance(k))
+    assert sorted(set(range(NSLOTS)) - set(h)) == [50, 51, 58]       # 22 + 19 + 14 + 6 handlers
     return h
 
 
@@ -229,7 +319,7 @@ def handlers(streamed=False):
     return h
 
 
-def emit(streamed=False, held=False):
+def emit(streamed=False, held=False, pairs=False):
     """-> (prologue up to the dispatch of the first op, handler table and epilogue)"""
     L = []           # (text, is_label)
 
@@ -271,6 +361,9 @@ def emit(streamed=False, held=False):
                 "v_add_lshl_u32 v72, v72, %[y0], 5", "v_add_lshl_u32 v73, v73, %[y0], 5",
                 "ds_read_b128 v[56:59], v72", "ds_read_b128 v[60:63], v72 offset:16",
                 "ds_read_b128 v[64:67], v73", "ds_read_b128 v[68:71], v73 offset:16",
+                # pair products: the second observation's values into buffer 1 (its byte and table are operands: a program
+                # with one observation names the first again)
+                ] + (lookup(BUF[1], "%[b1]", "%[y1]") if pairs else []) + [
                 "s_waitcnt lgkmcnt(0)"]
     else:
         pro += [
@@ -287,7 +380,7 @@ def emit(streamed=False, held=False):
     ins(RET)           # the first op
     npro = len(L)
     # ---- handlers ----
-    h = handlers(streamed)
+    h = pair_handlers() if pairs else handlers(streamed)
     ins([".p2align 15", ".Lh0_%=:"])
     for idx in range(NSLOTS):
         if idx:
@@ -325,11 +418,13 @@ def main():
              "v_sub_u32": 8, "v_ldexp_f64": 8, "v_add3_u32": 8, "v_add_lshl_u32": 8, "v_lshl_add_u32": 8, "ds_read_b128": 8,
              "ds_read_u8": 8, "s_waitcnt": 4, "s_add_u32": 8, "s_addc_u32": 4, "s_load_dwordx16": 8, "s_setpc_b64": 4,
              "s_lshr_b32": 4, "s_and_b32": 8, "s_branch": 4, "s_movrels_b64": 4, "s_addk_i32": 4, "s_or_b32": 4, "s_mov_b32": 4,
-             "v_bfe_u32": 8, "global_load_dwordx2": 8}
+             "v_bfe_u32": 8, "global_load_dwordx2": 8, "s_lshl_b32": 4, "s_bfe_u32": 8}
     for streamed in (False, True):
         for idx, body in handlers(streamed).items():
             n = sum(sizes[b.replace("@HALF ", "").split()[0]] for b in body)
             assert n <= HS, (streamed, idx, n)
+    for idx, body in pair_handlers().items():
+        assert sum(sizes[b.split()[0]] for b in body) <= HS, ("pairs", idx)
     vregs = ["v%d" % r for r in range(24, STACK0 + 64)]
     sregs = ["s%d" % r for r in range(20, 100)] + ["m0"]
     hdr = '''/* GENERATED by tools/gen_fused4_v4.py -- do not edit; change the generator and run it again.
@@ -403,6 +498,40 @@ def main():
     with open(path, "w") as f:
         f.write(hdr)
     print("wrote", path, "(%d asm lines)" % len(pro + held + lines))
+    # ---- pair products ----
+    held, lines = emit(True, True, True)
+    assert not any(t.startswith("@HALF ") for t in held + lines)
+    hdr = '''/* GENERATED by tools/gen_fused4_v4.py -- do not edit; change the generator and run it again.
+ *
+ * Assembly text of k_ll_fused4_v4s<768, true, true> (plk_fused4_v4s.h): the streamed two-sites-per-lane interpreter for programs within
+ * three stack slots, with two look-up buffers and PAIR ops.  Op format, handler numbering and the register map are
+ * documented in the generator. */
+#ifndef PLK_FUSED4_V4P_ASM_H
+#define PLK_FUSED4_V4P_ASM_H
+
+#define PLK_V4P_STACK_SLOTS %d
+#define PLK_V4P_FOLD_ADV %d
+#define PLK_V4P_PAIR_EVEN %d
+#define PLK_V4P_PAIR_ODD %d
+/* handler index of observation kind j on buffer 0, on buffer 1 (-1: none), and the kinds with an ADVANCE inside in the order of
+ * their handlers; plk_v4p_obs_slot in plk_program.h states the same numbering and tests/pairmulcheck_main.cpp compares the two */
+#define PLK_V4P_GEN_OBS_EVEN {%s}
+#define PLK_V4P_GEN_OBS_ODD {%s}
+#define PLK_V4P_GEN_OBS_FOLDED {%s}
+
+/* the unit's first three chunks are the operands c0, c1, c2 */
+#define PLK_V4P_PROGRAM_HELD \\
+%s
+%s
+        ""
+
+#endif
+''' % (PAIR_SLOTS, PAIR_FOLD0, PAIR_EVEN0, PAIR_ODD0, ", ".join(str(v) for v in PAIR_OBS_HANDLERS),
+       ", ".join(str(-1 if v is None else v) for v in PAIR_OBS_ODD), ", ".join(str(v) for v in PAIR_OBS_FOLDED), c_string(held), c_string(lines))
+    path = os.path.join(os.path.dirname(path), "plk_fused4_v4p_asm.h")
+    with open(path, "w") as f:
+        f.write(hdr)
+    print("wrote", path, "(%d asm lines)" % len(held + lines))
 
 
 if __name__ == "__main__":
