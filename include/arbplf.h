@@ -69,12 +69,22 @@ char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *ret
  * independent); an "equilibrium_exit_rate" divisor is differentiated through (it carries the expected rate).  A model
  * without a mixture is refused. */
 char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode);
+/* Log likelihood of nearest-neighbour interchanges of the tree (the reference has no such command): what a tree search
+ * asks between two fits, from one pass over the current tree (plk_nni_ll in plk.h) in place of one arbplf-ll per candidate.
+ * Input: model_and_data, an optional site_reduction exactly as for arbplf-ll, and an optional "swaps": [[a, b], ...] in the
+ * edge indices of the document's `edges`.  A swap is a pair of edges a = (v -> c), b = (u -> s) with v a child of u and
+ * s != v; the swapped tree has a = (u -> c) and b = (v -> s): the two subtrees exchange parents, each edge keeps its index
+ * and rate, all data stay where they are.  Without "swaps": every swap of the tree, ordered by (a, b).
+ * Columns ["site", "first_edge", "second_edge", "value"], without the site column under site aggregation; rows in the
+ * order of the request, site outermost.  A pair that is no swap, a non-integer or an index out of range is an error; a
+ * value that is not finite (likelihood 0 under the swapped tree) is refused as arbplf-ll refuses it. */
+char *arbplf_nni_string(void *userdata, const char *s_in, int *retcode);
 
 /* Host-only validation of an input document (JSON grammar, model_and_data,
  * reductions) exactly as the corresponding query would perform it, without
  * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
  * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate" | "rate_matrix_deriv" |
- * "mixture_deriv".  0 = accepted.  Where the document selects at least one site this includes the preparation of the
+ * "mixture_deriv" | "nni" (the swap list is checked by the query itself).  0 = accepted.  Where the document selects at least one site this includes the preparation of the
  * model on the host (normalised rate matrix, category rates and priors) and the check of its values that every query
  * makes before any device work (plk_check_model_values in plk.h: non-finite or negative values, rate x length x |Qn|
  * beyond 2^40); the diagnostic names the edge in the order of the document's `edges`.  A document that selects no site

@@ -23,7 +23,8 @@
  *                          evaluate_site_marginal_unnormalized
  *                          (src/arbplfmarginal.c:111-264)
  * and add what the reference does not have: plk_cat_posterior (rate-category posteriors), plk_edge_pair_sums and
- * plk_rate_matrix_sens (site-summed outer products per edge; the gradient of the log likelihood in the rate matrix).
+ * plk_rate_matrix_sens (site-summed outer products per edge; the gradient of the log likelihood in the rate matrix),
+ * plk_nni_ll (the log likelihood of every nearest-neighbour interchange of the tree from one down pass).
  *
  * Conventions: every function returns 0 on success and a nonzero PLK_E_* code
  * on failure (plk_last_error() gives the text).  The caller owns all buffers
@@ -167,7 +168,7 @@ int plk_set_stream(plk_engine *h, void *hip_stream);
  * where its derivatives are not finite (likelihood 0).
  *
  * Nodes with many factors: plk_deriv, plk_marginal, plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens,
- * plk_mixture_sens, plk_second_order and plk_hess keep one rescaling factor per node.  On a tree with a node that takes
+ * plk_mixture_sens, plk_nni_ll, plk_second_order and plk_hess keep one rescaling factor per node.  On a tree with a node that takes
  * more than 32 edge factors at once (33 leaf children, or three children over 16 edges each) they first measure the
  * node products on the device; where one has no entry of at least 2^-969 at some site they return PLK_E_ARG, the
  * diagnostic naming the query and the node, and the engine stays usable.  With ordinary branch lengths nothing is refused.
@@ -304,6 +305,32 @@ int plk_mixture_chain(int mode, int n, const double *rates, const double *prior,
                       double *drates_out, double *dprior_out, double *dshape_out, double *dinvariable_out,
                       int *has_invariable_out, char *err, size_t errlen);
 
+/*
+ * Nearest-neighbour interchanges (the reference has no such query).  The tree is rooted and directed as everywhere here.
+ * A swap is a pair of CSR edges (a, b) with a = (v -> c), b = (u -> s), v a child of u and s != v.  The swapped tree has
+ * a = (u -> c) and b = (v -> s): the two subtrees exchange parents; each edge keeps its index, its rate coefficient and
+ * the subtree below it; data on u, v and every other node stay where they are; every node keeps its number of children.
+ * Multifurcations, unary nodes, leaves as c or s and the root as u are all allowed; a leaf v has no swap.
+ *
+ * plk_nni_swaps: host only, no engine and no GPU involved.  Returns the number of swaps of the tree (0 for arrays that are
+ * no tree) and, when pairs_out is not NULL, fills the canonical list [count][2], ordered by a, then by b.
+ *
+ * plk_nni_ll: the log likelihood ll'_s of every site under every listed swapped tree, from the vectors of ONE down pass
+ * over the current tree and one up pass per 256 swaps (plk_nni.h): a swap costs a handful of k x k products at u and v,
+ * whatever the size of the tree.  swaps: [n_swaps][2] CSR edge pairs; NULL = the canonical list, n_swaps being its length.
+ * Repeated pairs are allowed, and a pair has the same bits wherever it stands in whatever list.  site_out: NULL or
+ * [n_swaps][S] host; sums_out: NULL or [n_swaps][2] double-double sums of w_s ll'_s, summed in a fixed order.
+ * Nothing is divided by the likelihood of the current tree: a swapped tree may have positive likelihood where the current
+ * one has none, and the other way round.  A site of likelihood 0 under the swapped tree has ll' = -inf; in the sums it
+ * behaves as in plk_ll (weight exactly 0: it adds nothing; otherwise the sum is not finite).
+ * PLK_E_ARG, the diagnostic naming the pair, for a pair that is no swap (the same edge twice, s = v, edges further apart,
+ * reversed order, an index out of range); nothing has run then and the engine stays usable.  Preconditions as for
+ * plk_deriv (nodes with more than 32 factors: the same range check and refusal).  Which tree the engine holds does not
+ * change.  PLK_INFO_NNI_KERNEL, PLK_INFO_DOWN4_KERNEL and PLK_INFO_LAST_QUERY_NS report on the call.
+ */
+int plk_nni_swaps(int N, const int *indptr, const int *indices, int *pairs_out /* NULL or [count][2] */);
+int plk_nni_ll(plk_engine *h, int n_swaps, const int *swaps, double *site_out, double *sums_out);
+
 /* the scaled Frechet matrices coef_{c,e} * F_{c,e} themselves, [C][E][k][k] host (tests) */
 int plk_get_frechet_matrices(plk_engine *h, const double *L_hi, const double *L_lo, int coef_mode,
                              double *F_out);
@@ -398,7 +425,7 @@ enum {
     PLK_INFO_PAIR_SUMS_KERNEL = 14, /* up pass of the last plk_edge_pair_sums / plk_rate_matrix_sens: 0 = none yet, 1 = the k = 4
                                        kernel (compact codes, at most 4 categories), 2 = generic */
     PLK_INFO_LAST_QUERY_NS = 15,    /* HIP-event time from the first to the last device operation of the last plk_deriv,
-                                       plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens or plk_mixture_sens
+                                       plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens, plk_mixture_sens or plk_nni_ll
                                        (0 when it could not be taken); for tools/time_rate_matrix_deriv.py and
                                        tools/time_mixture_deriv.py */
     PLK_INFO_MIXTURE_SENS_KERNEL = 16, /* up pass of the last plk_mixture_sens: 0 = none yet, 1 = the k = 4 kernel (compact
@@ -409,7 +436,7 @@ enum {
                                        product of two table rows), 8 = two-leaf nodes finished inside their parent's visit
                                        (one rate category); 0 when another kernel family ran */
     PLK_INFO_DOWN4_KERNEL = 18,     /* k = 4 down pass of the last query that ran on the k = 4 up/down kernels (deriv, marginal,
-                                       expectations, and the pair-sum and mixture-gradient passes): 4, 8 or 16 = k_down_fused4<D>
+                                       expectations, and the pair-sum, mixture-gradient and swap passes): 4, 8 or 16 = k_down_fused4<D>
                                        with a register stack of that depth, 0 = k_down_store4 (the staged code rows do not fit
                                        the LDS, or the tree needs more than 16 slots) or no such query yet */
     PLK_INFO_LL_FORM = 19,          /* form of the last ll evaluation's k = 4 pair-table kernel: 1 = streamed codes with the tables
@@ -419,13 +446,15 @@ enum {
                                        kernel, a tree that needs 4 stack slots, PLK_OPT_PAIR_TABLES + 64 / + 128 / + 256 / + 512, or
                                        a stream that did not replay), else bit 0 = k_ll_fused4_v4s<768, true, true> ran its op stream and bits 8-23 =
                                        PAIR ops of one category (two table rows multiplied under one dispatch, saturating; can be 0) */
-    PLK_INFO_LL_FOLD = 20           /* op stream of the last ll evaluation's streamed kernel (0 for every other kernel), bit fields:
+    PLK_INFO_LL_FOLD = 20,          /* op stream of the last ll evaluation's streamed kernel (0 for every other kernel), bit fields:
                                        bit 0 = the folded op stream ran, bit 1 = the first chunks of a unit were held across the
                                        categories, bits 4-7 = stack slots d whose MATVEC + POPMUL + SCALE handler the stream
                                        dispatches, bits 8-15 = SCALE ops left with a dispatch of their own, bits 16-23 / 24-30 =
                                        observation ops of one category with ADVANCE_0 / ADVANCE_1 folded in (saturating).  Under
                                        the pair-product form (PLK_INFO_LL_PAIRMUL) bits 0 and 4-30 describe the folded stream it was
                                        derived next to: a PAIR op with an ADVANCE counts as the observation op that carried it */
+    PLK_INFO_NNI_KERNEL = 22        /* up pass of the last plk_nni_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
+                                       4 categories), 2 = generic */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -519,6 +548,9 @@ int plk_group_edge_pair_sums(plk_group *g, const int *edge_mask, double *W_out, 
 int plk_group_rate_matrix_sens(plk_group *g, double *G_out, double *root_out);
 /* prior_out, rate_out [C][2]: partial sums of the engines added in engine order (long double) */
 int plk_group_mixture_sens(plk_group *g, double *prior_out, double *rate_out);
+/* site_out [n_swaps][S] at the global site positions; sums_out [n_swaps][2]: partial sums of the engines added in engine
+ * order (long double) */
+int plk_group_nni_ll(plk_group *g, int n_swaps, const int *swaps, double *site_out, double *sums_out);
 int plk_group_hess(plk_group *g, double *hess_sums_out);
 int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out);   /* either may be NULL */
 

@@ -118,6 +118,12 @@ def arbplf_mixture_deriv(s):
     return _call("arbplf_mixture_deriv", s)
 
 
+def arbplf_nni(s):
+    """log likelihood of every nearest-neighbour interchange of the tree, or of the listed "swaps" (no counterpart in the
+    reference): columns site, first_edge, second_edge, value; site_reduction as for arbplf_ll"""
+    return _call("arbplf_nni", s)
+
+
 def _out_of_scope(name):
     def f(s):
         raise RuntimeError("arbplf likelihood error: %s is outside the MI355X hot path of this build" % name)

@@ -257,7 +257,7 @@ static int check_finite(double v, const char *what)
 }
 
 /* _parse of the drivers: kind 0 ll, 1 deriv, 2 marginal, 3 dwell, 4 trans, 5 em-update, 6 the second-order family,
- * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv, 10 mixture-deriv (no counterpart in the reference: its reduction grammar, its table layout)
+ * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv, 10 mixture-deriv, 11 nni (no counterpart in the reference: its reduction grammar, its table layout)
  * (src/arbplfll.c:250-288, src/arbplfderiv.c:445-493, src/arbplfmarginal.c:348-405,
  *  src/arbplfdwell.c:507-566, src/arbplftrans.c:553-614, src/arbplfem.c:505-545) */
 static int query_parse(query *q, int kind, const jval *root)
@@ -269,8 +269,9 @@ static int query_parse(query *q, int kind, const jval *root)
     static const char *const all_dwell[] = {"model_and_data", "site_reduction", "edge_reduction", "state_reduction", NULL};
     static const char *const all_trans[] = {"model_and_data", "site_reduction", "edge_reduction", "trans_reduction", NULL};
     static const char *const all_catpost[] = {"model_and_data", "site_reduction", "category_reduction", NULL};
+    static const char *const all_nni[] = {"model_and_data", "site_reduction", "swaps", NULL};
     const char *const *allowed = kind == 0 ? all_ll : kind == 1 ? all_deriv : kind == 2 ? all_marg :
-                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : kind == 7 ? all_catpost : all_ll;
+                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : kind == 7 ? all_catpost : kind == 11 ? all_nni : all_ll;
     if (host_check_keys(root, req, allowed, "input")) return -1;
     if (host_model_parse(&q->m, j_get(root, "model_and_data"))) return -1;
     if (host_reduction_parse(&q->r_site, (int)q->m.S, "site", j_get(root, "site_reduction"))) return -1;
@@ -1012,6 +1013,115 @@ done:
     return rc;
 }
 
+/* ------------------------------------------------------------------ nni (kind 11)
+ * The log likelihood of nearest-neighbour interchanges of the tree (no counterpart in the reference; include/plk.h:
+ * plk_nni_ll).  "swaps": [[a, b], ...] in the user's edge indices, a = (v -> c) and b = (u -> s) with v a child of u and
+ * s != v; omitted: every swap of the tree, ordered by (a, b) in the user's indices.  Columns site, first_edge,
+ * second_edge, value; rows in the order of the request, site outermost; the site column goes under site aggregation. */
+static int nni_pair_cmp(const void *x, const void *y)
+{
+    const int *p = x, *q = y;
+    return p[0] != q[0] ? (p[0] > q[0]) - (p[0] < q[0]) : (p[1] > q[1]) - (p[1] < q[1]);
+}
+
+static int run_nni(const jval *root, jbuf *out)
+{
+    query q;
+    int rc = -1;
+    int *user = NULL, *csr = NULL, *user_to_csr = NULL;
+    double *vals = NULL;
+    query_init(&q);
+    if (query_parse(&q, 11, root)) goto done;
+    const host_model *m = &q.m;
+    const int E = m->E;
+    user_to_csr = malloc((size_t)(E + 1) * sizeof(int));
+    if (!user_to_csr) goto done;
+    for (int e = 0; e < E; e++) user_to_csr[m->csr_to_user[e]] = e;
+    const jval *sw = j_get(root, "swaps");
+    int n = 0;
+    if (sw) {
+        if (!j_is_array(sw)) { fprintf(stderr, "error: swaps must be an array of pairs of edge indices\n"); goto done; }
+        n = (int)j_len(sw);
+        user = malloc((size_t)(2 * n + 2) * sizeof(int));
+        if (!user) goto done;
+        for (int i = 0; i < n; i++) {
+            const jval *p = j_at(sw, i);
+            if (!j_is_array(p) || j_len(p) != 2) { fprintf(stderr, "error: swaps: entry %d is not a pair of edge indices\n", i); goto done; }
+            for (int j = 0; j < 2; j++) {
+                const jval *x = j_at(p, j);
+                if (!j_is_int(x)) { fprintf(stderr, "error: swaps: entry %d: edge indices must be integers\n", i); goto done; }
+                if (x->u.i < 0 || x->u.i >= E) { fprintf(stderr, "error: swaps: entry %d: edge index %lld is out of range\n", i, x->u.i); goto done; }
+                user[2 * i + j] = (int)x->u.i;
+            }
+        }
+    } else {
+        n = plk_nni_swaps(m->N, m->indptr, m->indices, NULL);
+        user = malloc((size_t)(2 * n + 2) * sizeof(int));
+        if (!user) goto done;
+        plk_nni_swaps(m->N, m->indptr, m->indices, user);
+        for (int i = 0; i < 2 * n; i++) user[i] = m->csr_to_user[user[i]];
+        qsort(user, (size_t)n, 2 * sizeof(int), nni_pair_cmp);
+    }
+    csr = malloc((size_t)(2 * n + 2) * sizeof(int));
+    if (!csr) goto done;
+    for (int i = 0; i < 2 * n; i++) csr[i] = user_to_csr[user[i]];
+    /* a pair that is no swap is refused here, in the user's indices, whether or not a site is selected */
+    {
+        const int count = plk_nni_swaps(m->N, m->indptr, m->indices, NULL);
+        int *all = malloc((size_t)(2 * count + 2) * sizeof(int));
+        if (!all) goto done;
+        plk_nni_swaps(m->N, m->indptr, m->indices, all);           /* sorted by (a, b) in CSR indices */
+        for (int i = 0; i < n; i++)
+            if (!bsearch(csr + 2 * i, all, (size_t)count, 2 * sizeof(int), nni_pair_cmp)) {
+                fprintf(stderr, "error: swaps: entry %d: edges (%d, %d) are no swap: the first must start at a child of the node "
+                                "the second starts at, and the second must not end there\n", i, user[2 * i], user[2 * i + 1]);
+                free(all);
+                goto done;
+            }
+        free(all);
+    }
+    if (query_prepare(&q)) goto done;
+    const int agg = q.r_site.agg_mode != AGG_NONE;
+    const long U = q.U;
+    vals = malloc(((size_t)n * (agg ? 2 : (size_t)U) + 2) * sizeof(double));
+    if (!vals) goto done;
+    if (U > 0 && n > 0 && plk_group_nni_ll(q.eng, n, csr, agg ? NULL : vals, agg ? vals : NULL)) {
+        fprintf(stderr, "error: %s\n", plk_group_last_error(q.eng));
+        goto done;
+    }
+    jbuf_puts(out, agg ? "{\"columns\": [\"first_edge\", \"second_edge\", \"value\"], \"data\": ["
+                       : "{\"columns\": [\"site\", \"first_edge\", \"second_edge\", \"value\"], \"data\": [");
+    int first = 1;
+    if (agg) {
+        for (int i = 0; i < n; i++) {
+            const double v = U > 0 ? clean(((long double)vals[2 * i] + (long double)vals[2 * i + 1]) / q.div_site) : 0.0;
+            if (check_finite(v, "the aggregated log likelihood of a swapped tree")) goto done;
+            if (!first) jbuf_puts(out, ", ");
+            first = 0;
+            jbuf_puts(out, "["); jbuf_int(out, user[2 * i]); jbuf_puts(out, ", "); jbuf_int(out, user[2 * i + 1]); jbuf_puts(out, ", ");
+            jbuf_real(out, v); jbuf_puts(out, "]");
+        }
+    } else {
+        for (int si = 0; si < q.r_site.selection_len; si++) {
+            const int s = q.r_site.selection[si];
+            for (int i = 0; i < n; i++) {
+                const double v = clean(vals[(size_t)i * U + q.site_to_u[s]]);
+                if (check_finite(v, "a site log likelihood of a swapped tree")) goto done;
+                if (!first) jbuf_puts(out, ", ");
+                first = 0;
+                jbuf_puts(out, "["); jbuf_int(out, s); jbuf_puts(out, ", "); jbuf_int(out, user[2 * i]); jbuf_puts(out, ", ");
+                jbuf_int(out, user[2 * i + 1]); jbuf_puts(out, ", "); jbuf_real(out, v); jbuf_puts(out, "]");
+            }
+        }
+    }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(user); free(csr); free(user_to_csr); free(vals);
+    query_clear(&q);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ string API */
 static char *string_hom(int (*run)(const jval *, jbuf *), void *userdata, const char *s_in, int *retcode)
 {
@@ -1053,11 +1163,13 @@ char *arbplf_cat_posterior_string(void *userdata, const char *s_in, int *retcode
 char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_site_rate, userdata, s_in, retcode); }
 char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_rate_matrix_deriv, userdata, s_in, retcode); }
 char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_mixture_deriv, userdata, s_in, retcode); }
+char *arbplf_nni_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_nni, userdata, s_in, retcode); }
 
 /* Host-only validation (JSON grammar, model, reductions and, where a site is selected, the prepared model's values
  * against what the transition matrix kernel accepts); no GPU is touched.
  * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta", "newton_update",
- * "cat_posterior", "site_rate", "rate_matrix_deriv" or "mixture_deriv".
+ * "cat_posterior", "site_rate", "rate_matrix_deriv", "mixture_deriv" or "nni" (the model and the reductions; the swap
+ * list is checked by the query itself).
  * Returns 0 when the input would be accepted. */
 int arbplf_validate_string(const char *what, const char *s_in)
 {
@@ -1066,7 +1178,7 @@ int arbplf_validate_string(const char *what, const char *s_in)
                !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 :
                (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 :
                !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : !strcmp(what, "rate_matrix_deriv") ? 9 :
-               !strcmp(what, "mixture_deriv") ? 10 : -1;
+               !strcmp(what, "mixture_deriv") ? 10 : !strcmp(what, "nni") ? 11 : -1;
     if (kind < 0 || !s_in) return -1;
     json_doc *doc = json_doc_parse(s_in, err, sizeof err);
     if (!doc) { fprintf(stderr, "%s\n", err); return -1; }

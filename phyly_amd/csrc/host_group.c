@@ -480,6 +480,55 @@ int plk_group_mixture_sens(plk_group *g, double *prior_out, double *rate_out)
     return rc;
 }
 
+/* log likelihood of nearest-neighbour interchanges: per-site rows [swap][site] of the engines' blocks put side by side,
+ * sums added in engine order as the pair sums are.  Weak for the same reason as above. */
+extern int plk_nni_ll(plk_engine *h, int n_swaps, const int *swaps, double *site_out, double *sums_out) __attribute__((weak));
+
+typedef struct { int n; const int *swaps; double *site, *part; int want_sums; } nni_ctx;
+
+static int job_nni_ll(plk_group *g, int i, void *p)
+{
+    nni_ctx *c = p;
+    const long s0 = g->s0[i], ni = g->s0[i + 1] - s0, S = g->S;
+    if (ni == 0) return PLK_OK;                            /* an engine without sites adds nothing */
+    double *mine = NULL;
+    if (c->site && c->n > 0 && !(mine = malloc((size_t)c->n * ni * sizeof(double)))) return PLK_E_NOMEM;
+    const int rc = plk_nni_ll(g->eng[i], c->n, c->swaps, mine, c->want_sums ? c->part + (size_t)i * c->n * 2 : NULL);
+    if (!rc && mine)
+        for (int r = 0; r < c->n; r++) memcpy(c->site + (size_t)r * S + s0, mine + (size_t)r * ni, (size_t)ni * sizeof(double));
+    free(mine);
+    return rc;
+}
+
+int plk_group_nni_ll(plk_group *g, int n_swaps, const int *swaps, double *site_out, double *sums_out)
+{
+    if (!g) return PLK_E_ARG;
+    if (!plk_nni_ll) return fail(g, PLK_E_UNSUPPORTED, "plk_group: the engine has no plk_nni_ll");
+    if (!g->have_patterns) return fail(g, PLK_E_ARG, "plk_group: tree, model and patterns must be set");
+    if (n_swaps < 0) return fail(g, PLK_E_ARG, "plk_group_nni_ll: negative number of swaps");
+    nni_ctx c = {n_swaps, swaps, site_out, NULL, sums_out != NULL};
+    c.part = calloc((size_t)g->G * n_swaps * 2 + 2, sizeof(double));
+    if (!c.part) return fail(g, PLK_E_NOMEM, "plk_group: out of host memory");
+    int rc = for_each(g, job_nni_ll, &c, 1);
+    if (!rc && sums_out) {
+        for (int r = 0; r < n_swaps; r++) {
+            double *dst = sums_out + 2 * (size_t)r;
+            if (g->G == 1) { dst[0] = c.part[2 * r]; dst[1] = c.part[2 * r + 1]; continue; }   /* one engine: its sums, bit for bit */
+            long double acc = 0;
+            for (int i = 0; i < g->G; i++) {
+                if (g->s0[i + 1] == g->s0[i]) continue;
+                acc += (long double)c.part[((size_t)i * n_swaps + r) * 2];
+                acc += (long double)c.part[((size_t)i * n_swaps + r) * 2 + 1];
+            }
+            const double hi = (double)acc;
+            dst[0] = hi;
+            dst[1] = (double)(acc - (long double)hi);
+        }
+    }
+    free(c.part);
+    return rc;
+}
+
 int plk_group_hess(plk_group *g, double *hess_sums_out)
 {
     if (!g || !hess_sums_out) return PLK_E_ARG;

@@ -192,6 +192,7 @@ struct plk_engine {
     long info_pair_sums_kernel = 0, info_query_ns = 0;
     double *d_mixD = nullptr; size_t mixd_cap = 0;   /* plk_mixture_sens: its direction matrices t_e Qn P[c][e] (the query's own; d_dP is not touched) */
     long info_mixture_sens_kernel = 0;
+    long info_nni_kernel = 0;                        /* PLK_INFO_NNI_KERNEL: up pass of the last plk_nni_ll */
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
@@ -1414,6 +1415,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_up(UpArgs a)
 
 #include "plk_pairsums.h"
 #include "plk_mixsens.h"
+#include "plk_nni.h"
 
 /* padded edge-indexed matrix streams for the up/down kernels:
  * mode 0: out[j*K+i] = M[i][j] (transposed), mode 1: out[i*K+j] = M[i][j] */
@@ -1583,6 +1585,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_PAIR_SUMS_KERNEL: *out = h->info_pair_sums_kernel; return PLK_OK;
     case PLK_INFO_LAST_QUERY_NS: *out = h->info_query_ns; return PLK_OK;
     case PLK_INFO_MIXTURE_SENS_KERNEL: *out = h->info_mixture_sens_kernel; return PLK_OK;
+    case PLK_INFO_NNI_KERNEL: *out = h->info_nni_kernel; return PLK_OK;
     case PLK_INFO_UP4_PATH: *out = h->info_up4_path; return PLK_OK;
     case PLK_INFO_DOWN4_KERNEL: *out = h->info_down4_kernel; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
@@ -2568,6 +2571,17 @@ static void launch_pairsums(plk_engine *h, const UpArgs &a, const PairSumOut &o,
     hipLaunchKernelGGL(k_up_pairsums<K>, dim3(pgrid), dim3(GEN_BLOCK), 0, h->stream, a, o, (int)grid);
 }
 
+/* generic down pass (with the first group of swaps of a chunk) + the swap up pass on the chunk's grid (plk_nni.h) */
+template <int K>
+static void launch_nni(plk_engine *h, const UpArgs &a, const NniOut &o, unsigned grid, bool down)
+{
+    if (down) {
+        hipLaunchKernelGGL(k_down_store<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a);
+        hipLaunchKernelGGL((k_up_nni<K, true>), dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, o);
+    }
+    hipLaunchKernelGGL((k_up_nni<K, false>), dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, o);
+}
+
 /* ... and the mixture-gradient up pass on the same grid (plk_mixsens.h) */
 template <int K>
 static void launch_mixsens(plk_engine *h, const UpArgs &a, const MixSensOut &o, unsigned grid, unsigned pgrid)
@@ -2948,6 +2962,114 @@ struct PairSumReq {
      * prior c at c, rate c at MIX4_MAX_C + c; the generic kernel: C prior rows, then C rate rows) */
     const double *mix_D = nullptr;
 };
+/* plk_nni_ll asks the same drivers for the swap pass (plk_nni.h) instead of an edge form: deriv = marg = false, no
+ * edge-form matrices.  swaps: [n][2] validated CSR edge pairs (a, b); the up pass runs once per group of NNI_MAX_ROWS */
+struct NniReq {
+    int n = 0;
+    const int *swaps = nullptr;
+    double *site_out = nullptr;        /* null or [n][S] host */
+    std::vector<long double> acc;      /* [n] weighted site sums (filled when want_sums) */
+    bool want_sums = false;
+    /* maps of the tree, made once by plk_nni_ll for the check of the pairs and for the records of every group */
+    std::vector<int> par, in, pos;     /* upper node of every CSR edge; edge into every node (-1: root); preorder position */
+};
+
+/* parent node of every CSR edge */
+static std::vector<int> edge_parents(int N, const int *indptr)
+{
+    std::vector<int> par(indptr[N], -1);
+    for (int a = 0; a < N; a++)
+        for (int idx = indptr[a]; idx < indptr[a + 1]; idx++) par[idx] = a;
+    return par;
+}
+
+/* "" when (a, b) is a swap of the tree: a = (v -> c), b = (u -> s), v a child of u, s != v; else why it is none */
+static std::string nni_pair_fault(int N, const int *indptr, const int *indices, const std::vector<int> &par,
+                                  const std::vector<int> &in_edge, int a, int b)
+{
+    const int E = indptr[N];
+    if (a < 0 || a >= E || b < 0 || b >= E) return "edge index out of range";
+    if (a == b) return "the same edge twice";
+    const int v = par[a], u = par[b];
+    if (in_edge[v] < 0) return "the first edge starts at the root";
+    if (par[in_edge[v]] != u) return "the first edge does not start at a child of the second edge's upper node";
+    if (indices[b] == v) return "the second edge ends where the first starts";
+    return "";
+}
+
+/* edge into every node (-1 for the root) */
+static std::vector<int> in_edges(int N, const int *indptr, const int *indices)
+{
+    std::vector<int> in(N, -1);
+    for (int idx = 0; idx < indptr[N]; idx++) in[indices[idx]] = idx;
+    return in;
+}
+
+/* records of plk_nni.h for the swaps [g0, g0 + ng) of the request, sorted by the preorder position of the upper node;
+ * pair_ok: the kernel takes records of two swaps (the k = 4 kernel) */
+static std::vector<int> nni_records(const plk_engine *h, const NniReq &q, int g0, int ng, bool pair_ok)
+{
+    const int *ip = h->indptr.data();
+    const std::vector<int> &par = q.par, &in = q.in, &pos = q.pos;
+    struct Rec { int w[NNI_REC]; };
+    std::vector<Rec> recs;
+    std::vector<int> open_rec((size_t)h->E, -1);     /* per edge (u -> v): the record of two swaps still taking rows, by b */
+    for (int i = 0; i < ng; i++) {
+        const int a = q.swaps[2 * (g0 + i)], b = q.swaps[2 * (g0 + i) + 1];
+        const int v = par[a], u = par[b], idx_v = in[v];
+        const bool two = pair_ok && ip[u + 1] - ip[u] == 2 && ip[v + 1] - ip[v] == 2;
+        if (two) {
+            const int second = a == ip[v] ? 0 : 1;
+            int ri = open_rec[idx_v];
+            if (ri < 0 || recs[ri].w[4 + 2 * second] >= 0) {
+                Rec r = {{pos[u], idx_v, b, ip[v], -1, ip[v] + 1, -1, 0}};
+                ri = (int)recs.size();
+                recs.push_back(r);
+                open_rec[idx_v] = ri;
+            }
+            recs[ri].w[4 + 2 * second] = i;
+        } else {
+            Rec r = {{pos[u], idx_v, b, a, i, -1, -1, 0}};
+            recs.push_back(r);
+        }
+    }
+    std::stable_sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) { return x.w[0] < y.w[0]; });
+    std::vector<int> out;
+    out.reserve(recs.size() * NNI_REC);
+    for (const Rec &r : recs) out.insert(out.end(), r.w, r.w + NNI_REC);
+    return out;
+}
+
+/* per group of swaps: the records go to the device with the call's other integer tables */
+struct NniGroups {
+    std::vector<size_t> off;           /* offset of the group's records in the pack */
+    std::vector<int> nrec;
+    int rows = 0;                      /* rows of the plane: the largest group */
+    void put(const plk_engine *h, const NniReq &q, bool pair_ok, IntPack &pack)
+    {
+        for (int g0 = 0; g0 < q.n; g0 += NNI_MAX_ROWS) {
+            const int ng = std::min(NNI_MAX_ROWS, q.n - g0);
+            const std::vector<int> r = nni_records(h, q, g0, ng, pair_ok);
+            off.push_back(pack.put(r.data(), r.size()));
+            nrec.push_back((int)(r.size() / NNI_REC));
+            rows = std::max(rows, ng);
+        }
+    }
+};
+
+/* one chunk's outputs of one group: rows of the plane to their places in site_out, weighted row sums into acc */
+static int nni_group_out(plk_engine *h, NniReq *q, int g0, int ng, long n, long s0, const double *plane)
+{
+    int rc;
+    if (q->want_sums && (rc = wsum_rows(h, ng, n, plane, h->d_w ? h->d_w + s0 : nullptr, q->acc.data() + g0))) return rc;
+    if (q->site_out) {
+        HIPCHK(h, hipMemcpy2DAsync(q->site_out + (size_t)g0 * h->S + s0, (size_t)h->S * sizeof(double), plane, (size_t)n * sizeof(double),
+                                   (size_t)n * sizeof(double), (size_t)ng, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return PLK_OK;
+}
+
 /* workgroups of the pair-sum passes: fixed by the device, so the partial sums never grow with S */
 static unsigned pair_sums_grid(const plk_engine *h, long nbatch) { return (unsigned)std::min<long>(nbatch, 4L * h->num_cus); }
 
@@ -2966,7 +3088,7 @@ static int pair_sums_finish(plk_engine *h, PairSumReq *ps, size_t rows, unsigned
 }
 
 static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
-                       double *site_out, double *sums_out, const double *d_M, int dzero, int nM, PairSumReq *ps = nullptr)
+                       double *site_out, double *sums_out, const double *d_M, int dzero, int nM, PairSumReq *ps = nullptr, NniReq *nni = nullptr)
 {
     int rc;
     const int N = h->N, E = h->E, C = h->C;
@@ -3052,7 +3174,7 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
                                                    any_rebuild ? rebuild_tab.data() : nullptr, pair_of.data());
         if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
     }
-    if (!ps) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
+    if (!ps && !nni) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
     const size_t ntab = (size_t)C * (ntips + 1) * h->nchar * 4;
     /* all small integer tables of this call in one host block, one upload */
     IntPack pack;
@@ -3065,6 +3187,8 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     const size_t o_vis = nodes4 ? pack.put(un4.rec.data(), un4.rec.size()) : 0;
     const size_t o_pt = npairs4 ? pack.put(pair_tabs.data(), pair_tabs.size()) : 0;
     const size_t o_rb = any_rebuild ? pack.put(rebuild_tab.data(), rebuild_tab.size()) : 0;
+    NniGroups ng4;
+    if (nni) ng4.put(h, *nni, true, pack);
     const size_t nptab = (size_t)C * npairs4 * h->nchar * h->nchar * 4;
     if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, ntab * (size_t)(1 + nM) + nptab)) || (rc = pack.upload(h))) return rc;
     int *const d_psflag = pack.flag(h);
@@ -3086,7 +3210,7 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
 
     const bool msum_only = marginal_sums_only(deriv, marg, site_out, sums_out);      /* per-wave sums instead of the N x 4 planes */
-    const size_t per_site = ((size_t)(2 * (size_t)nin) * C * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? ER : 0) + (marg && !msum_only ? (size_t)N * 4 : 0)) * sizeof(double);
+    const size_t per_site = ((size_t)(2 * (size_t)nin) * C * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? ER : 0) + (marg && !msum_only ? (size_t)N * 4 : 0) + (size_t)ng4.rows) * sizeof(double);
     long chunk;
     if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0), UD4_BLOCK, false, &chunk))) return rc;
     const size_t mvs_doubles = msum_only ? (size_t)N * 4 * (size_t)((chunk + UD4_BLOCK - 1) / UD4_BLOCK) * (UD4_BLOCK / 64) : 0;   /* per-wave marginal sums */
@@ -3133,6 +3257,18 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
         else if (fused_ok && h->slots_needed <= 8) hipLaunchKernelGGL(k_down_fused4<8>, dim3(grid), dim3(UD4_BLOCK), lds_codes, h->stream, a, d_ops2, d_oe2, (int)h->ops.size(), d_obs2, nobs2, first_slot2, first_row2);
         else if (fused_ok && h->slots_needed <= 16) hipLaunchKernelGGL(k_down_fused4<16>, dim3(grid), dim3(UD4_BLOCK), lds_codes, h->stream, a, d_ops2, d_oe2, (int)h->ops.size(), d_obs2, nobs2, first_slot2, first_row2);
         else hipLaunchKernelGGL(k_down_store4, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a);
+        if (nni) {
+            /* one up pass per group of swaps over the vectors of this chunk; the first stores the forward vectors */
+            for (size_t gi = 0; gi < ng4.off.size(); gi++) {
+                NniOut no;
+                no.rec = b + ng4.off[gi]; no.nrec = ng4.nrec[gi]; no.store_fn = gi == 0 ? 1 : 0; no.plane = p;
+                hipLaunchKernelGGL(k_up4_nni, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a, no);
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_nni_ll: kernel launch failed"; return PLK_E_DEVICE; }
+                const int g0 = (int)gi * NNI_MAX_ROWS;
+                if ((rc = nni_group_out(h, nni, g0, std::min(NNI_MAX_ROWS, nni->n - g0), n, s0, p))) return rc;
+            }
+            continue;
+        }
         if (ps) {
             const long nbatch = (n + PS4_BLOCK - 1) / PS4_BLOCK;
             const unsigned pgrid = pair_sums_grid(h, nbatch);
@@ -3298,17 +3434,23 @@ static bool use_updown4(const plk_engine *h)
 /* d_M: the per-(category, edge) matrices of the edge bilinear form fe^T M L_b: dP for the derivative
  * (dzero = 1: rows sum to zero), scaled Frechet matrices for dwell / trans / em-update (dzero = 0) */
 static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
-                      double *site_out, double *sums_out, const double *d_M_in = nullptr, int dzero = 1, int nM = 1, PairSumReq *ps = nullptr)
+                      double *site_out, double *sums_out, const double *d_M_in = nullptr, int dzero = 1, int nM = 1, PairSumReq *ps = nullptr,
+                      NniReq *nni = nullptr)
 {
     if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_deriv/plk_marginal: tree, model and patterns must be set"; return PLK_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
-    if ((rc = check_stored_range(h, ps ? (ps->mix_D ? "plk_mixture_sens" : "plk_edge_pair_sums/plk_rate_matrix_sens")
+    if ((rc = check_stored_range(h, nni ? "plk_nni_ll" : ps ? (ps->mix_D ? "plk_mixture_sens" : "plk_edge_pair_sums/plk_rate_matrix_sens")
                                        : marg ? (deriv ? "plk_deriv/plk_marginal" : "plk_marginal") : d_M_in ? "plk_edge_expect" : "plk_deriv"))) return rc;
-    if (!d_M_in && !ps && (rc = ensure_dP(h))) return rc;
+    if (!d_M_in && !ps && !nni && (rc = ensure_dP(h))) return rc;
     const double *d_M = d_M_in ? d_M_in : h->d_dP;
-    if (!ps) h->info_up4_path = 0;
+    if (!ps && !nni) h->info_up4_path = 0;
+    if (nni) {
+        /* as for the pair sums: the k = 4 kernel takes compact codes and at most four categories */
+        if (use_updown4(h) && h->C <= 4) { h->info_nni_kernel = 1; return run_updown4(h, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nni); }
+        h->info_nni_kernel = 2;
+    } else
     if (ps) {
         /* the k = 4 kernel takes compact codes and at most four categories; everything else the generic kernel below */
         long &info = ps->mix_D ? h->info_mixture_sens_kernel : h->info_pair_sums_kernel;
@@ -3319,7 +3461,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     else if (use_mfma(h)) { h->info_updown_kernel = 3; return run_updown_mfma(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
     else if (use_updown4(h)) { h->info_updown_kernel = 1; return run_updown4(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero, nM); }
     if (nM != 1) { h->err = "internal: several edge forms per pass need the k = 4 kernels"; return PLK_E_ARG; }
-    if (!ps) h->info_updown_kernel = 2;
+    if (!ps && !nni) h->info_updown_kernel = 2;
     const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
     const long S = h->S;
     /* padded edge-indexed streams in the grow-only matrix buffer; each starts at a multiple of 32 doubles (256 bytes, what
@@ -3330,7 +3472,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     const int bt = K * K >= 256 ? 256 : 64;
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, h->d_P, d_PT);
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 1, h->d_P, d_PN);
-    if (!ps || ps->mix_D) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
+    if (!nni && (!ps || ps->mix_D)) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
     /* the call's integer tables; of the storage maps the generic kernels take the rescaling slots only */
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
     const PlkStorageMaps sm = storage_maps(h);
@@ -3338,13 +3480,15 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     IntPack pack;
     const size_t o_em = pack.put_opt(edge_mask, (size_t)E), o_nm = pack.put_opt(node_mask, (size_t)N);
     const size_t o_has = pack.put_has_data(h), o_ns = pack.put(sm.node_scale.data(), (size_t)N);
+    NniGroups ngg;
+    if (nni) ngg.put(h, *nni, false, pack);
     if ((rc = pack.upload(h))) return rc;
     const int *pk = h->d_u4pack;
     const int *d_emask = edge_mask ? pk + o_em : nullptr, *d_nmask = node_mask ? pk + o_nm : nullptr, *d_has = pk + o_has, *d_ns = pk + o_ns;
     int *const d_psflag = pack.flag(h);
 
     /* chunk the site axis so that the stored vectors fit */
-    const size_t per_site = ((size_t)(E + 2 * (size_t)N) * C * k + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg ? (size_t)N * k : 0)) * sizeof(double);
+    const size_t per_site = ((size_t)(E + 2 * (size_t)N) * C * k + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg ? (size_t)N * k : 0) + (size_t)ngg.rows) * sizeof(double);
     long chunk;
     if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site, GEN_BLOCK, false, &chunk))) return rc;
     const size_t ps_rows = ps ? (ps->mix_D ? (size_t)2 * C : (size_t)C * E * k * k + (size_t)C * k) : 0;
@@ -3380,6 +3524,17 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
         if (deriv) HIPCHK(h, hipMemsetAsync(a.DV, 0, (size_t)E * n * sizeof(double), h->stream));
         if (marg) HIPCHK(h, hipMemsetAsync(a.MV, 0, (size_t)N * k * n * sizeof(double), h->stream));
         const unsigned grid = (unsigned)((n + GEN_BLOCK - 1) / GEN_BLOCK);
+        if (nni) {
+            for (size_t gi = 0; gi < ngg.off.size(); gi++) {
+                NniOut no;
+                no.rec = pk + ngg.off[gi]; no.nrec = ngg.nrec[gi]; no.store_fn = gi == 0 ? 1 : 0; no.plane = p;
+                dispatch_K(K, [&](auto Kc) { launch_nni<decltype(Kc)::value>(h, a, no, grid, gi == 0); });
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_nni_ll: kernel launch failed"; return PLK_E_DEVICE; }
+                const int g0 = (int)gi * NNI_MAX_ROWS;
+                if ((rc = nni_group_out(h, nni, g0, std::min(NNI_MAX_ROWS, nni->n - g0), n, s0, p))) return rc;
+            }
+            continue;
+        }
         if (ps) {
             const unsigned pgrid = pair_sums_grid(h, (long)grid);
             if (ps->mix_D) {
@@ -3734,6 +3889,52 @@ extern "C" int plk_mixture_sens(plk_engine *h, double *prior_out, double *rate_o
         put_dd(prior_out + 2 * c, ps.acc[c]);
         put_dd(rate_out + 2 * c, ps.acc[rate_row0 + c]);
     }
+    return PLK_OK;
+}
+
+/*
+ * Log likelihood of nearest-neighbour interchanges of the current tree (plk_nni.h): one down pass per site chunk, one up
+ * pass per group of NNI_MAX_ROWS swaps.  Every pair is checked before anything is queued.
+ */
+extern "C" int plk_nni_ll(plk_engine *h, int n_swaps, const int *swaps, double *site_out, double *sums_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_nni_ll: tree, model and patterns must be set"; return PLK_E_ARG; }
+    if (n_swaps < 0) { h->err = "plk_nni_ll: negative number of swaps"; return PLK_E_ARG; }
+    const int N = h->N;
+    const int *ip = h->indptr.data(), *ix = h->indices.data();
+    std::vector<int> canon;
+    NniReq q;
+    q.par = edge_parents(N, ip); q.in = in_edges(N, ip, ix);
+    q.pos.assign((size_t)N, 0);
+    for (int u = 0; u < N; u++) q.pos[h->preorder[u]] = u;
+    if (!swaps) {
+        canon.resize((size_t)2 * std::max(1, plk_nni_swaps(N, ip, ix, nullptr)));
+        const int count = plk_nni_swaps(N, ip, ix, canon.data());
+        if (n_swaps != count) {
+            h->err = "plk_nni_ll: the canonical list has " + std::to_string(count) + " swaps, the call asks for " + std::to_string(n_swaps);
+            return PLK_E_ARG;
+        }
+        swaps = canon.data();
+    } else {
+        for (int i = 0; i < n_swaps; i++) {
+            const std::string bad = nni_pair_fault(N, ip, ix, q.par, q.in, swaps[2 * i], swaps[2 * i + 1]);
+            if (!bad.empty()) {
+                h->err = "plk_nni_ll: pair " + std::to_string(i) + " (" + std::to_string(swaps[2 * i]) + ", " + std::to_string(swaps[2 * i + 1]) +
+                         ") is no swap: " + bad;
+                return PLK_E_ARG;
+            }
+        }
+    }
+    if (n_swaps == 0) return PLK_OK;
+    QueryTimer qt(h);
+    q.n = n_swaps; q.swaps = swaps; q.site_out = site_out; q.want_sums = sums_out != nullptr;
+    q.acc.assign((size_t)n_swaps, 0.0L);
+    const int rc = run_updown(h, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, nullptr, &q);
+    if (rc) return rc;
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = std::string("plk_nni_ll: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
+    if (sums_out) put_dd_rows(sums_out, q.acc.data(), (size_t)n_swaps);
     return PLK_OK;
 }
 

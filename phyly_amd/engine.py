@@ -19,6 +19,7 @@ HOST, DEVICE = 0, 1
 ROOT_NONE, ROOT_CUSTOM, ROOT_UNIFORM, ROOT_EQUILIBRIUM = 1, 2, 3, 4
 INFO_LL_KERNEL, INFO_STACK_SLOTS, INFO_PROGRAM_OPS, INFO_LL_KERNEL_NS, INFO_LL_TOTAL_NS, INFO_LL_KERNEL_NS_SUM, INFO_LL_KERNEL_COUNT, INFO_LL_VARIANT, INFO_PAIR_TABLES, INFO_LL_EXEC_FLOPS, \
     INFO_UPDOWN_KERNEL, INFO_CAT_POSTERIOR_KERNEL, INFO_CATEGORIES, INFO_CAT_POSTERIOR_NS, INFO_PAIR_SUMS_KERNEL, INFO_QUERY_NS, INFO_MIXTURE_SENS_KERNEL, INFO_UP4_PATH, INFO_DOWN4_KERNEL, INFO_LL_FORM, INFO_LL_FOLD, INFO_LL_PAIRMUL = range(22)
+INFO_NNI_KERNEL = 22
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 COEF_PRIOR, COEF_PRIOR_RATE_EDGE, COEF_PRIOR_RATE = 0, 1, 2
 FIT_EM, FIT_LBFGS = 0, 1
@@ -42,6 +43,19 @@ def check_model_values(Qn, edge_rates, cat_rates, cat_prior, root_mode=ROOT_NONE
     rw = _f64(root_w) if root_w is not None else None
     return int(lib.plk_check_model_values(Qn.shape[0], len(cr), len(er), _ptr(Qn), _ptr(Qn_lo), _ptr(er), _ptr(cr), _ptr(cp),
                                           int(root_mode), _ptr(rw)))
+
+
+def nni_swaps(indptr, indices):
+    """plk_nni_swaps: the canonical list of nearest-neighbour interchanges of a tree in CSR form, [count][2] CSR edge
+    pairs (a, b) ordered by a, then by b (include/plk.h:plk_nni_ll); no engine, no GPU"""
+    lib = load_library()
+    indptr, indices = _i32(indptr), _i32(indices)
+    N = len(indptr) - 1
+    count = int(lib.plk_nni_swaps(N, _ptr(indptr), _ptr(indices), None))
+    pairs = np.zeros((count, 2), dtype=np.int32)
+    if count:
+        lib.plk_nni_swaps(N, _ptr(indptr), _ptr(indices), _ptr(pairs))
+    return pairs
 
 
 def load_library():
@@ -89,6 +103,8 @@ def load_library():
     lib.plk_mixture_sens.argtypes = [vp, vp, vp]
     lib.plk_mixture_chain.argtypes = [ci, ci, vp, vp, ctypes.c_double, ctypes.c_double, ci, vp, vp, vp, vp, vp, vp,
                                       ctypes.POINTER(ci), ctypes.c_char_p, ctypes.c_size_t]
+    lib.plk_nni_swaps.argtypes = [ci, vp, vp, vp]
+    lib.plk_nni_ll.argtypes = [vp, ci, vp, vp, vp]
     lib.plk_get_transition_matrices.argtypes = [vp, vp]
     lib.plk_get_info.argtypes = [vp, ci, ctypes.POINTER(cl)]
     lib.plk_set_option.argtypes = [vp, ci, cl]
@@ -131,6 +147,7 @@ class Engine:
             raise EngineError(self._lib.plk_create_error().decode())
         self.N = self.E = self.k = self.C = 0
         self.S = 0
+        self._csr = None              # (indptr, indices) of the tree the engine accepted last
 
     def close(self):
         if getattr(self, "_h", None):
@@ -154,6 +171,7 @@ class Engine:
         self.N = len(preorder)
         self.E = self.N - 1
         self._check(self._lib.plk_set_tree(self._h, self.N, _ptr(indptr), _ptr(indices), _ptr(preorder)))
+        self._csr = (indptr.copy(), indices.copy())
 
     def set_model(self, Qn, edge_rates_csr, cat_rates, cat_prior, root_mode, root_w=None, Qn_lo=None):
         Qn = _f64(Qn)
@@ -327,6 +345,24 @@ class Engine:
         rate = np.zeros((self.C, 2))
         self._check(self._lib.plk_mixture_sens(self._h, _ptr(prior), _ptr(rate)))
         return prior, rate
+
+    def nni_ll(self, swaps=None, per_site=True, want_sums=True):
+        """log likelihood of nearest-neighbour interchanges of the tree (include/plk.h:plk_nni_ll); swaps: [n][2] CSR
+        edge pairs (a, b), None = the canonical list (nni_swaps) -> (ll' [n][S] or None, sums [n][2] or None)"""
+        if swaps is None:
+            if self._csr is None:
+                err = EngineError("plk_nni_ll: tree, model and patterns must be set")
+                err.code = E_ARG
+                raise err
+            n = len(nni_swaps(*self._csr))
+            sw = None
+        else:
+            sw = _i32(swaps).reshape(-1, 2)
+            n = sw.shape[0]
+        out = np.zeros((n, self.S)) if per_site else None
+        sums = np.zeros((n, 2)) if want_sums else None
+        self._check(self._lib.plk_nni_ll(self._h, n, _ptr(sw), _ptr(out), _ptr(sums)))
+        return out, sums
 
     def transition_matrices(self):
         P = np.empty((self.C, self.E, self.k, self.k))
