@@ -21,6 +21,7 @@ import pytest
 
 from helpers import (IRREGULAR_CHERRY, IRREGULAR_EDGES, IRREGULAR_RATES, K4_MODELS, cherry_with_unequal_edges, deep_workload, family_workload,
                      k4_workload, oracle_model, rel_err, tree_workload)
+from second_order_cases import edge_scale, scaled_err
 from test_gpu_kernel_families import MFMA, PROB_ULP, SUM_TOL, TOL, VEC, _row_err, _wsum
 
 gpu = pytest.mark.gpu                # every test but the one on the tables of expected paths, which needs no GPU
@@ -48,6 +49,7 @@ XS = 65                              # edge expectations
 # sites to 1e-14 of the largest entry: three decades inside the 1e-11 bar, which stays
 HESS_SIZES = {"irregular": (65, 257), "balanced32": (65, 257), "balanced64": (5, 65)}
 HESS_LONG_DOUBLE = {("balanced64", 65)}
+HESS_SCALED = ("irregular", "balanced32")      # also held entry by entry at the scale d_i d_j of second_order_cases.edge_scale
 
 
 def _pt(model):
@@ -161,7 +163,7 @@ class _Ref:
             F = oracle.frechet(self.m, self.w, self.Ls[d], 1.0, False, self.xmask, precise=2)
             for coef in ((0, 1) if d == 0 else (1,)):
                 self.expect[d, coef] = oracle.site_edge_expect(self.m, self.w, B, F, coef, self.xmask, precise=2)
-        self.hess = {}
+        self.hess, self.hscale = {}, {}
         self.hdata, self.hderiv = {}, {}
         for S in HESS_SIZES.get(model, ()):
             src = S if S in self.deriv else 65
@@ -174,6 +176,7 @@ class _Ref:
             elif S == 5:
                 site_hess_5 = H
             self.hess[S] = (H.astype(np.longdouble) * wts[:, None, None].astype(np.longdouble)).sum(axis=0).astype(float)
+            self.hscale[S] = edge_scale(H, self.hderiv[S], wts)            # each edge's own curvature, for the scaled bar
 
 
 _REFS = {}
@@ -388,6 +391,9 @@ def test_second_order(eng, ref, model, force_generic):
             for got in (H1, H2):
                 assert np.allclose(got, got.T, rtol=0, atol=0), S
                 assert np.max(np.abs(got - want)) <= 1e-11 * np.max(np.abs(want)), S
+                if model in HESS_SCALED:
+                    assert np.all(ref.hscale[S] > 0), S
+                    assert scaled_err(got, want, ref.hscale[S]) <= 1e-11, (S, scaled_err(got, want, ref.hscale[S]))
             gwant = _wsum(ref.hderiv[S], wts).astype(float)
             scale = np.max(np.abs(ref.hderiv[S]), axis=1)
             assert np.max(np.abs(grad - gwant)) <= TOL * np.sum(np.abs(wts) * scale), S       # the per-site tolerance, summed

@@ -188,27 +188,7 @@ def _fn(name):
     return getattr(arbplf, "arbplf_" + name)
 
 
-def _check_commands(oracle, x):
-    """-> True when the case counted"""
-    kappa, E, want = cases.expected(oracle, x)
-    s = json.dumps(x)
-    counts = cases.counts(kappa, E, want)
-    for name in COMMANDS:
-        try:
-            got = _table(_fn(name)(s))
-        except RuntimeError:
-            assert not counts, "%s refused a well-conditioned input (kappa %.3g, E %d)" % (name, kappa, E)
-            continue
-        vals = np.array([r[-1] for r in got["data"]])
-        assert np.all(np.isfinite(vals))
-        assert got["columns"] == (["first_edge", "second_edge", "value"] if name == "inv_hess" else ["edge", "value"])
-        assert len(vals) == (E * E if name == "inv_hess" else E)
-        if counts:
-            ref = (want["newton_delta"] if name == "newton_update" else want[name]).astype(float)
-            scale = np.max(np.abs(ref))             # the update is rates + delta: its error is the delta's
-            err = np.max(np.abs(vals - want[name].astype(float)))
-            assert err <= 2 * kappa * E * 1e-11 * scale + 1e-300, (name, err, kappa, E, scale)
-    return counts
+_check_commands = cases.check_commands       # shared with test_gpu_second_order_families.py
 
 
 @pytest.mark.parametrize("d", ["with.full.data", "with.leaf.data"])
