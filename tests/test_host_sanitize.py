@@ -30,8 +30,10 @@ def binary(tmp_path_factory):
 
 def _files(kind):
     pats = {"ll": ["*/in.json", "*/ll/in*.json"], "deriv": ["*/deriv/in.json", "JC.long.branch/*.json"],
-            "marginal": ["*/marginal/in.json"], "dwell": ["*/dwell/*/in.json", "BEAST.MarkovJumps/MarkovRewardsC/in.json"],
-            "trans": ["*/trans/*/in*.json", "BEAST.MarkovJumps/MarkovJumpsC/in*.json", "BEAST.MarkovJumps/MarkovMarginalRate/in*.json"],
+            "marginal": ["*/marginal/in.json"], "dwell": ["*/dwell/*/in.json", "BEAST.MarkovJumps/MarkovRewardsC/in.json",
+                                                 "JC.long.branch/dwell/in.json"],
+            "trans": ["*/trans/*/in*.json", "BEAST.MarkovJumps/MarkovJumpsC/in*.json", "BEAST.MarkovJumps/MarkovMarginalRate/in*.json",
+                      "JC.long.branch/trans/in.json"],
             "em_update": ["*/em-update/*/in.json"], "hess": ["*/hess/*/in.json"]}[kind]
     out = []
     for p in pats:
@@ -53,20 +55,22 @@ def test_host_layer_under_sanitizers(binary, kind):
         assert int(last[3]) == len(files), "every golden input must validate: " + out[-300:]
 
 
-@pytest.mark.parametrize("kind,seed", [("ll", 11), ("deriv", 22), ("marginal", 33)])
+@pytest.mark.parametrize("kind,seed", [("ll", 11), ("deriv", 22), ("marginal", 33), ("dwell", 44), ("trans", 55), ("em_update", 66)])
 def test_random_queries_under_sanitizers(binary, tmp_path, kind, seed):
     """the seeded random queries of tests/test_gpu_differential.py (multifurcating trees, duplicate selections,
-    weighted aggregations, both observation forms) through the drivers with the stand-in engine"""
+    weighted aggregations, both observation forms) and, for the expectation queries, of tests/expect_cases.py (state
+    and pair selections: listed, aggregated, duplicated, diagonal) through the drivers with the stand-in engine"""
     import json
     import random
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from expect_cases import feasible_query
     from test_gpu_differential import random_model
     rng = random.Random(seed)
     files = []
     for i in range(30):
         f = tmp_path / ("q%03d.json" % i)
-        f.write_text(json.dumps(random_model(rng, kind)))
+        f.write_text(json.dumps(random_model(rng, kind) if kind in ("ll", "deriv", "marginal") else feasible_query(rng, kind)[0]))
         files.append(str(f))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                FAKE_ENGINE="1")

@@ -143,10 +143,10 @@ def _pairs(kind_dirs):
 
 
 DWELL = _pairs(["Felsenstein.2004.fig.16.4/dwell/adenine", "Felsenstein.2004.fig.16.4/dwell/pyrimidines",
-                "BEAST.MarkovJumps/MarkovRewardsC"])
+                "BEAST.MarkovJumps/MarkovRewardsC", "JC.long.branch/dwell"])
 TRANS = _pairs(["Felsenstein.2004.fig.16.4/trans/A.to.C.only", "Felsenstein.2004.fig.16.4/trans/all.types",
                 "Felsenstein.2004.fig.16.4/trans/transversions.only", "BEAST.MarkovJumps/MarkovJumpsC",
-                "BEAST.MarkovJumps/MarkovMarginalRate"])
+                "BEAST.MarkovJumps/MarkovMarginalRate", "JC.long.branch/trans"])
 EM = _pairs(["Felsenstein.2004.fig.16.4/em-update/with.full.data", "Felsenstein.2004.fig.16.4/em-update/with.leaf.data",
              "Felsenstein.2004.fig.16.4/em-update/with.no.data"])
 
