@@ -453,8 +453,15 @@ enum {
                                        observation ops of one category with ADVANCE_0 / ADVANCE_1 folded in (saturating).  Under
                                        the pair-product form (PLK_INFO_LL_PAIRMUL) bits 0 and 4-30 describe the folded stream it was
                                        derived next to: a PAIR op with an ADVANCE counts as the observation op that carried it */
-    PLK_INFO_NNI_KERNEL = 22        /* up pass of the last plk_nni_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
+    PLK_INFO_NNI_KERNEL = 22,       /* up pass of the last plk_nni_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
                                        4 categories), 2 = generic */
+    PLK_INFO_LL_TRIPLE = 23         /* three-leaf tables in the last ll evaluation's streamed kernel: 0 = the form did not run (another
+                                       kernel, no node that qualifies, too few sites for the default, PLK_OPT_PAIR_TABLES + 2048, or
+                                       formats that did not replay), else bit 0 = it ran, bits 4-7 = groups the categories ran in
+                                       (phases of the one launch), bits 8-23 = nodes of a category that are look-ups of a
+                                       three-leaf table (a cherry, a leaf and the edge above their parent in one row).
+                                       PLK_INFO_PAIR_TABLES then counts the cherries that still have a table of their own, and
+                                       PLK_INFO_LL_EXEC_FLOPS the stream that ran */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -497,7 +504,14 @@ enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PE
                                + 512: without the pair products of trees within 3 stack slots (k_ll_fused4_v4s<768, true, true>: a second
                                look-up buffer in the registers of slot 3, two table rows multiplied under one dispatch):
                                the folded stream with held chunks on k_ll_fused4_v4s, the default before that form
-                               (measurements; + 64 / + 128 / + 256 imply it) */,
+                               (measurements; + 64 / + 128 / + 256 imply it);
+                               + 1024: the three-leaf form of the streamed kernel wherever it applies (a node that is not the
+                               root and whose children are a cherry and a leaf becomes, with the edge above it, one look-up
+                               of a table of nchar^3 rows, nchar^3 <= 256; to make room the categories may run in groups,
+                               the tables of one group resident at a time, in phases of the one launch); the default takes
+                               it only where every wave walks enough units per phase to pay for the phases (DESIGN.md
+                               section 4); + 2048: never; + 4096 / + 8192 / both: the categories in one group / one group
+                               per category / two groups instead of the cost model's choice (measurements) */,
        PLK_OPT_VEC_REG_STACK = 7 /* 1 (default): the vector kernels (9 <= k <= 20) keep the three busiest stack slots in
                                registers (2 waves per SIMD); 0: every waiting vector goes through HBM slots (round 2) */,
        PLK_OPT_MFMA_NS2 = 8 /* 1: the matrix-core ll kernel for 33 <= k <= 64 gives a wave two groups of 16 sites (every staged

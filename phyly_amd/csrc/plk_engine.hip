@@ -68,6 +68,8 @@ struct LlPlan {
     long info_fold = 0;                  /* PLK_INFO_LL_FOLD */
     bool pairmul = false;                /* streamed form: the pair-product stream is the one uploaded, k_ll_fused4_v4s<768, true, true> runs it */
     long info_pairmul = 0;               /* PLK_INFO_LL_PAIRMUL */
+    PlkV4TPlan triple;                   /* streamed form: three-leaf tables and category groups (nodes == 0: the form does not run) */
+    long info_triple = 0;                /* PLK_INFO_LL_TRIPLE */
 };
 
 struct plk_engine {
@@ -140,7 +142,13 @@ struct plk_engine {
     PlkFusedV4P fv4p;                    /* ... and the pair-product stream of trees within 3 slots (k_ll_fused4_v4s<768, true, true>) */
     unsigned *d_cstream = nullptr; size_t cstream_cap = 0;   /* the code stream (plk_stream_dword), built by upload_formats */
     int *d_obs_row = nullptr;            /* staged row per observation of the program */
-    int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [2][rows] staged-row nodes; [4][ntab] unit, edge, leaf edges of a pair */
+    int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [3][rows] staged-row nodes (third: the leaf of a three-leaf row); [6][ntab] unit, edge,
+                                                        leaf edges of a pair, edge above the cherry and leaf edge of a three-leaf table;
+                                                        the three-leaf tables are the last fpt.ntriples of the list */
+    PlkFusedPT fpt_t;                    /* three-leaf form: the rewritten formats while they are derived and checked (then moved to fpt) */
+    PlkFusedV4S fv4s_t;
+    double *d_llstate = nullptr; size_t llstate_cap = 0;   /* category groups: per site the partial mixture sum, then the exponents */
+    bool k4_groups_ok = false;           /* k_ll_fused4_v4s<768, true, true, true> can be described and has the static LDS of <768, false> */
     int num_cus = 256;
     int2 *d_ops = nullptr;
     int4 *d_fops = nullptr;              /* fused-kernel program (C++ interpreter) */
@@ -196,7 +204,7 @@ struct plk_engine {
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
-    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_pairmul = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
+    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_pairmul = 0, info_ll_triple = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
 static std::string g_create_error;
@@ -666,6 +674,35 @@ __global__ void k_build_tip(int E, int ntips, int nchar, const int *__restrict__
  *   pair    out[cb*nchar+cc][i]  = (P_a (P_b defs[cb] o P_c defs[cc]))_i    (src/evaluate_site_lhood.c:36-56 for a cherry)
  *   pseudo  out[code][i]         = defs[code][i]
  * A constant vector maps to itself exactly under a stochastic matrix, as the reference's shortcut does (src/util.c:276-283). */
+/* P_e defs[code] in double-double (a constant definition row maps to itself) */
+__device__ __forceinline__ void pt_leaf_dd(const dd *Pm, const double *d, dd (&v)[4])
+{
+    if (d[0] == d[1] && d[0] == d[2] && d[0] == d[3]) { for (int i = 0; i < 4; i++) v[i] = dd_make(d[0], 0.0); return; }
+    for (int i = 0; i < 4; i++) {
+        dd acc = dd_make(0.0, 0.0);
+        for (int j = 0; j < 4; j++) acc = dd_add(acc, dd_mul_d(Pm[i * 4 + j], d[j]));
+        v[i] = acc;
+    }
+}
+
+/* the rounded row of a cherry's pair table: (P_a (P_b db o P_c dc))_i, the one definition for k_build_tables_pt and k_build_tables_t */
+__device__ __forceinline__ void pt_pair_row(const dd *Pa, const dd *Pb, const dd *Pc, const double *db, const double *dc, double *out)
+{
+    dd vb[4], vc[4], pr[4];
+    pt_leaf_dd(Pb, db, vb);
+    pt_leaf_dd(Pc, dc, vc);
+    bool cst = true;
+    for (int j = 0; j < 4; j++) { pr[j] = dd_mul(vb[j], vc[j]); cst = cst && pr[j].hi == pr[0].hi && pr[j].lo == pr[0].lo; }
+    for (int i = 0; i < 4; i++) {
+        dd acc = pr[0];
+        if (!cst) {
+            acc = dd_make(0.0, 0.0);
+            for (int j = 0; j < 4; j++) acc = dd_add(acc, dd_mul(Pa[i * 4 + j], pr[j]));
+        }
+        out[i] = acc.hi;
+    }
+}
+
 __global__ void k_build_tables_pt(int E, int ntab, int units, int nchar, const int *__restrict__ tab,
                                   const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
                                   double *__restrict__ tip)
@@ -673,21 +710,13 @@ __global__ void k_build_tables_pt(int E, int ntab, int units, int nchar, const i
     const int t = blockIdx.x, c = blockIdx.y;
     const int unit = tab[t], e = tab[ntab + t], eb = tab[2 * ntab + t], ec = tab[3 * ntab + t];
     double *out = tip + ((size_t)c * units + unit) * nchar * 4;
-    auto leaf = [&](const dd *Pm, const double *d, dd (&v)[4]) {
-        if (d[0] == d[1] && d[0] == d[2] && d[0] == d[3]) { for (int i = 0; i < 4; i++) v[i] = dd_make(d[0], 0.0); return; }
-        for (int i = 0; i < 4; i++) {
-            dd acc = dd_make(0.0, 0.0);
-            for (int j = 0; j < 4; j++) acc = dd_add(acc, dd_mul_d(Pm[i * 4 + j], d[j]));
-            v[i] = acc;
-        }
-    };
     if (eb < 0) {
         const dd *Pm = Pdd + ((size_t)c * E + (e < 0 ? 0 : e)) * 16;
         for (int code = threadIdx.x; code < nchar; code += blockDim.x) {
             const double *d = defs + code * 4;
             dd v[4];
             if (e < 0) { for (int i = 0; i < 4; i++) out[code * 4 + i] = d[i]; continue; }
-            leaf(Pm, d, v);
+            pt_leaf_dd(Pm, d, v);
             for (int i = 0; i < 4; i++) out[code * 4 + i] = v[i].hi;
         }
         return;
@@ -695,19 +724,35 @@ __global__ void k_build_tables_pt(int E, int ntab, int units, int nchar, const i
     const dd *Pa = Pdd + ((size_t)c * E + e) * 16, *Pb = Pdd + ((size_t)c * E + eb) * 16, *Pc = Pdd + ((size_t)c * E + ec) * 16;
     for (int comb = threadIdx.x; comb < nchar * nchar; comb += blockDim.x) {
         const int cb = comb / nchar, cc = comb - cb * nchar;
-        dd vb[4], vc[4], pr[4];
-        leaf(Pb, defs + cb * 4, vb);
-        leaf(Pc, defs + cc * 4, vc);
-        bool cst = true;
-        for (int j = 0; j < 4; j++) { pr[j] = dd_mul(vb[j], vc[j]); cst = cst && pr[j].hi == pr[0].hi && pr[j].lo == pr[0].lo; }
-        for (int i = 0; i < 4; i++) {
-            dd acc = pr[0];
-            if (!cst) {
-                acc = dd_make(0.0, 0.0);
-                for (int j = 0; j < 4; j++) acc = dd_add(acc, dd_mul(Pa[i * 4 + j], pr[j]));
-            }
-            out[comb * 4 + i] = acc.hi;
-        }
+        pt_pair_row(Pa, Pb, Pc, defs + cb * 4, defs + cc * 4, out + comb * 4);
+    }
+}
+
+/* Three-leaf tables of the streamed form (plk_fused_v4t_build), one block per (table, category): tab[6][ntab] as for
+ * k_build_tables_pt, then the edge above the cherry and the leaf edge; the tables built here are first .. first + gridDim.x - 1
+ * of the list.  A row is the MATVEC handler's fp64 sequence (plk_v4t_row) on what the interpreter would have looked up and
+ * loaded: the rounded row of the cherry's pair table and the rounded row of the leaf's table (pt_pair_row, pt_leaf_dd: the
+ * functions k_build_tables_pt writes them with), and the rounded matrix of the edge above the node as K1 writes it to the matrix stream.
+ *   out[(cb*nchar+cc)*nchar+cl][i] = (P_d (pair[cb*nchar+cc] o tip[cl]))_i */
+__global__ void k_build_tables_t(int E, int ntab, int first, int units, int nchar, const int *__restrict__ tab,
+                                 const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
+                                 double *__restrict__ tip)
+{
+    const int t = first + blockIdx.x, c = blockIdx.y;
+    const int unit = tab[t], e = tab[ntab + t], eb = tab[2 * ntab + t], ec = tab[3 * ntab + t], ea = tab[4 * ntab + t], el = tab[5 * ntab + t];
+    double *out = tip + ((size_t)c * units + unit) * nchar * 4;
+    const dd *Pd = Pdd + ((size_t)c * E + e) * 16, *Pa = Pdd + ((size_t)c * E + ea) * 16, *Pb = Pdd + ((size_t)c * E + eb) * 16,
+             *Pc = Pdd + ((size_t)c * E + ec) * 16, *Pl = Pdd + ((size_t)c * E + el) * 16;
+    double M[16];
+    for (int idx = 0; idx < 16; idx++) M[idx] = Pd[(idx & 3) * 4 + (idx >> 2)].hi;     /* the stream's layout: M[4 j + i] = P[i][j] (Pdd is clamped at 0) */
+    for (int comb = threadIdx.x; comb < nchar * nchar * nchar; comb += blockDim.x) {
+        const int cl = comb % nchar, cbc = comb / nchar, cb = cbc / nchar, cc = cbc - cb * nchar;
+        dd vl[4];
+        double pair[4], tipv[4];
+        pt_pair_row(Pa, Pb, Pc, defs + cb * 4, defs + cc * 4, pair);
+        pt_leaf_dd(Pl, defs + cl * 4, vl);
+        for (int i = 0; i < 4; i++) tipv[i] = vl[i].hi;
+        plk_v4t_row(M, pair, tipv, out + (size_t)comb * 4);
     }
 }
 
@@ -1510,7 +1555,7 @@ extern "C" void plk_destroy(plk_engine *h)
     void *ptrs[] = {h->d_indptr, h->d_indices, h->d_preorder, h->d_Qn, h->d_edge_rates, h->d_cat_rates,
                     h->d_cat_prior, h->d_root_w, h->d_Pdd, h->d_P, h->d_dP, h->d_scratch, h->d_codes,
                     h->d_defs, h->d_B, h->d_w, h->d_ops, h->d_fops, h->d_words, h->d_mat_edge, h->d_edge_slot, h->d_op_edge, h->d_tip_edge, h->d_obs_nodes,
-                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
+                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_llstate, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
                     h->d_cp_fops, h->d_cp_ops, h->d_cp_mat_edge, h->d_cp_tip_edge, h->d_cp_obs_nodes, h->d_cp_op_edge, h->d_cp_expo, h->d_cp_flag,
                     h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial, h->d_mixD};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1592,6 +1637,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LL_FORM: *out = h->info_ll_form; return PLK_OK;
     case PLK_INFO_LL_FOLD: *out = h->info_ll_fold; return PLK_OK;
     case PLK_INFO_LL_PAIRMUL: *out = h->info_ll_pairmul; return PLK_OK;
+    case PLK_INFO_LL_TRIPLE: *out = h->info_ll_triple; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && h->plan.pair_tables ? h->plan.npairs : 0; return PLK_OK;
     case PLK_INFO_STACK_SLOTS: *out = h->slots_needed; return PLK_OK;
@@ -1709,9 +1755,12 @@ static int run_expm(plk_engine *h, bool post = false, bool need_dP = true)
                        h->d_scratch, use_lds, (const double *)nullptr, 0L, 0, (const int *)nullptr, (double *)nullptr, ep);
     HIPCHK(h, hipGetLastError());
     if (post && pt) {
-        const int ntab = (int)h->fpt.tab_unit.size();
-        hipLaunchKernelGGL(k_build_tables_pt, dim3(ntab, C), dim3(64), 0, h->stream,
+        const int ntab = (int)h->fpt.tab_unit.size(), ntri = h->fpt.ntriples;
+        hipLaunchKernelGGL(k_build_tables_pt, dim3(ntab - ntri, C), dim3(64), 0, h->stream,
                            E, ntab, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
+        if (ntri > 0)
+            hipLaunchKernelGGL(k_build_tables_t, dim3(ntri, C), dim3(64), 0, h->stream,
+                               E, ntab, ntab - ntri, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
         HIPCHK(h, hipGetLastError());
     }
     h->model_dirty = false;
@@ -1967,19 +2016,30 @@ static int vec_reg_window(const plk_engine *h)
     return lo_best;
 }
 
-/* the pair-table formats both the k = 4 and the vector kernels read: [2][rows] staged-row nodes; [4][ntab] unit, edge,
- * leaf edges of a pair */
+/* the pair-table formats both the k = 4 and the vector kernels read: [3][rows] staged-row nodes; [6][ntab] unit, edge,
+ * leaf edges of a pair, edge above the cherry and leaf edge of a three-leaf table (-1 where a row or a table has none).
+ * The list names every table's first unit, so its order is free: the three-leaf tables come last, which lets
+ * k_build_tables_pt build the others and k_build_tables_t these from one list. */
 static int upload_pair_table_lists(plk_engine *h)
 {
     const PlkFusedPT &f = h->fpt;
     int rc;
-    std::vector<int> rn(f.row_node);
-    rn.insert(rn.end(), f.row_node2.begin(), f.row_node2.end());
+    const size_t nrows = f.row_node.size(), ntab = f.tab_unit.size();
+    std::vector<int> rn(3 * nrows, -1);
+    for (size_t r = 0; r < nrows; r++) {
+        rn[r] = f.row_node[r]; rn[nrows + r] = f.row_node2[r];
+        if (r < f.row_node3.size()) rn[2 * nrows + r] = f.row_node3[r];
+    }
     if ((rc = dev_upload(h, &h->d_row_nodes, rn.data(), rn.size()))) return rc;
-    std::vector<int> tabs(f.tab_unit);
-    tabs.insert(tabs.end(), f.tab_edge.begin(), f.tab_edge.end());
-    tabs.insert(tabs.end(), f.tab_eb.begin(), f.tab_eb.end());
-    tabs.insert(tabs.end(), f.tab_ec.begin(), f.tab_ec.end());
+    std::vector<size_t> order;
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t t = 0; t < ntab; t++) if ((t < f.tab_el.size() && f.tab_el[t] >= 0) == (pass == 1)) order.push_back(t);
+    std::vector<int> tabs(6 * ntab, -1);
+    for (size_t q = 0; q < ntab; q++) {
+        const size_t t = order[q];
+        tabs[q] = f.tab_unit[t]; tabs[ntab + q] = f.tab_edge[t]; tabs[2 * ntab + q] = f.tab_eb[t]; tabs[3 * ntab + q] = f.tab_ec[t];
+        if (t < f.tab_el.size()) { tabs[4 * ntab + q] = f.tab_ea[t]; tabs[5 * ntab + q] = f.tab_el[t]; }
+    }
     return dev_upload(h, &h->d_tabs, tabs.data(), tabs.size());
 }
 
@@ -2002,6 +2062,8 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
         else h->k4_held_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
         if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true, true>) != hipSuccess) (void)hipGetLastError();
         else h->k4_pair_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
+        if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true, true, true>) != hipSuccess) (void)hipGetLastError();
+        else h->k4_groups_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
         h->k4_static_lds_known = true;
     }
     PlkK4Shape sh = {h->nchar, h->C, h->S, h->num_cus, h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
@@ -2023,6 +2085,51 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     p.info_variant = c.variant == PLK_K4_CPP ? 3 : c.variant == PLK_K4_ASM ? 1 : c.variant == PLK_K4_ASM_PT ? 5 : 6;
     p.info_form = c.variant == PLK_K4_V4S ? 1 : 0;
     p.fold = false; p.held = c.variant == PLK_K4_V4S && c.held && h->k4_held_ok; p.info_fold = p.held ? 2 : 0;
+    p.triple = PlkV4TPlan(); p.info_triple = 0;
+    if (c.variant == PLK_K4_V4S && c.bad.empty()) {
+        /* three-leaf tables, and the categories in groups to make room for them: derived from the checked pair-table formats
+         * and replayed against them; formats that do not replay are not run -- the checked ones are, and the error text says why.
+         * More than one group needs the pair-product instantiation (the only one compiled with phases). */
+        const PlkPairTablesOpt po = plk_pair_tables_opt(h->opt_pair_tables);
+        const bool can_group = c.pair && c.fold && p.held && h->k4_pair_ok && h->k4_groups_ok;
+        /* the plan is plk_k4_choose's; the engine only takes the groups back where the instantiation with phases cannot be described */
+        PlkV4TPlan tp = c.triple;
+        if (tp.groups > 1 && !can_group) tp = plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1);
+        if (tp.nodes > 0 && tp.groups > 1 &&
+            dev_reserve(h, &h->d_llstate, &h->llstate_cap, (size_t)nunits * PLK_V4S_UNIT * 3 / 2) != PLK_OK) {
+            /* no room for the partial sums: one group */
+            h->err.clear();
+            (void)hipGetLastError();
+            tp = plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1);
+        }
+        for (int attempt = 0; attempt < 2 && tp.nodes > 0; attempt++) {
+            plk_fused_v4t_build(h->fpt, h->pg.slots_needed, h->nchar, tp.extra_bytes, true, h->fpt_t);
+            std::string bad = plk_fused_check_v4t(h->N, h->indptr.data(), h->indices.data(), h->fpt, h->fpt_t, h->nchar);
+            const size_t lds = plk_fused_v4s_lds_bytes(h->fpt_t, h->nchar, tp.Cg);
+            if (bad.empty() && h->fpt_t.ntriples != tp.nodes) bad = "v4t program: the builder took another number of nodes than the plan";
+            if (bad.empty()) {
+                plk_fused_v4s_words(h->fpt_t, h->nchar, h->C, c.tip_base, h->fv4s_t, tp.Cg);
+                bad = plk_fused_check_v4s(h->fpt_t, h->fv4s_t, h->nchar, h->C, c.tip_base, lds);
+            }
+            /* fewer observations: the stream fits the room reserved for the checked one */
+            if (bad.empty() && h->fv4s_t.chunks > h->fv4s.chunks) bad = "v4t program: more chunks than the checked stream";
+            if (bad.empty() && tp.groups > 1) {
+                /* the phases exist in the pair-product instantiation only: a rewritten stream that form does not take runs in one group */
+                plk_fused_v4p_build(h->fv4s_t, h->fv4p);
+                if (h->fv4p.words.empty() || !plk_fused_check_v4p(h->fv4s_t, h->fv4p).empty()) {
+                    tp = plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1);
+                    continue;
+                }
+            }
+            if (bad.empty()) {
+                h->fpt = std::move(h->fpt_t); h->fv4s = std::move(h->fv4s_t);
+                p.k4.lds = lds; p.lds = lds;
+                p.triple = tp;
+                p.info_triple = 1 | (long)std::min(tp.groups, 15) << 4 | (long)std::min(tp.nodes, 65535) << 8;
+            } else h->err = "internal: " + bad + " (the stream without three-leaf tables runs)";
+            break;
+        }
+    }
     if (c.variant == PLK_K4_V4S && c.fold) {
         /* the folded stream is derived from the checked one and replayed against it; a fold that does not replay is not
          * run: the checked stream is, and the engine's error text says why */
@@ -2355,7 +2462,14 @@ static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool 
             sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
             sa.sync = c.sync;
             sa.first_y1 = p.pairmul ? h->fv4p.first_y1[0] : 0u; sa.first_b1 = p.pairmul ? h->fv4p.first_b1 : 0u;
-            if (p.pairmul) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            sa.groups = p.triple.groups; sa.cg = p.triple.Cg > 0 ? p.triple.Cg : h->C;
+            sa.part_sum = h->d_llstate;
+            sa.part_exp = h->d_llstate ? reinterpret_cast<int *>(h->d_llstate + (size_t)((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT) * PLK_V4S_UNIT) : nullptr;
+            if (sa.groups > 1) {
+                /* phases: only with the plan's checks behind it (pair products, room for the partial sums of every unit) */
+                if (!p.pairmul || !h->d_llstate || h->llstate_cap < (size_t)((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT) * PLK_V4S_UNIT * 3 / 2) { h->err = "internal: category groups without their plan"; return PLK_E_ARG; }
+                hipLaunchKernelGGL((k_ll_fused4_v4s<768, true, true, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            } else if (p.pairmul) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
             else if (p.held) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
             else hipLaunchKernelGGL((k_ll_fused4_v4s<768, false>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
         } else if (c.variant == PLK_K4_V4) {
@@ -2491,7 +2605,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     default: rc = launch_ll_generic(h, p, d_out, want_sum, &npartials); break;
     }
     if (rc) return rc;
-    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_pairmul = p.info_pairmul; h->info_ll_exec_flops = p.info_exec_flops;
+    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_pairmul = p.info_pairmul; h->info_ll_triple = p.info_triple; h->info_ll_exec_flops = p.info_exec_flops;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->evk[evi][1], h->stream));
     h->evk_pending[evi] = true;

@@ -47,11 +47,15 @@ struct FusedV4SArgs {
     unsigned first_y;           /* LDS offset / 32 of the first observation's table in category 0 */
     int sync;                   /* workgroup barrier: 1 before every unit, 2 before every category, 0 none */
     unsigned first_y1, first_b1; /* pair products: table of the second observation in category 0, bit offset of its code */
+    int groups, cg;             /* GROUPS instantiation: phases of the launch, categories per phase (category c reads image c % cg) */
+    double *part_sum;           /* GROUPS: per site, the mixture sum after the phases so far (padded to whole units) ... */
+    int *part_exp;              /* ... and its exponent; PLK_V4S_NO_TERM: no term yet */
 };
+#define PLK_V4S_NO_TERM INT_MIN
 
 /* stream[unit][chunk][lane][half]: one thread per dword; sites past S carry code 0 (the code rows are zero padded) */
 __global__ __launch_bounds__(256) void k_build_code_stream(const uint8_t *__restrict__ codes, long Spad, long nunits,
-                                                           const int *__restrict__ obs_row, int nobs, const int *__restrict__ row_nodes,
+                                                           const int *__restrict__ obs_row, int nobs, const int *__restrict__ row_nodes /* [3][nrows] */,
                                                            int nrows, int nchar, int chunks, unsigned *__restrict__ out)
 {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)nunits * chunks * PLK_V4S_UNIT;
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256) void k_build_code_stream(const uint8_t *__rest
     const int chunk = (int)(uc - unit * (size_t)chunks);
     const size_t site = unit * PLK_V4S_UNIT + (size_t)half * 64 + lane;
     out[plk_stream_dword(unit, chunk, lane, half, chunks)] =
-        site < (size_t)Spad ? plk_stream_site_dword(codes, (size_t)Spad, site, obs_row, nobs, row_nodes, nrows, nchar, chunk) : 0u;
+        site < (size_t)Spad ? plk_stream_site_dword(codes, (size_t)Spad, site, obs_row, nobs, row_nodes, nrows, nchar, chunk, 3) : 0u;
 }
 
 /* HELD: the unit's first three chunks (c0 the current dword pair, c1 and c2 the two "in flight") are operands, loaded by
@@ -101,7 +105,12 @@ __device__ __forceinline__ void fused_run_program_v4s(double &lha, double &lhb, 
     lhb = __hiloint2double(bh, bl);
 }
 
-template <int THREADS, bool HELD = false, bool PAIR = false>
+/* GROUPS: the categories run in va.groups phases of va.cg categories (the three-leaf form, plk_v4t_plan: fewer resident images
+ * leave room for more tables).  A phase stages its group's tables -- behind a barrier that ends the look-ups of the phase
+ * before -- and every wave walks the same units as in every other phase, for the group's categories only; between the phases
+ * a site's partial mixture sum and exponent wait in va.part_sum / va.part_exp, written and read by the same lane.  The terms
+ * of a site are added in category order as without groups, so its log likelihood has the same bits. */
+template <int THREADS, bool HELD = false, bool PAIR = false, bool GROUPS = false>
 __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
 {
     constexpr int NW = THREADS / 64;
@@ -116,84 +125,116 @@ __global__ __launch_bounds__(THREADS) void k_ll_fused4_v4s(FusedV4SArgs va)
     const bool plain = a.root_mode == PLK_ROOT_NONE || a.root_mode == PLK_ROOT_UNIFORM;
     const double wu = a.root_mode == PLK_ROOT_NONE ? 1.0 : 0.25;
     const double rw0 = plain ? wu : rootw[0], rw1 = plain ? wu : rootw[1], rw2 = plain ? wu : rootw[2], rw3 = plain ? wu : rootw[3];
-    /* the tables of all categories, once per launch; the only barrier of the kernel */
-    {
-        const double2 *src = reinterpret_cast<const double2 *>(a.tip);
-        double2 *dst = reinterpret_cast<double2 *>(lds_dyn);
-        const int n2 = a.C * (tip_doubles / 2);
-        for (int i0 = tid; i0 < n2; i0 += 4 * THREADS) {
-            double2 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) v[u] = i0 + u * THREADS < n2 ? src[i0 + u * THREADS] : double2{0.0, 0.0};
-#pragma unroll
-            for (int u = 0; u < 4; u++) if (i0 + u * THREADS < n2) dst[i0 + u * THREADS] = v[u];
-        }
-    }
-    __syncthreads();
     const long nunits = (a.S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
     const unsigned cat32 = (unsigned)(a.ntips * a.nchar);
     dd acc = dd_make(0.0, 0.0);
     /* every wave makes the same number of passes (va.sync: the waves of the workgroup meet before every unit / category, so
      * that they read the same category's matrices and op words through the scalar cache at the same time) */
     const long stride = (long)gridDim.x * NW, passes = (nunits + stride - 1) / stride;
-    /* HELD: chunks 0 .. 2 of a unit are the same bytes in every category.  They are requested once per unit -- the next
-     * unit's before this unit's epilogue, the first unit's here -- and every category's prologue copies them.  A wave whose
-     * next unit does not exist requests nothing: no load goes past the stream (a unit has at least three chunks). */
-    unsigned long long c0 = 0, c1 = 0, c2 = 0;
-    auto request = [&](long unit) {
-        /* uniform base + the lane's 32-bit offset, formed here: a per-lane 64-bit address kept across the interpreter costs
-         * the two registers that decide between 168 VGPRs and a spill */
-        unsigned off = (unsigned)lane * 8u;
-        asm volatile("" : "+v"(off));
-        const char *p = reinterpret_cast<const char *>(va.stream + (size_t)unit * (size_t)va.chunks * PLK_V4S_UNIT) + off;
-        c0 = *reinterpret_cast<const unsigned long long *>(p);
-        c1 = *reinterpret_cast<const unsigned long long *>(p + PLK_V4S_CHUNK_BYTES);
-        c2 = *reinterpret_cast<const unsigned long long *>(p + 2 * PLK_V4S_CHUNK_BYTES);
-    };
-    if (HELD && (long)blockIdx.x * NW + wave < nunits) request((long)blockIdx.x * NW + wave);
-    for (long pass = 0; pass < passes; pass++) {
-        const long u = pass * stride + (long)blockIdx.x * NW + wave;
-        const bool active = u < nunits;
-        const unsigned *strm = va.stream + (size_t)(active ? u : 0) * (size_t)va.chunks * PLK_V4S_UNIT;
-        double sum[2] = {0.0, 0.0};
-        int Eexp[2] = {0, 0};
-        bool have[2] = {false, false};
-        if (va.sync & 1) __syncthreads();
-        for (int c = 0; c < a.C; c++) {
-            const double *ps = a.PS + (size_t)c * (a.nmat + 1) * 16;
-            const unsigned *ops = aa.words + (size_t)c * aa.nwords;
-            if (va.sync & 2) __syncthreads();
-            if (!active) continue;
-            if (aa.warm) {
-                /* scalar-cache warm-up of the category's matrix stream and op words: the waves of a CU start a unit's category
-                 * loosely in step, each touches its share of the lines (no barrier: best effort) */
-                fused_touch_lines(ps, (unsigned)(a.nmat + 1) * 128u, (unsigned)wave * 64u, NW * 64u);
-                fused_touch_lines(ops, (unsigned)aa.nwords * 4u, (unsigned)wave * 64u, NW * 64u);
+    const int ngroups = GROUPS ? va.groups : 1;
+    for (int g = 0; g < ngroups; g++) {
+        const int c_lo = GROUPS ? g * va.cg : 0, c_hi = GROUPS ? min(a.C, c_lo + va.cg) : a.C;
+        /* the tables of the resident categories (all of them, once per launch, without GROUPS); the only barrier of the kernel
+         * that something is staged behind */
+        if (GROUPS && g > 0) __syncthreads();
+        {
+            const double2 *src = reinterpret_cast<const double2 *>(a.tip) + (size_t)c_lo * (tip_doubles / 2);
+            double2 *dst = reinterpret_cast<double2 *>(lds_dyn);
+            const int n2 = (c_hi - c_lo) * (tip_doubles / 2);
+            /* GROUPS: the thread's index formed again in every phase from the wave's number and the lane count (kept across
+             * the interpreter, it and the addresses made from it are spilled to scratch) */
+            int first = tid;
+            if (GROUPS) {
+                int l;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+                first = wave * 64 + l;
             }
-            double lhs[2];
-            int esc[2];
-            fused_run_program_v4s<HELD, PAIR>(lhs[0], lhs[1], esc[0], esc[1], ops, ps, strm, (unsigned)lane * 8u, va.first_y + (unsigned)c * cat32,
-                                              rw0, rw1, rw2, rw3, c0, c1, c2, va.first_y1 + (unsigned)c * cat32, va.first_b1);
+            for (int i0 = first; i0 < n2; i0 += 4 * THREADS) {
+                double2 v[4];
 #pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const double lh = lhs[j];
-                const double term = prior[c] * lh;
-                if (term != 0.0) {
-                    if (!have[j]) { sum[j] = term; Eexp[j] = esc[j]; have[j] = true; }
-                    else if (esc[j] > Eexp[j]) { sum[j] = ldexp(sum[j], Eexp[j] - esc[j]) + term; Eexp[j] = esc[j]; }
-                    else sum[j] += ldexp(term, esc[j] - Eexp[j]);
-                }
+                for (int u = 0; u < 4; u++) v[u] = i0 + u * THREADS < n2 ? src[i0 + u * THREADS] : double2{0.0, 0.0};
+#pragma unroll
+                for (int u = 0; u < 4; u++) if (i0 + u * THREADS < n2) dst[i0 + u * THREADS] = v[u];
             }
         }
-        /* the next unit's first chunks travel while this unit's log, store and sum run */
-        if (HELD && u + stride < nunits) request(u + stride);
+        __syncthreads();
+        /* HELD: chunks 0 .. 2 of a unit are the same bytes in every category.  They are requested once per unit -- the next
+         * unit's before this unit's epilogue, the first unit's here -- and every category's prologue copies them.  A wave whose
+         * next unit does not exist requests nothing: no load goes past the stream (a unit has at least three chunks). */
+        unsigned long long c0 = 0, c1 = 0, c2 = 0;
+        auto request = [&](long unit) {
+            /* uniform base + the lane's 32-bit offset, formed here: a per-lane 64-bit address kept across the interpreter costs
+             * the two registers that decide between 168 VGPRs and a spill */
+            unsigned off = (unsigned)lane * 8u;
+            asm volatile("" : "+v"(off));
+            const char *p = reinterpret_cast<const char *>(va.stream + (size_t)unit * (size_t)va.chunks * PLK_V4S_UNIT) + off;
+            c0 = *reinterpret_cast<const unsigned long long *>(p);
+            c1 = *reinterpret_cast<const unsigned long long *>(p + PLK_V4S_CHUNK_BYTES);
+            c2 = *reinterpret_cast<const unsigned long long *>(p + 2 * PLK_V4S_CHUNK_BYTES);
+        };
+        if (HELD && (long)blockIdx.x * NW + wave < nunits) request((long)blockIdx.x * NW + wave);
+        for (long pass = 0; pass < passes; pass++) {
+            const long u = pass * stride + (long)blockIdx.x * NW + wave;
+            const bool active = u < nunits;
+            const unsigned *strm = va.stream + (size_t)(active ? u : 0) * (size_t)va.chunks * PLK_V4S_UNIT;
+            double sum[2] = {0.0, 0.0};
+            int Eexp[2] = {0, 0};
+            bool have[2] = {false, false};
+            if (GROUPS && g > 0 && active) {
 #pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const long s = u * PLK_V4S_UNIT + j * 64 + lane;
-            const double ll = have[j] ? log(sum[j]) + (double)Eexp[j] * 0.6931471805599453094 : -INFINITY;
-            if (active && s < a.S) {
-                if (a.site_ll) a.site_ll[s] = ll;
-                acc = dd_add(acc, dd_weighted(a.w, s, ll));
+                for (int j = 0; j < 2; j++) {
+                    const size_t s = (size_t)u * PLK_V4S_UNIT + j * 64 + lane;
+                    sum[j] = va.part_sum[s]; Eexp[j] = va.part_exp[s];
+                    have[j] = Eexp[j] != PLK_V4S_NO_TERM;
+                }
+            }
+            if (va.sync & 1) __syncthreads();
+            for (int c = c_lo; c < c_hi; c++) {
+                const double *ps = a.PS + (size_t)c * (a.nmat + 1) * 16;
+                const unsigned *ops = aa.words + (size_t)c * aa.nwords;
+                if (va.sync & 2) __syncthreads();
+                if (!active) continue;
+                if (aa.warm) {
+                    /* scalar-cache warm-up of the category's matrix stream and op words: the waves of a CU start a unit's category
+                     * loosely in step, each touches its share of the lines (no barrier: best effort) */
+                    fused_touch_lines(ps, (unsigned)(a.nmat + 1) * 128u, (unsigned)wave * 64u, NW * 64u);
+                    fused_touch_lines(ops, (unsigned)aa.nwords * 4u, (unsigned)wave * 64u, NW * 64u);
+                }
+                double lhs[2];
+                int esc[2];
+                fused_run_program_v4s<HELD, PAIR>(lhs[0], lhs[1], esc[0], esc[1], ops, ps, strm, (unsigned)lane * 8u, va.first_y + (unsigned)(c - c_lo) * cat32,
+                                                  rw0, rw1, rw2, rw3, c0, c1, c2, va.first_y1 + (unsigned)(c - c_lo) * cat32, va.first_b1);
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const double lh = lhs[j];
+                    const double term = prior[c] * lh;
+                    if (term != 0.0) {
+                        if (!have[j]) { sum[j] = term; Eexp[j] = esc[j]; have[j] = true; }
+                        else if (esc[j] > Eexp[j]) { sum[j] = ldexp(sum[j], Eexp[j] - esc[j]) + term; Eexp[j] = esc[j]; }
+                        else sum[j] += ldexp(term, esc[j] - Eexp[j]);
+                    }
+                }
+            }
+            /* the next unit's first chunks travel while this unit's log, store and sum run */
+            if (HELD && u + stride < nunits) request(u + stride);
+            if (GROUPS && g + 1 < ngroups) {
+                if (active) {
+#pragma unroll
+                    for (int j = 0; j < 2; j++) {
+                        const size_t s = (size_t)u * PLK_V4S_UNIT + j * 64 + lane;
+                        va.part_sum[s] = sum[j]; va.part_exp[s] = have[j] ? Eexp[j] : PLK_V4S_NO_TERM;
+                    }
+                }
+                continue;
+            }
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const long s = u * PLK_V4S_UNIT + j * 64 + lane;
+                const double ll = have[j] ? log(sum[j]) + (double)Eexp[j] * 0.6931471805599453094 : -INFINITY;
+                if (active && s < a.S) {
+                    if (a.site_ll) a.site_ll[s] = ll;
+                    acc = dd_add(acc, dd_weighted(a.w, s, ll));
+                }
             }
         }
     }

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -471,6 +472,12 @@ struct PlkFusedPT {
      * P_a (P_b defs[i] o P_c defs[j]) at code i * nchar + j) or the pseudo table (1 unit: the raw definitions) */
     std::vector<int> tab_unit, tab_edge, tab_eb, tab_ec;   /* first unit | leaf edge, edge above the cherry or -1 | pair: leaf edges, else -1 */
     int units = 0, npairs = 0;
+    /* three-leaf tables (plk_fused_v4t_build only; empty lists = none): a node d whose children are a cherry a = (b, c) and a
+     * leaf l, with the edge above d, as nchar * nchar units: P_d ((pair row of a) o (tip row of l)) at code
+     * (code_b * nchar + code_c) * nchar + code_l.  tab_edge = the edge above d, tab_eb / tab_ec the cherry's leaf edges,
+     * tab_ea the edge above the cherry, tab_el the leaf edge; row_node3 = l in the row of (b, c, l) */
+    std::vector<int> row_node3, tab_ea, tab_el;
+    int ntriples = 0;
     int first_unit = 0, first_row = 0, second_row = 0;
     /* the program after folding the cherries, op by op (what the words encode; the vector kernel's int4 program is made from it) */
     struct VOp { int code, unit, row, d, edge; };
@@ -497,6 +504,63 @@ static inline bool plk_pair_at(int N, const int *ip, const int *ix, const PlkPro
     return ea >= 0 && ix[ea] == a;
 }
 
+/* the 32-bit op words and the prologue fields of fu.vops (tables and rows are in place) */
+static inline void plk_fused_pt_words(int slots_needed, bool fuse_set, PlkFusedPT &fu)
+{
+    const std::vector<PlkFusedPT::VOp> &v = fu.vops;
+    std::vector<int> ou, orow;
+    for (const PlkFusedPT::VOp &o : v) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) { ou.push_back(o.unit); orow.push_back(o.row); }
+    const int nv = (int)v.size();
+    fu.words.assign(((nv + 1 + 7) / 8) * 8 + 8, (unsigned)OP_END);
+    size_t oi = 0, nw = 0;
+    bool matvec_since_obs = false;
+    for (int i = 0; i < nv; i++) {
+        const int code = v[i].code;
+        unsigned wv = (unsigned)code;
+        auto obs_fields = [&]() {
+            /* cyclic: the last observations request the first ones again, so that every request of the chain pairs a
+             * table with a row of its own kind (the values are dropped; the next category's prologue asks again) */
+            const unsigned un = (unsigned)ou[(oi + 1) % ou.size()];
+            const unsigned rn = (unsigned)orow[(oi + 2) % orow.size()];
+            return (un << 5) | (rn << 16);
+        };
+        if (code == OP_MATVEC) {
+            const int nx = i + 1 < nv ? v[i + 1].code : OP_END;
+            if (nx == OP_TIP_MUL && oi > 0) {
+                fu.words[nw++] = PLK_WORD_MATVEC_TIPMUL | obs_fields();
+                oi++; matvec_since_obs = false; i++;
+                continue;
+            }
+            matvec_since_obs = true;
+            if ((nx == OP_PUSH || nx == OP_POPMUL) && slots_needed <= 4) {
+                fu.words[nw++] = (nx == OP_PUSH ? 24u : 28u) + (unsigned)v[i + 1].d;
+                i++;
+                continue;
+            }
+        }
+        if (code == OP_TIP_SET || code == OP_TIP_MUL) {
+            unsigned oc = code == OP_TIP_SET ? (unsigned)OP_TIP_SET
+                                             : (matvec_since_obs && oi > 0 ? PLK_WORD_TIPMUL_NOWAIT : (unsigned)OP_TIP_MUL);
+            const int nx = i + 1 < nv ? v[i + 1].code : OP_END;
+            if (fuse_set && code == OP_TIP_SET && (nx == OP_POPMUL || nx == OP_PUSH)) {
+                /* TIP_SET followed by POPMUL / PUSH (a look-up as the last or as an earlier internal child): one word, handlers
+                 * 12 + d / 20 + d of the two-sites-per-lane interpreter; the value goes straight into the product / the slot */
+                oc = (nx == OP_POPMUL ? PLK_WORD_SET_POPMUL : PLK_WORD_SET_PUSH) + (unsigned)v[i + 1].d;
+                i++;
+            }
+            wv = oc | obs_fields();
+            matvec_since_obs = false;
+            oi++;
+        } else if (code == OP_PUSH || code == OP_POPMUL) {
+            wv = (code == OP_PUSH ? 8u : 16u) + (unsigned)v[i].d;
+        }
+        fu.words[nw++] = wv;
+    }
+    fu.first_unit = ou.empty() ? 0 : ou[0];
+    fu.first_row = orow.empty() ? 0 : orow[0];
+    fu.second_row = orow.size() > 1 ? orow[1] : 0;
+}
+
 /* max_pairs: how many cherries may become tables (LDS budget); nchar * nchar <= 256 is the caller's business */
 static inline void plk_fused_pt_build(int N, const int *ip, const int *ix, const PlkProgram &pg, int nchar, int max_pairs, PlkFusedPT &fu,
                                       bool fuse_set = false)
@@ -508,6 +572,7 @@ static inline void plk_fused_pt_build(int N, const int *ip, const int *ix, const
     fu.mat_edge.clear(); fu.row_node.clear(); fu.row_node2.clear();
     fu.tab_unit.clear(); fu.tab_edge.clear(); fu.tab_eb.clear(); fu.tab_ec.clear();
     fu.units = 0; fu.npairs = 0;
+    fu.row_node3.clear(); fu.tab_ea.clear(); fu.tab_el.clear(); fu.ntriples = 0;
     std::vector<int> row_of(N, -1);
     auto single_row = [&](int node) {
         if (row_of[node] < 0) { row_of[node] = (int)fu.row_node.size(); fu.row_node.push_back(node); fu.row_node2.push_back(-1); }
@@ -539,57 +604,7 @@ static inline void plk_fused_pt_build(int N, const int *ip, const int *ix, const
         }
     }
     if (pseudo_unit < 0) table(-1, -1, -1, 1);      /* always present: keeps the image non-empty and the layout regular */
-    std::vector<int> ou, orow;
-    for (const VOp &o : v) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) { ou.push_back(o.unit); orow.push_back(o.row); }
-    const int nv = (int)v.size();
-    fu.words.assign(((nv + 1 + 7) / 8) * 8 + 8, (unsigned)OP_END);
-    size_t oi = 0, nw = 0;
-    bool matvec_since_obs = false;
-    for (int i = 0; i < nv; i++) {
-        const int code = v[i].code;
-        unsigned wv = (unsigned)code;
-        auto obs_fields = [&]() {
-            /* cyclic: the last observations request the first ones again, so that every request of the chain pairs a
-             * table with a row of its own kind (the values are dropped; the next category's prologue asks again) */
-            const unsigned un = (unsigned)ou[(oi + 1) % ou.size()];
-            const unsigned rn = (unsigned)orow[(oi + 2) % orow.size()];
-            return (un << 5) | (rn << 16);
-        };
-        if (code == OP_MATVEC) {
-            const int nx = i + 1 < nv ? v[i + 1].code : OP_END;
-            if (nx == OP_TIP_MUL && oi > 0) {
-                fu.words[nw++] = PLK_WORD_MATVEC_TIPMUL | obs_fields();
-                oi++; matvec_since_obs = false; i++;
-                continue;
-            }
-            matvec_since_obs = true;
-            if ((nx == OP_PUSH || nx == OP_POPMUL) && pg.slots_needed <= 4) {
-                fu.words[nw++] = (nx == OP_PUSH ? 24u : 28u) + (unsigned)v[i + 1].d;
-                i++;
-                continue;
-            }
-        }
-        if (code == OP_TIP_SET || code == OP_TIP_MUL) {
-            unsigned oc = code == OP_TIP_SET ? (unsigned)OP_TIP_SET
-                                             : (matvec_since_obs && oi > 0 ? PLK_WORD_TIPMUL_NOWAIT : (unsigned)OP_TIP_MUL);
-            const int nx = i + 1 < nv ? v[i + 1].code : OP_END;
-            if (fuse_set && code == OP_TIP_SET && (nx == OP_POPMUL || nx == OP_PUSH)) {
-                /* TIP_SET followed by POPMUL / PUSH (a look-up as the last or as an earlier internal child): one word, handlers
-                 * 12 + d / 20 + d of the two-sites-per-lane interpreter; the value goes straight into the product / the slot */
-                oc = (nx == OP_POPMUL ? PLK_WORD_SET_POPMUL : PLK_WORD_SET_PUSH) + (unsigned)v[i + 1].d;
-                i++;
-            }
-            wv = oc | obs_fields();
-            matvec_since_obs = false;
-            oi++;
-        } else if (code == OP_PUSH || code == OP_POPMUL) {
-            wv = (code == OP_PUSH ? 8u : 16u) + (unsigned)v[i].d;
-        }
-        fu.words[nw++] = wv;
-    }
-    fu.first_unit = ou.empty() ? 0 : ou[0];
-    fu.first_row = orow.empty() ? 0 : orow[0];
-    fu.second_row = orow.size() > 1 ? orow[1] : 0;
+    plk_fused_pt_words(pg.slots_needed, fuse_set, fu);
 }
 
 static inline size_t plk_fused_pt_lds_bytes(const PlkFusedPT &fu, int nchar, int tile)
@@ -845,9 +860,10 @@ PLK_HD static inline size_t plk_stream_byte(size_t unit, int chunk, int lane, in
     return plk_stream_dword(unit, chunk, lane, half, chunks) * 4 + (size_t)byte;
 }
 /* the dword of chunk `chunk` for one site: the bytes of observations 4 chunk .. 4 chunk + 3, 0 past the last;
- * row_nodes = [2][nrows] as uploaded (node | second node of a pair row or -1), codes = [N][Spad] */
+ * row_nodes = [nlists][nrows] as uploaded (node | second node of a pair row or -1 | with nlists = 3: third node of a
+ * three-leaf row or -1; the byte of (b, c, l) is (code_b * nchar + code_c) * nchar + code_l), codes = [N][Spad] */
 PLK_HD static inline unsigned plk_stream_site_dword(const uint8_t *codes, size_t Spad, size_t site, const int *obs_row, int nobs,
-                                                    const int *row_nodes, int nrows, int nchar, int chunk)
+                                                    const int *row_nodes, int nrows, int nchar, int chunk, int nlists = 2)
 {
     unsigned d = 0;
     for (int b = 0; b < 4; b++) {
@@ -856,6 +872,8 @@ PLK_HD static inline unsigned plk_stream_site_dword(const uint8_t *codes, size_t
         const int row = obs_row[n], nb = row_nodes[row], nc = row_nodes[nrows + row];
         unsigned code = codes[(size_t)nb * Spad + site];
         if (nc >= 0) code = code * (unsigned)nchar + codes[(size_t)nc * Spad + site];
+        const int nl = nlists > 2 ? row_nodes[2 * nrows + row] : -1;
+        if (nl >= 0) code = code * (unsigned)nchar + codes[(size_t)nl * Spad + site];
         d |= (code & 0xffu) << (8 * b);
     }
     return d;
@@ -867,12 +885,23 @@ struct PlkFusedV4S {
     std::vector<int> obs_row;          /* staged row of observation n, program order */
     std::vector<unsigned> first_y;     /* per category: LDS offset / 32 of the first observation's table */
     int nobs = 0, chunks = 0, C = 0;
+    int Cg = 0;                        /* categories whose tables are resident at a time (C unless the kernel runs them in groups):
+                                          category c reads the image of c % Cg */
 };
+
+/* codes of table t: nchar (one leaf, the pseudo table), nchar^2 (a cherry) or nchar^3 (a three-leaf table) */
+static inline size_t plk_pt_table_codes(const PlkFusedPT &fu, size_t t, int nchar)
+{
+    if (t < fu.tab_el.size() && fu.tab_el[t] >= 0) return (size_t)nchar * nchar * nchar;
+    return fu.tab_eb[t] >= 0 ? (size_t)nchar * nchar : (size_t)nchar;
+}
 
 static inline size_t plk_fused_v4s_lds_bytes(const PlkFusedPT &fu, int nchar, int C) { return (size_t)C * fu.units * nchar * 32; }
 
-static inline void plk_fused_v4s_words(const PlkFusedPT &fu, int nchar, int C, unsigned tip_base, PlkFusedV4S &vs)
+static inline void plk_fused_v4s_words(const PlkFusedPT &fu, int nchar, int C, unsigned tip_base, PlkFusedV4S &vs, int Cg = 0)
 {
+    if (Cg < 1 || Cg > C) Cg = C;
+    vs.Cg = Cg;
     std::vector<unsigned> ou;
     vs.obs_row.clear();
     for (const PlkFusedPT::VOp &o : fu.vops) if (o.code == OP_TIP_SET || o.code == OP_TIP_MUL) { ou.push_back((unsigned)o.unit); vs.obs_row.push_back(o.row); }
@@ -898,7 +927,7 @@ static inline void plk_fused_v4s_words(const PlkFusedPT &fu, int nchar, int C, u
     vs.first_y.assign(C, 0u);
     const unsigned tb32 = tip_base / 32, cat32 = (unsigned)fu.units * (unsigned)nchar;
     for (int c = 0; c < C; c++) {
-        const unsigned base = tb32 + (unsigned)c * cat32;
+        const unsigned base = tb32 + (unsigned)(c % Cg) * cat32;
         unsigned *o = &vs.words[(size_t)c * vs.stride];
         size_t src = 0;
         for (size_t b = 0; b < nblocks; b++)
@@ -925,8 +954,10 @@ static inline std::string plk_fused_check_v4s(const PlkFusedPT &fu, const PlkFus
 {
     if (tip_base % 32 != 0) return "v4s program: LDS base granule";
     if (C < 1 || vs.C != C || vs.stride % 16 != 0 || vs.stride < 48 || vs.words.size() != (size_t)C * vs.stride || (int)vs.first_y.size() != C) return "v4s program: word count";
+    const int Cg = vs.Cg;
+    if (Cg < 1 || Cg > C) return "v4s program: categories per group";
     const size_t tip_bytes = (size_t)fu.units * nchar * 32;
-    if ((size_t)C * tip_bytes > lds_bytes_launched || tip_base + lds_bytes_launched > plk_pt_lds_limit(1024)) return "v4s program: table images larger than the launch's dynamic LDS";
+    if ((size_t)Cg * tip_bytes > lds_bytes_launched || tip_base + lds_bytes_launched > plk_pt_lds_limit(1024)) return "v4s program: table images larger than the launch's dynamic LDS";
     /* the chain of the 32-bit words: row and unit of every observation */
     std::vector<long> crow, cunit;
     std::vector<size_t> real;          /* indices of the program's words up to the END */
@@ -943,16 +974,17 @@ static inline std::string plk_fused_check_v4s(const PlkFusedPT &fu, const PlkFus
     if (nobs < 1 || vs.nobs != nobs || (int)vs.obs_row.size() != nobs) return "v4s program: observation count";
     if (vs.chunks != plk_stream_chunks(nobs) || PLK_V4S_AHEAD >= vs.chunks) return "v4s program: chunks of a unit";
     for (int n = 0; n < nobs; n++) if (vs.obs_row[n] != crow[n] || crow[n] < 0 || crow[n] >= (long)fu.row_node.size()) return plk_fmt("v4s program: observation %ld streams another row than the program reads", n);
-    std::vector<char> pair_unit(fu.units, 0);
-    for (size_t t = 0; t < fu.tab_unit.size(); t++) if (fu.tab_eb[t] >= 0 && fu.tab_unit[t] >= 0 && fu.tab_unit[t] < fu.units) pair_unit[fu.tab_unit[t]] = 1;
+    std::vector<size_t> unit_codes(fu.units, (size_t)nchar);
+    for (size_t t = 0; t < fu.tab_unit.size(); t++) if (fu.tab_unit[t] >= 0 && fu.tab_unit[t] < fu.units) unit_codes[fu.tab_unit[t]] = plk_pt_table_codes(fu, t, nchar);
     const unsigned tb32 = tip_base / 32, cat32 = (unsigned)fu.units * (unsigned)nchar;
     const size_t nblocks = vs.stride / 16;
     for (int c = 0; c < C; c++) {
-        const unsigned base = tb32 + (unsigned)c * cat32;
+        const int cl = c % Cg;             /* the image the category reads */
+        const unsigned base = tb32 + (unsigned)cl * cat32;
         auto y_ok = [&](unsigned y, long unit) {
             if (unit < 0 || unit >= fu.units || y != base + (unsigned)unit * (unsigned)nchar || y >= 65536u) return false;
-            const size_t ncodes = pair_unit[unit] ? (size_t)nchar * nchar : (size_t)nchar;
-            return (size_t)y * 32 >= tip_base + (size_t)c * tip_bytes && ((size_t)y + ncodes) * 32 <= tip_base + (size_t)(c + 1) * tip_bytes;
+            const size_t ncodes = unit_codes[unit];
+            return (size_t)y * 32 >= tip_base + (size_t)cl * tip_bytes && ((size_t)y + ncodes) * 32 <= tip_base + (size_t)(cl + 1) * tip_bytes;
         };
         if (!y_ok(vs.first_y[c], cunit[0])) return "v4s program: prologue table field";
         const unsigned *wd = &vs.words[(size_t)c * vs.stride];
@@ -1470,6 +1502,299 @@ static inline std::string plk_fused_check_v4p(const PlkFusedV4S &vs, const PlkFu
 }
 
 /*
+ * THREE-LEAF TABLES of the streamed form (plk_fused_v4t_build).  A node d that is not the root and whose children are a
+ * cherry a = (b, c) and a leaf l reads, in the checked pair-table program, TIP_SET (pair table of a), TIP_MUL (table of l),
+ * MATVEC (edge above d): one of nchar^3 vectors per category.  With that vector in a table of its own (nchar^2 units,
+ * code (code_b * nchar + code_c) * nchar + code_l, which must stay a byte: nchar^3 <= 256) the three ops become one TIP_SET;
+ * the pair table of a, the table of l, their two staged rows and the matrix of the edge leave the formats.  What followed
+ * the MATVEC stays where it was -- PUSH, POPMUL, TIP_MUL, SCALE are ops of their own in PlkFusedPT::vops, and the word
+ * builder fuses TIP_SET + PUSH / POPMUL as it does for any look-up -- so no SCALE moves, appears or disappears.  A SCALE
+ * between the look-ups and the MATVEC (d rescaled) keeps the node as it is, and so does a third child or data at d: the
+ * MATVEC must follow the two look-ups directly.  The program builder visits an internal child before the leaves, so the
+ * cherry is always the TIP_SET; the product of the two rows commutes bit for bit, so the order of the children in the tree
+ * makes no difference to the row.
+ * The rows are NOT built in double-double: a row is the handlers' own fp64 sequence on the handlers' own operands
+ * (plk_v4t_row: the rounded pair-table row, the rounded tip row, the matrix the stream would have delivered), so the
+ * looked-up vector is bit for bit what the interpreter computes from the three ops.
+ * The fold and pair-product derivations run on the rewritten formats as on any other.
+ */
+/* M in the matrix stream's layout (M[4 j + i] = P[i][j]); the MATVEC handler's sequence (tools/gen_fused4_v4.py, matvec):
+ * x = a o b, then per row one multiply and three fused multiply-adds in column order */
+PLK_HD static inline void plk_v4t_row(const double *M, const double *a, const double *b, double *out)
+{
+    double x[4];
+    for (int j = 0; j < 4; j++) x[j] = a[j] * b[j];
+    for (int i = 0; i < 4; i++) {
+        double acc = M[i] * x[0];
+        for (int j = 1; j < 4; j++) acc = fma(M[4 * j + i], x[j], acc);
+        out[i] = acc;
+    }
+}
+
+/* LDS bytes a three-leaf table adds to one category's image: nchar^2 units for the nchar + 1 of its cherry and its leaf */
+static inline size_t plk_v4t_extra_bytes(int nchar) { return (size_t)(nchar * nchar - nchar - 1) * nchar * 32; }
+
+/* the nodes that qualify, in program order: index into in.vops of the TIP_SET of (pair look-up, leaf look-up, MATVEC) */
+static inline void plk_v4t_candidates(const PlkFusedPT &in, int nchar, std::vector<int> &at)
+{
+    at.clear();
+    if (nchar < 2 || nchar * nchar * nchar > 256 || in.ntriples != 0) return;
+    std::vector<int> table_at(std::max(in.units, 1), -1);
+    for (size_t t = 0; t < in.tab_unit.size(); t++) if (in.tab_unit[t] >= 0 && in.tab_unit[t] < in.units) table_at[in.tab_unit[t]] = (int)t;
+    const std::vector<PlkFusedPT::VOp> &v = in.vops;
+    for (size_t i = 0; i + 2 < v.size(); i++) {
+        if (v[i].code != OP_TIP_SET || v[i + 1].code != OP_TIP_MUL || v[i + 2].code != OP_MATVEC) continue;
+        const int tp = table_at[v[i].unit], tl = table_at[v[i + 1].unit];
+        if (tp < 0 || tl < 0 || in.tab_eb[tp] < 0 || in.tab_eb[tl] >= 0 || in.tab_edge[tl] < 0) continue;
+        at.push_back((int)i);
+        i += 2;
+    }
+}
+
+/* in: a pair-table program plk_fused_check_pt has accepted; extra_bytes: LDS one category's image may grow by.  Takes the
+ * qualifying nodes in program order as long as they fit; out.ntriples == 0: out is a copy of in. */
+static inline void plk_fused_v4t_build(const PlkFusedPT &in, int slots_needed, int nchar, size_t extra_bytes, bool fuse_set, PlkFusedPT &out)
+{
+    std::vector<int> at;
+    plk_v4t_candidates(in, nchar, at);
+    const size_t per = plk_v4t_extra_bytes(nchar);
+    size_t take = per ? std::min(at.size(), extra_bytes / per) : 0;
+    /* the unit field of the op words has 11 bits */
+    while (take > 0 && (size_t)in.units + take * (size_t)(nchar * nchar - nchar - 1) >= 2048) take--;
+    if (take == 0) { out = in; return; }
+    at.resize(take);
+    typedef PlkFusedPT::VOp VOp;
+    PlkFusedPT o;
+    const int ntab = (int)in.tab_unit.size(), nrows = (int)in.row_node.size();
+    std::vector<int> table_at(std::max(in.units, 1), -1), new_unit(ntab, -1), new_row(nrows, -1);
+    for (int t = 0; t < ntab; t++) table_at[in.tab_unit[t]] = t;
+    auto table = [&](int edge, int eb, int ec, int ea, int el, int nunits) {
+        o.tab_unit.push_back(o.units); o.tab_edge.push_back(edge); o.tab_eb.push_back(eb); o.tab_ec.push_back(ec);
+        o.tab_ea.push_back(ea); o.tab_el.push_back(el);
+        const int u = o.units; o.units += nunits; return u;
+    };
+    auto row = [&](int n1, int n2, int n3) {
+        o.row_node.push_back(n1); o.row_node2.push_back(n2); o.row_node3.push_back(n3);
+        return (int)o.row_node.size() - 1;
+    };
+    bool pseudo = false;
+    size_t next = 0;
+    const std::vector<VOp> &v = in.vops;
+    for (size_t i = 0; i < v.size(); i++) {
+        if (next < at.size() && (size_t)at[next] == i) {
+            const int tp = table_at[v[i].unit], tl = table_at[v[i + 1].unit], rp = v[i].row, rl = v[i + 1].row;
+            const int u = table(v[i + 2].edge, in.tab_eb[tp], in.tab_ec[tp], in.tab_edge[tp], in.tab_edge[tl], nchar * nchar);
+            o.vops.push_back(VOp{OP_TIP_SET, u, row(in.row_node[rp], in.row_node2[rp], in.row_node[rl]), 0, -1});
+            o.ntriples++;
+            next++; i += 2;
+            continue;
+        }
+        VOp w = v[i];
+        if (w.code == OP_TIP_SET || w.code == OP_TIP_MUL) {
+            const int t = table_at[w.unit];
+            if (new_unit[t] < 0) {
+                new_unit[t] = table(in.tab_edge[t], in.tab_eb[t], in.tab_ec[t], -1, -1, in.tab_eb[t] >= 0 ? nchar : 1);
+                if (in.tab_eb[t] >= 0) o.npairs++;
+                if (in.tab_edge[t] < 0) pseudo = true;
+            }
+            if (new_row[w.row] < 0) new_row[w.row] = row(in.row_node[w.row], in.row_node2[w.row], -1);
+            w.unit = new_unit[t]; w.row = new_row[w.row];
+        } else if (w.code == OP_MATVEC) o.mat_edge.push_back(w.edge);
+        o.vops.push_back(w);
+    }
+    if (!pseudo) table(-1, -1, -1, -1, -1, 1);
+    plk_fused_pt_words(slots_needed, fuse_set, o);
+    out = std::move(o);
+}
+
+/*
+ * Replays the rewritten formats against the checked pair-table program they were derived from (in: accepted by
+ * plk_fused_check_pt).  The 32-bit words are decoded with their look-up chain into the ops they execute, which must be
+ * out.vops; those, with every three-leaf look-up unfolded into (pair look-up, leaf look-up, MATVEC), must be in.vops
+ * exactly: same opcodes, stack slots and SCALE positions, tables of the same edges read through rows of the same nodes, the
+ * matrix stream consumed exactly (the absorbed matrices are the ones missing).  A three-leaf table stands for a node of
+ * the tree that is not the root, whose children are exactly the cherry and the leaf, under the edge it names; the tables
+ * tile the unit range without gaps, so the largest code of every row kind addresses inside its table; unit and row fields
+ * fit the op words.  (The LDS offsets of the streamed words are plk_fused_check_v4s's business, which knows the table
+ * sizes; the rows themselves are checked against the fp64 replay by tests/triplecheck_main.cpp with plk_v4t_row, the
+ * function the device builder calls.)
+ */
+static inline std::string plk_fused_check_v4t(int N, const int *ip, const int *ix, const PlkFusedPT &in, const PlkFusedPT &out, int nchar)
+{
+    typedef PlkFusedPT::VOp VOp;
+    const int ntab = (int)out.tab_unit.size(), nrows = (int)out.row_node.size(), E = N - 1;
+    if (nchar < 2 || nchar * nchar * nchar > 256) return "v4t program: the combined code must stay a byte";
+    if ((int)out.tab_edge.size() != ntab || (int)out.tab_eb.size() != ntab || (int)out.tab_ec.size() != ntab || (int)out.tab_ea.size() != ntab ||
+        (int)out.tab_el.size() != ntab || (int)out.row_node2.size() != nrows || (int)out.row_node3.size() != nrows) return "v4t program: table sizes";
+    if (nrows < 1 || out.units < 1 || out.units >= 2048 || nrows >= 65536) return "v4t program: field widths";
+    std::vector<int> table_at(out.units, -1), in_table_at(std::max(in.units, 1), -1);
+    int expect = 0, ntri = 0;
+    for (int t = 0; t < ntab; t++) {
+        const int nu = (int)(plk_pt_table_codes(out, (size_t)t, nchar) / (size_t)nchar);
+        if (out.tab_unit[t] != expect || expect + nu > out.units) return "v4t program: table layout";
+        table_at[expect] = t;
+        expect += nu;
+        if (out.tab_el[t] >= 0) ntri++;
+    }
+    if (expect != out.units || ntri != out.ntriples) return "v4t program: table layout";
+    for (size_t t = 0; t < in.tab_unit.size(); t++) if (in.tab_unit[t] >= 0 && in.tab_unit[t] < in.units) in_table_at[in.tab_unit[t]] = (int)t;
+    /* the words, decoded: the chain delivers (cur_unit, cur_row) to every observation handler */
+    std::vector<VOp> dec;
+    {
+        if (out.words.size() % 8 != 0 || out.words.size() < 16) return "v4t program: word buffer";
+        auto unit_ok = [&](long u) { return u >= 0 && u < out.units && table_at[u] >= 0; };
+        auto row_ok = [&](long r) { return r >= 0 && r < nrows; };
+        long cur_unit = out.first_unit, cur_row = out.first_row, next_row = out.second_row;
+        if (!unit_ok(cur_unit) || !row_ok(cur_row) || !row_ok(next_row)) return "v4t program: prologue fields";
+        bool waited = true, ended = false;
+        for (size_t wi = 0; wi < out.words.size() && !ended; wi++) {
+            const unsigned w = out.words[wi], hidx = w & 31, y = (w >> 5) & 0x7ff, z = w >> 16;
+            auto observe = [&](int code) -> bool {
+                dec.push_back(VOp{code, (int)cur_unit, (int)cur_row, 0, -1});
+                if (!unit_ok(y) || !row_ok(z)) return false;
+                /* a row's largest code must fit the table it indexes: rows and tables of one kind */
+                const int t = table_at[y];
+                const int kind_t = out.tab_el[t] >= 0 ? 3 : out.tab_eb[t] >= 0 ? 2 : 1;
+                const int kind_r = out.row_node3[next_row] >= 0 ? 3 : out.row_node2[next_row] >= 0 ? 2 : 1;
+                if (kind_r > kind_t) return false;
+                cur_unit = y; cur_row = next_row; next_row = z;
+                waited = false;
+                return true;
+            };
+            bool ok = true;
+            if (hidx == OP_END) ended = true;
+            else if (hidx == OP_MATVEC) { dec.push_back(VOp{OP_MATVEC, 0, 0, 0, -1}); waited = true; }
+            else if (hidx == PLK_WORD_MATVEC_TIPMUL) { dec.push_back(VOp{OP_MATVEC, 0, 0, 0, -1}); waited = true; ok = observe(OP_TIP_MUL); }
+            else if (hidx == OP_TIP_SET) ok = observe(OP_TIP_SET);
+            else if (hidx == OP_TIP_MUL) ok = observe(OP_TIP_MUL);
+            else if (hidx == PLK_WORD_TIPMUL_NOWAIT) { if (!waited) return plk_fmt("v4t program: word %ld skips a wait it needs", (long)wi); ok = observe(OP_TIP_MUL); }
+            else if (hidx == OP_SCALE) dec.push_back(VOp{OP_SCALE, 0, 0, 0, -1});
+            else if (hidx >= PLK_WORD_SET_POPMUL && hidx < PLK_WORD_SET_POPMUL + 4) { ok = observe(OP_TIP_SET); dec.push_back(VOp{OP_POPMUL, 0, 0, (int)(hidx & 3), -1}); }
+            else if (hidx >= PLK_WORD_SET_PUSH && hidx < PLK_WORD_SET_PUSH + 4) { ok = observe(OP_TIP_SET); dec.push_back(VOp{OP_PUSH, 0, 0, (int)(hidx & 3), -1}); }
+            else if (hidx >= 24) { dec.push_back(VOp{OP_MATVEC, 0, 0, 0, -1}); waited = true; dec.push_back(VOp{hidx < 28 ? OP_PUSH : OP_POPMUL, 0, 0, (int)(hidx & 3), -1}); }
+            else if (hidx >= 8 && hidx < 12) dec.push_back(VOp{OP_PUSH, 0, 0, (int)(hidx & 7), -1});
+            else if (hidx >= 16 && hidx < 20) dec.push_back(VOp{OP_POPMUL, 0, 0, (int)(hidx & 7), -1});
+            else return plk_fmt("v4t program: word %ld jumps to an empty handler slot", (long)wi);
+            if (!ok) return plk_fmt("v4t program: word %ld requests a table or a row out of range", (long)wi);
+        }
+        if (!ended) return "v4t program: no END";
+    }
+    if (dec.size() != out.vops.size()) return plk_fmt("v4t program: the words execute %ld ops, the rewritten program has %ld", (long)dec.size(), (long)out.vops.size());
+    for (size_t i = 0; i < dec.size(); i++) {
+        const VOp &a = dec[i], &b = out.vops[i];
+        const bool obs = b.code == OP_TIP_SET || b.code == OP_TIP_MUL;
+        if (a.code != b.code || (obs && (a.unit != b.unit || a.row != b.row)) || ((b.code == OP_PUSH || b.code == OP_POPMUL) && a.d != b.d))
+            return plk_fmt("v4t program: decoded op %ld is not the rewritten program's", (long)i);
+    }
+    /* the rewritten ops, unfolded, against the checked ones */
+    size_t j = 0, mi = 0;
+    int absorbed = 0;
+    std::vector<char> used(ntab, 0);
+    auto same_single = [&](const VOp &a, const VOp &b) {       /* a of out, b of in: one look-up of the same table through the same row */
+        if (b.unit < 0 || b.unit >= in.units || in_table_at[b.unit] < 0 || b.row < 0 || b.row >= (int)in.row_node.size()) return false;
+        const int t = table_at[a.unit], ti = in_table_at[b.unit];
+        return out.tab_el[t] < 0 && out.tab_edge[t] == in.tab_edge[ti] && out.tab_eb[t] == in.tab_eb[ti] && out.tab_ec[t] == in.tab_ec[ti] &&
+               out.row_node[a.row] == in.row_node[b.row] && out.row_node2[a.row] == in.row_node2[b.row] && out.row_node3[a.row] == -1;
+    };
+    for (size_t i = 0; i < out.vops.size(); i++) {
+        const VOp &a = out.vops[i];
+        if (j >= in.vops.size()) return "v4t program: more ops than the checked program";
+        const VOp &b = in.vops[j];
+        if (a.code == OP_TIP_SET || a.code == OP_TIP_MUL) {
+            const int t = table_at[a.unit];
+            if (used[t]++ && out.tab_edge[t] >= 0) return plk_fmt("v4t program: table %ld used twice", (long)t);
+            if (out.tab_el[t] < 0) {
+                if (a.code != b.code || !same_single(a, b)) return plk_fmt("v4t program: look-up %ld is not the checked program's", (long)i);
+                j++;
+                continue;
+            }
+            /* a three-leaf look-up: the checked program continues with the cherry's look-up, the leaf's and the MATVEC */
+            if (a.code != OP_TIP_SET || j + 2 >= in.vops.size()) return plk_fmt("v4t program: three-leaf look-up %ld", (long)i);
+            const VOp &bp = in.vops[j], &bl = in.vops[j + 1], &bm = in.vops[j + 2];
+            if (bp.code != OP_TIP_SET || bl.code != OP_TIP_MUL || bm.code != OP_MATVEC) return plk_fmt("v4t program: three-leaf look-up %ld does not stand for look-up, look-up, MATVEC", (long)i);
+            const int tp = in_table_at[bp.unit], tl = in_table_at[bl.unit];
+            if (tp < 0 || tl < 0 || in.tab_eb[tp] < 0 || in.tab_eb[tl] >= 0 || in.tab_edge[tl] < 0) return plk_fmt("v4t program: three-leaf look-up %ld: not a cherry and a leaf", (long)i);
+            if (out.tab_eb[t] != in.tab_eb[tp] || out.tab_ec[t] != in.tab_ec[tp] || out.tab_ea[t] != in.tab_edge[tp] || out.tab_el[t] != in.tab_edge[tl] ||
+                out.tab_edge[t] != bm.edge) return plk_fmt("v4t program: three-leaf table %ld holds other edges than the ops it stands for", (long)t);
+            if (out.row_node[a.row] != in.row_node[bp.row] || out.row_node2[a.row] != in.row_node2[bp.row] || out.row_node3[a.row] != in.row_node[bl.row] ||
+                in.row_node2[bl.row] != -1) return plk_fmt("v4t program: row of three-leaf look-up %ld", (long)i);
+            /* the tree: d under the absorbed edge, not the root (it has an edge above it), children exactly a and l */
+            const int e = out.tab_edge[t], ea = out.tab_ea[t], el = out.tab_el[t];
+            if (e < 0 || e >= E || ea < 0 || ea >= E || el < 0 || el >= E) return plk_fmt("v4t program: edges of three-leaf table %ld", (long)t);
+            const int d = ix[e];
+            if (ip[d + 1] - ip[d] != 2 || plk_edge_parent(N, ip, ea) != d || plk_edge_parent(N, ip, el) != d || ea == el ||
+                plk_edge_parent(N, ip, out.tab_eb[t]) != ix[ea] || ip[ix[el] + 1] != ip[ix[el]] || out.row_node3[a.row] != ix[el])
+                return plk_fmt("v4t program: three-leaf table %ld is not a cherry and a leaf under one node", (long)t);
+            absorbed++;
+            j += 3;
+            continue;
+        }
+        if (a.code != b.code) return plk_fmt("v4t program: op %ld is not the checked program's", (long)i);
+        if (a.code == OP_MATVEC) {
+            if (mi >= out.mat_edge.size() || out.mat_edge[mi] != b.edge || a.edge != b.edge) return plk_fmt("v4t program: matrix %ld is not the op's edge", (long)mi);
+            mi++;
+        } else if ((a.code == OP_PUSH || a.code == OP_POPMUL) && a.d != b.d) return plk_fmt("v4t program: stack op %ld", (long)i);
+        j++;
+    }
+    if (j != in.vops.size()) return "v4t program: the checked program's ops are not all covered";
+    if (mi != out.mat_edge.size() || out.mat_edge.size() + (size_t)absorbed != in.mat_edge.size()) return "v4t program: matrix stream not consumed exactly";
+    if (absorbed != out.ntriples) return "v4t program: three-leaf tables that no op reads";
+    return "";
+}
+
+/*
+ * Which three-leaf form the streamed kernel takes: the categories in G groups of Cg = ceil(C / G) (the tables of one group
+ * resident at a time: G phases in one launch) and `nodes` three-leaf tables in the room that leaves.  Candidates G = 1, 2, C.
+ * Per unit and category an absorbed node saves PLK_V4T_NODE_INSTS vector instructions (the 32 of the product, the 8 of the
+ * elementwise product, 4 of the look-up's address); a further phase costs, per unit, the prologue of a category once more
+ * and the round trip of the partial mixture sum (PLK_V4T_PHASE_UNIT_INSTS), and once the restaging of the tables and the
+ * skew of two barriers (PLK_V4T_PHASE_INSTS, in instructions of one wave).  The best candidate with a gain is taken when
+ * the option forces the form; the default also asks every wave to walk at least PLK_V4T_MIN_PASSES units per phase: the
+ * smallest count at which the form was measured to win (4 at 1.25M sites of BASELINE config 3, - 16 %; 3 at config 2 was
+ * even; DESIGN.md section 4, profiles/ll_k4_triple_ab.json).
+ */
+#define PLK_V4T_NODE_INSTS 44
+#define PLK_V4T_PHASE_UNIT_INSTS 120
+#define PLK_V4T_PHASE_INSTS 6000
+#define PLK_V4T_MIN_PASSES 4
+struct PlkV4TPlan { int groups = 1, Cg = 0, nodes = 0; size_t extra_bytes = 0; };
+
+/* triple: 0 forbidden, 1 default, 2 forced;  groups_opt: 0 the model's choice, 1 one group, 2 two groups, -1 a group per category */
+static inline PlkV4TPlan plk_v4t_plan(const PlkFusedPT &fpt, int nchar, int C, long S, int num_cus, size_t static_lds, int triple, int groups_opt)
+{
+    PlkV4TPlan best;
+    best.Cg = C;
+    std::vector<int> at;
+    plk_v4t_candidates(fpt, nchar, at);
+    if (triple == 0 || at.empty() || C < 1 || S < 1) return best;
+    const long nunits = (S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
+    const long waves = std::min<long>((nunits + 11) / 12, std::max(num_cus, 1)) * 12;
+    const long passes = (nunits + waves - 1) / waves;
+    const size_t per = plk_v4t_extra_bytes(nchar), image = (size_t)fpt.units * nchar * 32, limit = plk_pt_lds_limit(1024);
+    double best_gain = triple == 2 ? -1e300 : 0.0;     /* forced: the best candidate whatever the model says of it */
+    const int cand[3] = {1, 2, C};
+    for (int q = 0; q < 3; q++) {
+        const int G = cand[q];
+        if (G < 1 || G > C || (q > 0 && G == cand[q - 1]) || (q == 2 && G == 1)) continue;
+        if (groups_opt > 0 && G != std::min(groups_opt, C)) continue;
+        if (groups_opt == -1 && G != C) continue;
+        const int Cg = (C + G - 1) / G, groups = (C + Cg - 1) / Cg;
+        if (static_lds + (size_t)Cg * image > limit) continue;
+        const size_t room = (limit - static_lds) / (size_t)Cg - image;
+        size_t t = std::min(at.size(), room / per);
+        while (t > 0 && (size_t)fpt.units + t * (size_t)(nchar * nchar - nchar - 1) >= 2048) t--;
+        if (t == 0) continue;
+        if (triple == 1 && passes < PLK_V4T_MIN_PASSES) continue;
+        const double gain = (double)C * (double)t * PLK_V4T_NODE_INSTS * (double)passes -
+                            (double)(groups - 1) * (PLK_V4T_PHASE_INSTS + (double)PLK_V4T_PHASE_UNIT_INSTS * (double)passes);
+        if (gain > best_gain) {
+            best_gain = gain; best.groups = groups; best.Cg = Cg; best.nodes = (int)t; best.extra_bytes = t * per;
+        }
+    }
+    return best;
+}
+
+/*
  * The vector ll kernel (k_ll_vec, plk_vec.h) on the pair-table program: int4 ops
  *   observation (TIP_SET / TIP_MUL)  x = opcode, y = first row of the op's table (unit * nchar: the kernel adds the code),
  *                                    w = staged row of the NEXT observation op (cyclic)
@@ -1621,12 +1946,15 @@ enum { PLK_K4_LDS_V4S_768 = 0, PLK_K4_LDS_V4_768, PLK_K4_LDS_V4_512 };     /* Pl
  * as it was before the folded op stream and the held first chunks (the checked stream unfolded, every category requests
  * the unit's first three chunks itself), + 128 / + 256 without the held chunks only / without the fold only, + 512 without the
  * pair-product form (the folded stream with held chunks on every tree; that form needs both, so + 64 / + 128 / + 256 turn
- * it off as well).  The + bits are for measurements. */
-struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held, pair; };
+ * it off as well), + 1024 the three-leaf form of the streamed kernel (plk_fused_v4t_build) wherever it applies, whatever the
+ * site count, + 2048 never, + 4096 / + 8192 / both its categories in one group / a group per category / two groups (more
+ * than one group needs the pair-product form).  The + bits are for measurements. */
+struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held, pair, triple, groups; };
 static inline PlkPairTablesOpt plk_pair_tables_opt(long v)
 {
     return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2, (v & (64 | 256)) ? 0 : 1, (v & (64 | 128)) ? 0 : 1,
-            (v & (64 | 128 | 256 | 512)) ? 0 : 1};
+            (v & (64 | 128 | 256 | 512)) ? 0 : 1, (v & 2048) ? 0 : (v & 1024) ? 2 : 1,
+            (v & (4096 | 8192)) == (4096 | 8192) ? 2 : (v & 4096) ? 1 : (v & 8192) ? -1 : 0};
 }
 
 struct PlkK4Shape {
@@ -1647,6 +1975,7 @@ struct PlkK4Choice {
     int warm = 1, sync = 2;                          /* pair-table kernels: the measurement bits of PLK_OPT_PAIR_TABLES */
     int fold = 1, held = 1;                          /* v4s: folded op stream, first chunks held across the categories */
     int pair = 0;                                    /* v4s: the pair-product form is asked for and the program is within its 3 slots */
+    PlkV4TPlan triple;                               /* v4s: three-leaf tables and category groups (plk_v4t_plan; nodes == 0: not taken) */
     std::string bad;                                 /* the replay check of the chosen variant's formats; empty: fine */
 };
 
@@ -1687,6 +2016,10 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
                  * streamed words are checked against) */
                 ch.bad = plk_fused_check_pt(N, ip, ix, pg, fpt, nchar, 1, 0, true, false);
                 if (ch.bad.empty()) ch.bad = plk_fused_check_v4s(fpt, fv4s, nchar, sh.C, ch.tip_base, lds);
+                /* three-leaf tables: which nodes and how many groups (the phases exist in the pair-product instantiation only);
+                 * the formats themselves are derived from fpt and replayed like the fold and the pair products */
+                if (ch.bad.empty())
+                    ch.triple = plk_v4t_plan(fpt, nchar, sh.C, sh.S, sh.num_cus, st, po.triple, ch.pair && ch.fold && ch.held ? po.groups : 1);
                 return ch;
             }
         }
