@@ -455,6 +455,11 @@ enum {
                                        derived next to: a PAIR op with an ADVANCE counts as the observation op that carried it */
     PLK_INFO_NNI_KERNEL = 22,       /* up pass of the last plk_nni_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
                                        4 categories), 2 = generic */
+    PLK_INFO_LL_QUAD = 24,          /* four-leaf tables in the last ll evaluation's streamed kernel: 0 = the form did not run (as for
+                                       PLK_INFO_LL_TRIPLE; also: a leaf with more than 4 occurring codes under every node that
+                                       would qualify, PLK_OPT_PAIR_TABLES + 32768, or + 1024 without + 16384), else bit 0 = it ran
+                                       and bits 8-23 = nodes of a category that are look-ups of a four-leaf table.
+                                       PLK_INFO_LL_TRIPLE then reports the groups and the three-leaf tables beside them */
     PLK_INFO_LL_TRIPLE = 23         /* three-leaf tables in the last ll evaluation's streamed kernel: 0 = the form did not run (another
                                        kernel, no node that qualifies, too few sites for the default, PLK_OPT_PAIR_TABLES + 2048, or
                                        formats that did not replay), else bit 0 = it ran, bits 4-7 = groups the categories ran in
@@ -511,7 +516,14 @@ enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PE
                                the tables of one group resident at a time, in phases of the one launch); the default takes
                                it only where every wave walks enough units per phase to pay for the phases (DESIGN.md
                                section 4); + 2048: never; + 4096 / + 8192 / both: the categories in one group / one group
-                               per category / two groups instead of the cost model's choice (measurements) */,
+                               per category / two groups instead of the cost model's choice (measurements);
+                               + 16384: the four-leaf form wherever it applies, whatever the site count (a node that is not
+                               the root, with four leaves below it as ((cherry, leaf), leaf) or (cherry, cherry), each leaf
+                               taking at most 4 of the nchar codes in the uploaded patterns, becomes with the edge above it
+                               one look-up of a 256-row table indexed by the leaves' code ranks; any nchar <= 16); it
+                               implies + 1024 for the nodes it leaves, and the default takes it under the same rule as the
+                               three-leaf form; + 32768: never.  + 1024 alone keeps to three-leaf tables, + 2048 forbids
+                               both (PLK_INFO_LL_QUAD) */,
        PLK_OPT_VEC_REG_STACK = 7 /* 1 (default): the vector kernels (9 <= k <= 20) keep the three busiest stack slots in
                                registers (2 waves per SIMD); 0: every waiting vector goes through HBM slots (round 2) */,
        PLK_OPT_MFMA_NS2 = 8 /* 1: the matrix-core ll kernel for 33 <= k <= 64 gives a wave two groups of 16 sites (every staged

@@ -70,6 +70,7 @@ struct LlPlan {
     long info_pairmul = 0;               /* PLK_INFO_LL_PAIRMUL */
     PlkV4TPlan triple;                   /* streamed form: three-leaf tables and category groups (nodes == 0: the form does not run) */
     long info_triple = 0;                /* PLK_INFO_LL_TRIPLE */
+    long info_quad = 0;                  /* PLK_INFO_LL_QUAD */
 };
 
 struct plk_engine {
@@ -112,6 +113,7 @@ struct plk_engine {
     double *d_defs = nullptr;            /* [nchar][K] zero padded */
     double *d_B = nullptr;               /* [N][k][S] */
     std::vector<char> node_has_data;     /* internal nodes whose observations are not all-ones */
+    std::vector<int> node_codes;         /* N, codes with nchar <= 16 only (else empty): bit `code` set when some site carries it at the node */
     double *d_w = nullptr;
 
     /* traversal program (plk_program.h) */
@@ -142,9 +144,13 @@ struct plk_engine {
     PlkFusedV4P fv4p;                    /* ... and the pair-product stream of trees within 3 slots (k_ll_fused4_v4s<768, true, true>) */
     unsigned *d_cstream = nullptr; size_t cstream_cap = 0;   /* the code stream (plk_stream_dword), built by upload_formats */
     int *d_obs_row = nullptr;            /* staged row per observation of the program */
-    int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [3][rows] staged-row nodes (third: the leaf of a three-leaf row); [6][ntab] unit, edge,
-                                                        leaf edges of a pair, edge above the cherry and leaf edge of a three-leaf table;
-                                                        the three-leaf tables are the last fpt.ntriples of the list */
+    int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [5][rows] staged-row nodes (third: the leaf of a three-leaf row; fourth and the index
+                                                        of the rank tables: four-leaf rows); [10][ntab] unit, edge, leaf edges of a pair,
+                                                        edge above the cherry and leaf edge of a three-leaf table, shape and further edges
+                                                        of a four-leaf table; the list ends with fpt.ntriples three-leaf tables and then
+                                                        fpt.nquads four-leaf tables */
+    uint8_t *d_quad_lut = nullptr;       /* four-leaf rows: PlkFusedPT::lut, [nquads][4][16] code -> rank (the stream builder's) */
+    int *d_quad_codes = nullptr;         /* ... and [nquads][4][4] rank -> code (the table builder's; a rank that does not occur: the code of rank 0) */
     PlkFusedPT fpt_t;                    /* three-leaf form: the rewritten formats while they are derived and checked (then moved to fpt) */
     PlkFusedV4S fv4s_t;
     double *d_llstate = nullptr; size_t llstate_cap = 0;   /* category groups: per site the partial mixture sum, then the exponents */
@@ -204,7 +210,7 @@ struct plk_engine {
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
-    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_pairmul = 0, info_ll_triple = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
+    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_pairmul = 0, info_ll_triple = 0, info_ll_quad = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
 static std::string g_create_error;
@@ -703,11 +709,10 @@ __device__ __forceinline__ void pt_pair_row(const dd *Pa, const dd *Pb, const dd
     }
 }
 
-__global__ void k_build_tables_pt(int E, int ntab, int units, int nchar, const int *__restrict__ tab,
-                                  const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
-                                  double *__restrict__ tip)
+__device__ __forceinline__ void build_table_pt(int t, int c, int E, int ntab, int units, int nchar, const int *__restrict__ tab,
+                                               const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
+                                               double *__restrict__ tip)
 {
-    const int t = blockIdx.x, c = blockIdx.y;
     const int unit = tab[t], e = tab[ntab + t], eb = tab[2 * ntab + t], ec = tab[3 * ntab + t];
     double *out = tip + ((size_t)c * units + unit) * nchar * 4;
     if (eb < 0) {
@@ -728,17 +733,23 @@ __global__ void k_build_tables_pt(int E, int ntab, int units, int nchar, const i
     }
 }
 
+__global__ void k_build_tables_pt(int E, int ntab, int units, int nchar, const int *__restrict__ tab,
+                                  const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
+                                  double *__restrict__ tip)
+{
+    build_table_pt(blockIdx.x, blockIdx.y, E, ntab, units, nchar, tab, Pdd, defs, tip);
+}
+
 /* Three-leaf tables of the streamed form (plk_fused_v4t_build), one block per (table, category): tab[6][ntab] as for
  * k_build_tables_pt, then the edge above the cherry and the leaf edge; the tables built here are first .. first + gridDim.x - 1
  * of the list.  A row is the MATVEC handler's fp64 sequence (plk_v4t_row) on what the interpreter would have looked up and
  * loaded: the rounded row of the cherry's pair table and the rounded row of the leaf's table (pt_pair_row, pt_leaf_dd: the
  * functions k_build_tables_pt writes them with), and the rounded matrix of the edge above the node as K1 writes it to the matrix stream.
  *   out[(cb*nchar+cc)*nchar+cl][i] = (P_d (pair[cb*nchar+cc] o tip[cl]))_i */
-__global__ void k_build_tables_t(int E, int ntab, int first, int units, int nchar, const int *__restrict__ tab,
-                                 const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
-                                 double *__restrict__ tip)
+__device__ __forceinline__ void build_table_t(int t, int c, int E, int ntab, int units, int nchar, const int *__restrict__ tab,
+                                              const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
+                                              double *__restrict__ tip)
 {
-    const int t = first + blockIdx.x, c = blockIdx.y;
     const int unit = tab[t], e = tab[ntab + t], eb = tab[2 * ntab + t], ec = tab[3 * ntab + t], ea = tab[4 * ntab + t], el = tab[5 * ntab + t];
     double *out = tip + ((size_t)c * units + unit) * nchar * 4;
     const dd *Pd = Pdd + ((size_t)c * E + e) * 16, *Pa = Pdd + ((size_t)c * E + ea) * 16, *Pb = Pdd + ((size_t)c * E + eb) * 16,
@@ -756,18 +767,85 @@ __global__ void k_build_tables_t(int E, int ntab, int first, int units, int ncha
     }
 }
 
+__global__ void k_build_tables_t(int E, int ntab, int first, int units, int nchar, const int *__restrict__ tab,
+                                 const dd *__restrict__ Pdd, const double *__restrict__ defs /* [nchar][4] */,
+                                 double *__restrict__ tip)
+{
+    build_table_t(first + blockIdx.x, blockIdx.y, E, ntab, units, nchar, tab, Pdd, defs, tip);
+}
+
+/* The tables of formats with four-leaf tables (plk_fused_v4q_build), ALL of them in one launch of 256-thread blocks, one
+ * block per (table, category): tables 0 .. first_t - 1 of the list as k_build_tables_pt builds them, first_t .. first_q - 1
+ * as k_build_tables_t does (the same device functions; a launch less than the three-leaf form needs, so the step outside
+ * the traversal kernel does not grow with the form), the rest four-leaf tables, one row per thread: tab[10][ntab] as
+ * above, then shape and the further edges; rank_codes[16 q + 4 j + r] is the code of rank r at leaf j of the q-th
+ * four-leaf table (plk_v4q_rank_codes).
+ * One set of device functions now serves two launch shapes, and the two must stay in step: without four-leaf tables
+ * run_expm still launches k_build_tables_pt and k_build_tables_t on their own, in 64-thread blocks over their part of the
+ * list; here build_table_pt / build_table_t run in 256-thread blocks indexed by the whole list.  Both bodies only loop
+ * over their rows with a blockDim.x stride, use no barrier and no shared memory, and return for the whole block at once, which is
+ * what lets them run in front of this kernel's first __syncthreads; a change to either that breaks one of these breaks the
+ * fused launch.  (A single table's nchar rows leave most of a 256-thread block idle; the launch saved outweighs it, see
+ * DESIGN.md section 4.)  The
+ * operands are the rounded rows k_build_tables_pt writes (pt_pair_row, pt_leaf_dd) and the rounded matrices K1 writes to the
+ * matrix stream; every distinct one is computed once per block (16 pair rows and 4 tip rows at most per child, 64 inner
+ * rows of shape A), then
+ *   A  t[(rb*4+rc)*4+r1] = plk_v4t_row(M_et, pair[rb*4+rc], tip1[r1]);  out[.. *4 + r2] = plk_v4t_row(M_ed, t, tip2[r2])
+ *   B  out[(rb*4+rc)*16 + rf*4+rg] = plk_v4t_row(M_ed, pair[rb*4+rc], pair2[rf*4+rg])
+ * The elementwise product inside plk_v4t_row is the TIP_MUL / POPMUL handlers' v_mul_f64, which commutes bit for bit. */
+__global__ __launch_bounds__(256) void k_build_tables_q(int E, int ntab, int first_t, int first_q, int units, int nchar, const int *__restrict__ tab,
+                                                        const int *__restrict__ rank_codes, const dd *__restrict__ Pdd,
+                                                        const double *__restrict__ defs /* [nchar][4] */, double *__restrict__ tip)
+{
+    __shared__ double s_pair[2][16][4], s_tip[2][4][4], s_t[64][4], s_M[2][16];
+    const int t = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    /* block-uniform: the whole block leaves before the first barrier */
+    if (t < first_t) { build_table_pt(t, c, E, ntab, units, nchar, tab, Pdd, defs, tip); return; }
+    if (t < first_q) { build_table_t(t, c, E, ntab, units, nchar, tab, Pdd, defs, tip); return; }
+    const int unit = tab[t], e = tab[ntab + t], eb = tab[2 * ntab + t], ec = tab[3 * ntab + t], ea = tab[4 * ntab + t], el = tab[5 * ntab + t],
+              shape = tab[6 * ntab + t], et = tab[7 * ntab + t], ef = tab[8 * ntab + t], eg = tab[9 * ntab + t];
+    const int *rc4 = rank_codes + 16 * (size_t)(t - first_q);
+    const dd *Pc0 = Pdd + (size_t)c * E * 16;
+    double *out = tip + ((size_t)c * units + unit) * nchar * 4;
+    const bool A = shape == PLK_V4Q_A;
+    if (tid < 16) {
+        pt_pair_row(Pc0 + (size_t)ea * 16, Pc0 + (size_t)eb * 16, Pc0 + (size_t)ec * 16, defs + rc4[tid >> 2] * 4, defs + rc4[4 + (tid & 3)] * 4, s_pair[0][tid]);
+    } else if (tid < 32 && !A) {
+        const int q = tid - 16;
+        pt_pair_row(Pc0 + (size_t)et * 16, Pc0 + (size_t)ef * 16, Pc0 + (size_t)eg * 16, defs + rc4[8 + (q >> 2)] * 4, defs + rc4[12 + (q & 3)] * 4, s_pair[1][q]);
+    } else if (tid < 24 && A) {
+        const int q = tid - 16, which = q >> 2, r = q & 3;
+        dd v[4];
+        pt_leaf_dd(Pc0 + (size_t)(which ? ef : el) * 16, defs + rc4[8 + 4 * which + r] * 4, v);
+        for (int i = 0; i < 4; i++) s_tip[which][r][i] = v[i].hi;
+    } else if (tid >= 64 && tid < 96) {
+        /* the stream's layout: M[4 j + i] = P[i][j] (Pdd is clamped at 0); matrix 0 above d, matrix 1 above t (shape A) */
+        const int m = (tid - 64) >> 4, idx = tid & 15;
+        if (m == 0 || A) s_M[m][idx] = Pc0[(size_t)(m ? et : e) * 16 + (idx & 3) * 4 + (idx >> 2)].hi;
+    }
+    __syncthreads();
+    if (A && tid < 64) plk_v4t_row(s_M[1], s_pair[0][tid >> 2], s_tip[0][tid & 3], s_t[tid]);
+    __syncthreads();
+    if (A) plk_v4t_row(s_M[0], s_t[tid >> 2], s_tip[1][tid & 3], out + (size_t)tid * 4);
+    else plk_v4t_row(s_M[0], s_pair[0][tid >> 4], s_pair[1][tid & 15], out + (size_t)tid * 4);
+    /* the rows that round the table up to whole units: no byte can name them; zero, so that the staged image is defined */
+    const int spare = plk_v4q_units(nchar) * nchar - PLK_V4Q_ROWS;
+    if (tid < spare) for (int i = 0; i < 4; i++) out[(size_t)(PLK_V4Q_ROWS + tid) * 4 + i] = 0.0;
+}
+
 /* flags[n] bit 0: some site's code at node n is not an all-ones definition; bit 1: some code is >= nchar
  * (the kernels index LDS and the tip tables with the codes: an out-of-range code must never reach them); bit 2: some
- * code's definition is not a single 1.0 among zeros (code_trivial[ch]: bit 0 all-ones definition, bit 1 single state) */
+ * code's definition is not a single 1.0 among zeros (code_trivial[ch]: bit 0 all-ones definition, bit 1 single state).
+ * seen[n] (nchar <= 16, else not touched): bit `code` set when some site < S carries that code at node n (four-leaf tables) */
 __global__ void k_node_flags(long S, long Spad, const uint8_t *__restrict__ codes, int nchar,
-                             const int *__restrict__ code_trivial, int *__restrict__ flags)
+                             const int *__restrict__ code_trivial, int *__restrict__ flags, int *__restrict__ seen)
 {
     /* 16 codes per lane and iteration (rows are 1024-byte padded with code 0 beyond S;
      * the tail is masked), grid-stride over the row */
     const int n = blockIdx.y;
     const uint4 *row = reinterpret_cast<const uint4 *>(codes + (size_t)n * Spad);
     const long nvec = (S + 15) / 16;
-    int bad = 0;
+    int bad = 0, mask = 0;
     for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (long)gridDim.x * blockDim.x) {
         const uint4 q = row[v];
         const unsigned wds[4] = {q.x, q.y, q.z, q.w};
@@ -775,11 +853,18 @@ __global__ void k_node_flags(long S, long Spad, const uint8_t *__restrict__ code
         for (int j = 0; j < 16; j++) {
             const long s = v * 16 + j;
             const int ch = (wds[j >> 2] >> ((j & 3) * 8)) & 0xff;
-            if (s < S) { const int ct = ch >= nchar ? 0 : code_trivial[ch]; bad |= ch >= nchar ? 2 : ((ct & 1) ? 0 : 1) | ((ct & 2) ? 0 : 4); }
+            if (s < S) {
+                const int ct = ch >= nchar ? 0 : code_trivial[ch]; bad |= ch >= nchar ? 2 : ((ct & 1) ? 0 : 1) | ((ct & 2) ? 0 : 4);
+                if (ch < 16) mask |= 1 << ch;
+            }
         }
     }
     const int wbad = (__any(bad & 1) ? 1 : 0) | (__any(bad & 2) ? 2 : 0) | (__any(bad & 4) ? 4 : 0);
     if (wbad && (threadIdx.x & 63) == 0) atomicOr(&flags[n], wbad);
+    if (nchar <= 16) {
+        for (int off = 32; off > 0; off >>= 1) mask |= __shfl_xor(mask, off, 64);
+        if (mask && (threadIdx.x & 63) == 0) atomicOr(&seen[n], mask);
+    }
 }
 
 /* ====================================================================== */
@@ -1555,7 +1640,7 @@ extern "C" void plk_destroy(plk_engine *h)
     void *ptrs[] = {h->d_indptr, h->d_indices, h->d_preorder, h->d_Qn, h->d_edge_rates, h->d_cat_rates,
                     h->d_cat_prior, h->d_root_w, h->d_Pdd, h->d_P, h->d_dP, h->d_scratch, h->d_codes,
                     h->d_defs, h->d_B, h->d_w, h->d_ops, h->d_fops, h->d_words, h->d_mat_edge, h->d_edge_slot, h->d_op_edge, h->d_tip_edge, h->d_obs_nodes,
-                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_llstate, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
+                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_quad_lut, h->d_quad_codes, h->d_llstate, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
                     h->d_cp_fops, h->d_cp_ops, h->d_cp_mat_edge, h->d_cp_tip_edge, h->d_cp_obs_nodes, h->d_cp_op_edge, h->d_cp_expo, h->d_cp_flag,
                     h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial, h->d_mixD};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1638,6 +1723,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LL_FOLD: *out = h->info_ll_fold; return PLK_OK;
     case PLK_INFO_LL_PAIRMUL: *out = h->info_ll_pairmul; return PLK_OK;
     case PLK_INFO_LL_TRIPLE: *out = h->info_ll_triple; return PLK_OK;
+    case PLK_INFO_LL_QUAD: *out = h->info_ll_quad; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && h->plan.pair_tables ? h->plan.npairs : 0; return PLK_OK;
     case PLK_INFO_STACK_SLOTS: *out = h->slots_needed; return PLK_OK;
@@ -1755,12 +1841,18 @@ static int run_expm(plk_engine *h, bool post = false, bool need_dP = true)
                        h->d_scratch, use_lds, (const double *)nullptr, 0L, 0, (const int *)nullptr, (double *)nullptr, ep);
     HIPCHK(h, hipGetLastError());
     if (post && pt) {
-        const int ntab = (int)h->fpt.tab_unit.size(), ntri = h->fpt.ntriples;
-        hipLaunchKernelGGL(k_build_tables_pt, dim3(ntab - ntri, C), dim3(64), 0, h->stream,
-                           E, ntab, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
-        if (ntri > 0)
-            hipLaunchKernelGGL(k_build_tables_t, dim3(ntri, C), dim3(64), 0, h->stream,
-                               E, ntab, ntab - ntri, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
+        const int ntab = (int)h->fpt.tab_unit.size(), ntri = h->fpt.ntriples, nquad = h->fpt.nquads;
+        if (nquad > 0) {
+            /* one launch for every table of the list */
+            hipLaunchKernelGGL(k_build_tables_q, dim3(ntab, C), dim3(256), 0, h->stream,
+                               E, ntab, ntab - ntri - nquad, ntab - nquad, h->fpt.units, h->nchar, h->d_tabs, h->d_quad_codes, h->d_Pdd, h->d_defs, h->d_tip);
+        } else {
+            hipLaunchKernelGGL(k_build_tables_pt, dim3(ntab - ntri, C), dim3(64), 0, h->stream,
+                               E, ntab, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
+            if (ntri > 0)
+                hipLaunchKernelGGL(k_build_tables_t, dim3(ntri, C), dim3(64), 0, h->stream,
+                                   E, ntab, ntab - ntri, h->fpt.units, h->nchar, h->d_tabs, h->d_Pdd, h->d_defs, h->d_tip);
+        }
         HIPCHK(h, hipGetLastError());
     }
     h->model_dirty = false;
@@ -1908,15 +2000,18 @@ extern "C" int plk_set_patterns_codes(plk_engine *h, long S, const uint8_t *code
     /* which nodes carry observations that are not all-ones */
     int *d_triv = nullptr, *d_flags = nullptr;
     if ((rc = dev_upload(h, &d_triv, trivial.data(), trivial.size()))) return rc;
-    if ((rc = dev_alloc(h, &d_flags, (size_t)N))) { (void)hipFree(d_triv); return rc; }
-    HIPCHK(h, hipMemset(d_flags, 0, N * sizeof(int)));
+    if ((rc = dev_alloc(h, &d_flags, (size_t)2 * N))) { (void)hipFree(d_triv); return rc; }      /* flags | occurring codes */
+    HIPCHK(h, hipMemset(d_flags, 0, 2 * N * sizeof(int)));
     hipLaunchKernelGGL(k_node_flags, dim3((unsigned)std::min<long>(64, (S + 4095) / 4096), N), dim3(256), 0, h->stream,
-                       S, Spad, h->d_codes, nchar, d_triv, d_flags);
+                       S, Spad, h->d_codes, nchar, d_triv, d_flags, d_flags + N);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    std::vector<int> flags(N);
-    HIPCHK(h, hipMemcpy(flags.data(), d_flags, N * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int> flags(2 * (size_t)N);
+    HIPCHK(h, hipMemcpy(flags.data(), d_flags, 2 * N * sizeof(int), hipMemcpyDeviceToHost));
     (void)hipFree(d_triv); (void)hipFree(d_flags);
+    /* a property of the patterns, like node_has_data: every upload recomputes it, and prog_dirty below makes the formats stale */
+    h->node_codes.clear();
+    if (nchar <= 16) h->node_codes.assign(flags.begin() + N, flags.end());
     h->node_has_data.assign(N, 0);
     h->node_observed.assign(N, 0);
     for (int a = 0; a < N; a++) {
@@ -1947,6 +2042,7 @@ extern "C" int plk_set_patterns_dense(plk_engine *h, long S, const double *B, in
     h->S = S; h->Spad = S; h->pat_mode = 2; h->nchar = 0;
     h->node_has_data.assign(h->N, 1);
     h->node_observed.clear();
+    h->node_codes.clear();
     h->prog_dirty = true;
     return PLK_OK;
 }
@@ -2025,20 +2121,38 @@ static int upload_pair_table_lists(plk_engine *h)
     const PlkFusedPT &f = h->fpt;
     int rc;
     const size_t nrows = f.row_node.size(), ntab = f.tab_unit.size();
-    std::vector<int> rn(3 * nrows, -1);
+    std::vector<int> rn(5 * nrows, -1);
     for (size_t r = 0; r < nrows; r++) {
         rn[r] = f.row_node[r]; rn[nrows + r] = f.row_node2[r];
         if (r < f.row_node3.size()) rn[2 * nrows + r] = f.row_node3[r];
+        if (r < f.row_node4.size()) { rn[3 * nrows + r] = f.row_node4[r]; rn[4 * nrows + r] = f.row_lut[r]; }
     }
     if ((rc = dev_upload(h, &h->d_row_nodes, rn.data(), rn.size()))) return rc;
+    auto kind = [&](size_t t) { return t < f.tab_shape.size() && f.tab_shape[t] ? 2 : t < f.tab_el.size() && f.tab_el[t] >= 0 ? 1 : 0; };
     std::vector<size_t> order;
-    for (int pass = 0; pass < 2; pass++)
-        for (size_t t = 0; t < ntab; t++) if ((t < f.tab_el.size() && f.tab_el[t] >= 0) == (pass == 1)) order.push_back(t);
-    std::vector<int> tabs(6 * ntab, -1);
+    for (int pass = 0; pass < 3; pass++)
+        for (size_t t = 0; t < ntab; t++) if (kind(t) == pass) order.push_back(t);
+    std::vector<int> tabs(10 * ntab, -1);
+    std::vector<int> qcodes;
     for (size_t q = 0; q < ntab; q++) {
         const size_t t = order[q];
         tabs[q] = f.tab_unit[t]; tabs[ntab + q] = f.tab_edge[t]; tabs[2 * ntab + q] = f.tab_eb[t]; tabs[3 * ntab + q] = f.tab_ec[t];
         if (t < f.tab_el.size()) { tabs[4 * ntab + q] = f.tab_ea[t]; tabs[5 * ntab + q] = f.tab_el[t]; }
+        if (t < f.tab_shape.size()) { tabs[6 * ntab + q] = f.tab_shape[t]; tabs[7 * ntab + q] = f.tab_et[t]; tabs[8 * ntab + q] = f.tab_ef[t]; tabs[9 * ntab + q] = f.tab_eg[t]; }
+        if (kind(t) != 2) continue;
+        /* the codes behind the ranks of the table's row (the one row that reads it), in the list's order of four-leaf tables */
+        const int row = t < f.tab_row.size() ? f.tab_row[t] : -1;      /* checked by plk_fused_check_v4q against the look-up that reads the table */
+        if (row < 0 || (size_t)row >= nrows || f.row_lut[row] < 0 || h->node_codes.size() != (size_t)h->N) { h->err = "internal: a four-leaf table without its rank tables"; return PLK_E_ARG; }
+        const int nd[4] = {f.row_node[row], f.row_node2[row], f.row_node3[row], f.row_node4[row]};
+        for (int j = 0; j < 4; j++) {
+            int code_of[4];
+            plk_v4q_rank_codes(h->node_codes[nd[j]], code_of);
+            qcodes.insert(qcodes.end(), code_of, code_of + 4);
+        }
+    }
+    if (f.nquads > 0) {
+        if ((rc = dev_upload(h, &h->d_quad_lut, f.lut.data(), f.lut.size()))) return rc;
+        if ((rc = dev_upload(h, &h->d_quad_codes, qcodes.data(), qcodes.size()))) return rc;
     }
     return dev_upload(h, &h->d_tabs, tabs.data(), tabs.size());
 }
@@ -2068,6 +2182,8 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     }
     PlkK4Shape sh = {h->nchar, h->C, h->S, h->num_cus, h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
     std::copy(h->k4_static_lds, h->k4_static_lds + 3, sh.static_lds);
+    const int *node_codes = h->nchar <= 16 && h->node_codes.size() == (size_t)h->N ? h->node_codes.data() : nullptr;
+    sh.node_codes = node_codes;
     const long nunits = (h->S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
     p.k4 = plk_k4_choose(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess, h->fu, h->fpt, h->fv4, h->fv4s);
     if (p.k4.variant == PLK_K4_V4S && dev_reserve(h, &h->d_cstream, &h->cstream_cap, (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT) != PLK_OK) {
@@ -2085,7 +2201,7 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     p.info_variant = c.variant == PLK_K4_CPP ? 3 : c.variant == PLK_K4_ASM ? 1 : c.variant == PLK_K4_ASM_PT ? 5 : 6;
     p.info_form = c.variant == PLK_K4_V4S ? 1 : 0;
     p.fold = false; p.held = c.variant == PLK_K4_V4S && c.held && h->k4_held_ok; p.info_fold = p.held ? 2 : 0;
-    p.triple = PlkV4TPlan(); p.info_triple = 0;
+    p.triple = PlkV4TPlan(); p.info_triple = 0; p.info_quad = 0;
     if (c.variant == PLK_K4_V4S && c.bad.empty()) {
         /* three-leaf tables, and the categories in groups to make room for them: derived from the checked pair-table formats
          * and replayed against them; formats that do not replay are not run -- the checked ones are, and the error text says why.
@@ -2094,17 +2210,26 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
         const bool can_group = c.pair && c.fold && p.held && h->k4_pair_ok && h->k4_groups_ok;
         /* the plan is plk_k4_choose's; the engine only takes the groups back where the instantiation with phases cannot be described */
         PlkV4TPlan tp = c.triple;
-        if (tp.groups > 1 && !can_group) tp = plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1);
-        if (tp.nodes > 0 && tp.groups > 1 &&
+        auto one_group = [&]() { return plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1, po.quad, node_codes); };
+        if (tp.groups > 1 && !can_group) tp = one_group();
+        if (tp.nodes + tp.quads > 0 && tp.groups > 1 &&
             dev_reserve(h, &h->d_llstate, &h->llstate_cap, (size_t)nunits * PLK_V4S_UNIT * 3 / 2) != PLK_OK) {
             /* no room for the partial sums: one group */
             h->err.clear();
             (void)hipGetLastError();
-            tp = plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1);
+            tp = one_group();
         }
-        for (int attempt = 0; attempt < 2 && tp.nodes > 0; attempt++) {
-            plk_fused_v4t_build(h->fpt, h->pg.slots_needed, h->nchar, tp.extra_bytes, true, h->fpt_t);
-            std::string bad = plk_fused_check_v4t(h->N, h->indptr.data(), h->indices.data(), h->fpt, h->fpt_t, h->nchar);
+        for (int attempt = 0; attempt < 2 && tp.nodes + tp.quads > 0; attempt++) {
+            std::string bad;
+            if (tp.quads > 0) {
+                /* four-leaf tables and the three-leaf tables beside them, from the plan's lists */
+                plk_fused_v4q_build(h->fpt, h->pg.slots_needed, h->nchar, node_codes, tp.tri_at, tp.quad_at, tp.quad_shape, true, h->fpt_t);
+                bad = plk_fused_check_v4q(h->N, h->indptr.data(), h->indices.data(), h->fpt, h->fpt_t, h->nchar, node_codes);
+                if (bad.empty() && h->fpt_t.nquads != tp.quads) bad = "v4q program: the builder took another number of four-leaf nodes than the plan";
+            } else {
+                plk_fused_v4t_build(h->fpt, h->pg.slots_needed, h->nchar, tp.extra_bytes, true, h->fpt_t);
+                bad = plk_fused_check_v4t(h->N, h->indptr.data(), h->indices.data(), h->fpt, h->fpt_t, h->nchar);
+            }
             const size_t lds = plk_fused_v4s_lds_bytes(h->fpt_t, h->nchar, tp.Cg);
             if (bad.empty() && h->fpt_t.ntriples != tp.nodes) bad = "v4t program: the builder took another number of nodes than the plan";
             if (bad.empty()) {
@@ -2117,7 +2242,7 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
                 /* the phases exist in the pair-product instantiation only: a rewritten stream that form does not take runs in one group */
                 plk_fused_v4p_build(h->fv4s_t, h->fv4p);
                 if (h->fv4p.words.empty() || !plk_fused_check_v4p(h->fv4s_t, h->fv4p).empty()) {
-                    tp = plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1);
+                    tp = one_group();
                     continue;
                 }
             }
@@ -2126,7 +2251,8 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
                 p.k4.lds = lds; p.lds = lds;
                 p.triple = tp;
                 p.info_triple = 1 | (long)std::min(tp.groups, 15) << 4 | (long)std::min(tp.nodes, 65535) << 8;
-            } else h->err = "internal: " + bad + " (the stream without three-leaf tables runs)";
+                p.info_quad = tp.quads > 0 ? 1 | (long)std::min(tp.quads, 65535) << 8 : 0;
+            } else h->err = "internal: " + bad + (tp.quads > 0 ? " (the stream without four-leaf and three-leaf tables runs)" : " (the stream without three-leaf tables runs)");
             break;
         }
     }
@@ -2192,7 +2318,8 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
         const size_t total = (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT;
         if (total > h->cstream_cap || (total + 255) / 256 > 0x7fffffffu) { h->err = "internal: code stream size"; return PLK_E_ARG; }
         hipLaunchKernelGGL(k_build_code_stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_codes, h->Spad, nunits,
-                           h->d_obs_row, h->fv4s.nobs, h->d_row_nodes, (int)f.row_node.size(), h->nchar, h->fv4s.chunks, h->d_cstream);
+                           h->d_obs_row, h->fv4s.nobs, h->d_row_nodes, (int)f.row_node.size(), h->nchar, h->fv4s.chunks,
+                           f.nquads > 0 ? h->d_quad_lut : (const uint8_t *)nullptr, h->d_cstream);
         HIPCHK(h, hipGetLastError());
     }
     std::vector<int> em(2 * (size_t)h->E, -1);
@@ -2605,7 +2732,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     default: rc = launch_ll_generic(h, p, d_out, want_sum, &npartials); break;
     }
     if (rc) return rc;
-    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_pairmul = p.info_pairmul; h->info_ll_triple = p.info_triple; h->info_ll_exec_flops = p.info_exec_flops;
+    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_pairmul = p.info_pairmul; h->info_ll_triple = p.info_triple; h->info_ll_quad = p.info_quad; h->info_ll_exec_flops = p.info_exec_flops;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->evk[evi][1], h->stream));
     h->evk_pending[evi] = true;

@@ -53,10 +53,11 @@ struct FusedV4SArgs {
 };
 #define PLK_V4S_NO_TERM INT_MIN
 
-/* stream[unit][chunk][lane][half]: one thread per dword; sites past S carry code 0 (the code rows are zero padded) */
+/* stream[unit][chunk][lane][half]: one thread per dword; sites past S carry code 0 (the code rows are zero padded), which a
+ * four-leaf row's rank tables (luts, PlkFusedPT::lut; may be null without such rows) map to rank 0 whether it occurs or not */
 __global__ __launch_bounds__(256) void k_build_code_stream(const uint8_t *__restrict__ codes, long Spad, long nunits,
-                                                           const int *__restrict__ obs_row, int nobs, const int *__restrict__ row_nodes /* [3][nrows] */,
-                                                           int nrows, int nchar, int chunks, unsigned *__restrict__ out)
+                                                           const int *__restrict__ obs_row, int nobs, const int *__restrict__ row_nodes /* [5][nrows] */,
+                                                           int nrows, int nchar, int chunks, const uint8_t *__restrict__ luts, unsigned *__restrict__ out)
 {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)nunits * chunks * PLK_V4S_UNIT;
     if (idx >= total) return;
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void k_build_code_stream(const uint8_t *__rest
     const int chunk = (int)(uc - unit * (size_t)chunks);
     const size_t site = unit * PLK_V4S_UNIT + (size_t)half * 64 + lane;
     out[plk_stream_dword(unit, chunk, lane, half, chunks)] =
-        site < (size_t)Spad ? plk_stream_site_dword(codes, (size_t)Spad, site, obs_row, nobs, row_nodes, nrows, nchar, chunk, 3) : 0u;
+        site < (size_t)Spad ? plk_stream_site_dword(codes, (size_t)Spad, site, obs_row, nobs, row_nodes, nrows, nchar, chunk, 5, luts) : 0u;
 }
 
 /* HELD: the unit's first three chunks (c0 the current dword pair, c1 and c2 the two "in flight") are operands, loaded by

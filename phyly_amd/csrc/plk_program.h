@@ -478,6 +478,20 @@ struct PlkFusedPT {
      * tab_ea the edge above the cherry, tab_el the leaf edge; row_node3 = l in the row of (b, c, l) */
     std::vector<int> row_node3, tab_ea, tab_el;
     int ntriples = 0;
+    /* four-leaf tables (plk_fused_v4q_build only; empty lists = none): a node d with four leaves below it, each of which takes
+     * at most four of the nchar codes, with the edge above d, as 256 rows in ceil(256 / nchar) units.  The row index is in
+     * fixed radix 4 over the leaves' RANKS, ((r1 * 4 + r2) * 4 + r3) * 4 + r4, in the order row_node, row_node2, row_node3,
+     * row_node4 of the row; lut[64 q + 16 j + code] is the rank of `code` at leaf j of four-leaf table q (row_lut[row] = q,
+     * -1 for every other row): the rank of an occurring code among the leaf's occurring codes in increasing order, 0 for a
+     * code that does not occur.
+     *   shape A (PLK_V4Q_A): d = (t, l2), t = (a, l1), a = (b, c): leaves b, c, l1, l2; tab_edge above d, tab_et above t, tab_ea
+     *            above a, tab_eb / tab_ec / tab_el / tab_ef the leaf edges of b, c, l1, l2
+     *   shape B (PLK_V4Q_B): d = (a, a'), a = (b, c), a' = (f, g): leaves b, c, f, g; tab_edge above d, tab_ea above a, tab_et
+     *            above a', tab_eb / tab_ec / tab_ef / tab_eg the leaf edges (tab_el = -1) */
+    std::vector<int> row_node4, row_lut, tab_shape, tab_et, tab_ef, tab_eg;
+    std::vector<int> tab_row;          /* per table: the staged row of the one look-up that reads a four-leaf table (its leaves, its rank tables), else -1 */
+    std::vector<uint8_t> lut;
+    int nquads = 0;
     int first_unit = 0, first_row = 0, second_row = 0;
     /* the program after folding the cherries, op by op (what the words encode; the vector kernel's int4 program is made from it) */
     struct VOp { int code, unit, row, d, edge; };
@@ -573,6 +587,7 @@ static inline void plk_fused_pt_build(int N, const int *ip, const int *ix, const
     fu.tab_unit.clear(); fu.tab_edge.clear(); fu.tab_eb.clear(); fu.tab_ec.clear();
     fu.units = 0; fu.npairs = 0;
     fu.row_node3.clear(); fu.tab_ea.clear(); fu.tab_el.clear(); fu.ntriples = 0;
+    fu.row_node4.clear(); fu.row_lut.clear(); fu.tab_shape.clear(); fu.tab_et.clear(); fu.tab_ef.clear(); fu.tab_eg.clear(); fu.tab_row.clear(); fu.lut.clear(); fu.nquads = 0;
     std::vector<int> row_of(N, -1);
     auto single_row = [&](int node) {
         if (row_of[node] < 0) { row_of[node] = (int)fu.row_node.size(); fu.row_node.push_back(node); fu.row_node2.push_back(-1); }
@@ -861,15 +876,26 @@ PLK_HD static inline size_t plk_stream_byte(size_t unit, int chunk, int lane, in
 }
 /* the dword of chunk `chunk` for one site: the bytes of observations 4 chunk .. 4 chunk + 3, 0 past the last;
  * row_nodes = [nlists][nrows] as uploaded (node | second node of a pair row or -1 | with nlists = 3: third node of a
- * three-leaf row or -1; the byte of (b, c, l) is (code_b * nchar + code_c) * nchar + code_l), codes = [N][Spad] */
+ * three-leaf row or -1; the byte of (b, c, l) is (code_b * nchar + code_c) * nchar + code_l), codes = [N][Spad].
+ * With nlists = 5 and luts: fourth node of a four-leaf row or -1 | index q of the row's rank tables or -1; the byte of such a
+ * row is ((r1 * 4 + r2) * 4 + r3) * 4 + r4 with r_j = luts[64 q + 16 j + code at the row's j-th node] (PlkFusedPT::lut) */
 PLK_HD static inline unsigned plk_stream_site_dword(const uint8_t *codes, size_t Spad, size_t site, const int *obs_row, int nobs,
-                                                    const int *row_nodes, int nrows, int nchar, int chunk, int nlists = 2)
+                                                    const int *row_nodes, int nrows, int nchar, int chunk, int nlists = 2,
+                                                    const uint8_t *luts = nullptr)
 {
     unsigned d = 0;
     for (int b = 0; b < 4; b++) {
         const int n = 4 * chunk + b;
         if (n >= nobs) break;
         const int row = obs_row[n], nb = row_nodes[row], nc = row_nodes[nrows + row];
+        const int q = nlists > 4 && luts ? row_nodes[4 * nrows + row] : -1;
+        if (q >= 0) {
+            const uint8_t *lu = luts + (size_t)q * 64;
+            unsigned code = 0;
+            for (int j = 0; j < 4; j++) code = code * 4u + (lu[16 * j + (codes[(size_t)row_nodes[j * nrows + row] * Spad + site] & 15u)] & 3u);
+            d |= code << (8 * b);
+            continue;
+        }
         unsigned code = codes[(size_t)nb * Spad + site];
         if (nc >= 0) code = code * (unsigned)nchar + codes[(size_t)nc * Spad + site];
         const int nl = nlists > 2 ? row_nodes[2 * nrows + row] : -1;
@@ -889,11 +915,20 @@ struct PlkFusedV4S {
                                           category c reads the image of c % Cg */
 };
 
-/* codes of table t: nchar (one leaf, the pseudo table), nchar^2 (a cherry) or nchar^3 (a three-leaf table) */
+/* codes of table t: nchar (one leaf, the pseudo table), nchar^2 (a cherry), nchar^3 (a three-leaf table) or 256 (a four-leaf table) */
+#define PLK_V4Q_A 1
+#define PLK_V4Q_B 2
+#define PLK_V4Q_ROWS 256
 static inline size_t plk_pt_table_codes(const PlkFusedPT &fu, size_t t, int nchar)
 {
+    if (t < fu.tab_shape.size() && fu.tab_shape[t] != 0) return (size_t)PLK_V4Q_ROWS;
     if (t < fu.tab_el.size() && fu.tab_el[t] >= 0) return (size_t)nchar * nchar * nchar;
     return fu.tab_eb[t] >= 0 ? (size_t)nchar * nchar : (size_t)nchar;
+}
+/* allocation units of nchar rows that table t takes */
+static inline int plk_pt_table_units(const PlkFusedPT &fu, size_t t, int nchar)
+{
+    return (int)((plk_pt_table_codes(fu, t, nchar) + (size_t)nchar - 1) / (size_t)nchar);
 }
 
 static inline size_t plk_fused_v4s_lds_bytes(const PlkFusedPT &fu, int nchar, int C) { return (size_t)C * fu.units * nchar * 32; }
@@ -1752,16 +1787,37 @@ static inline std::string plk_fused_check_v4t(int N, const int *ip, const int *i
  * the option forces the form; the default also asks every wave to walk at least PLK_V4T_MIN_PASSES units per phase: the
  * smallest count at which the form was measured to win (4 at 1.25M sites of BASELINE config 3, - 16 %; 3 at config 2 was
  * even; DESIGN.md section 4, profiles/ll_k4_triple_ab.json).
+ * The phase charge is fitted to the forced runs of that file at 10M sites (26 units per wave): G = 1 with 2 nodes against no
+ * form prices an instruction per unit and category at 0.133 us of the launch; at that price G = 4 with 16 nodes runs 0.096 ms
+ * longer than its instruction count says, G = 2 with 15 nodes does not, so two further phases cost about 0.11 ms = 830
+ * instructions per unit, 415 a phase: 6000 / 26 + 180.  (One site count cannot tell the two constants apart; the fixed one is kept.)
  */
 #define PLK_V4T_NODE_INSTS 44
-#define PLK_V4T_PHASE_UNIT_INSTS 120
+#define PLK_V4T_PHASE_UNIT_INSTS 180
 #define PLK_V4T_PHASE_INSTS 6000
 #define PLK_V4T_MIN_PASSES 4
-struct PlkV4TPlan { int groups = 1, Cg = 0, nodes = 0; size_t extra_bytes = 0; };
+/* quads > 0: the four-leaf form (plk_fused_v4q_build) with the nodes listed, as indices into the checked program's vops:
+ * quad_at / quad_shape the four-leaf nodes, tri_at the `nodes` three-leaf nodes that are not below one of them */
+struct PlkV4TPlan {
+    int groups = 1, Cg = 0, nodes = 0; size_t extra_bytes = 0;
+    int quads = 0;
+    std::vector<int> tri_at, quad_at, quad_shape;
+};
 
-/* triple: 0 forbidden, 1 default, 2 forced;  groups_opt: 0 the model's choice, 1 one group, 2 two groups, -1 a group per category */
-static inline PlkV4TPlan plk_v4t_plan(const PlkFusedPT &fpt, int nchar, int C, long S, int num_cus, size_t static_lds, int triple, int groups_opt)
+static inline PlkV4TPlan plk_v4q_plan(const PlkFusedPT &fpt, int nchar, int C, long S, int num_cus, size_t static_lds, int quad, int groups_opt,
+                                      const int *node_codes);
+
+/* triple: 0 forbidden, 1 default, 2 forced;  groups_opt: 0 the model's choice, 1 one group, 2 two groups, -1 a group per category;
+ * quad: 0 three-leaf tables only, 1 / 2 four-leaf tables too where node_codes (the occurring codes per node) allow them, by
+ * default / forced (plk_v4q_plan; forced implies triple = 2) */
+static inline PlkV4TPlan plk_v4t_plan(const PlkFusedPT &fpt, int nchar, int C, long S, int num_cus, size_t static_lds, int triple, int groups_opt,
+                                      int quad = 0, const int *node_codes = nullptr)
 {
+    if (quad > 0 && triple > 0 && node_codes) {
+        const PlkV4TPlan q = plk_v4q_plan(fpt, nchar, C, S, num_cus, static_lds, quad, groups_opt, node_codes);
+        if (q.quads > 0) return q;
+        if (quad == 2) triple = 2;
+    }
     PlkV4TPlan best;
     best.Cg = C;
     std::vector<int> at;
@@ -1789,6 +1845,450 @@ static inline PlkV4TPlan plk_v4t_plan(const PlkFusedPT &fpt, int nchar, int C, l
                             (double)(groups - 1) * (PLK_V4T_PHASE_INSTS + (double)PLK_V4T_PHASE_UNIT_INSTS * (double)passes);
         if (gain > best_gain) {
             best_gain = gain; best.groups = groups; best.Cg = Cg; best.nodes = (int)t; best.extra_bytes = t * per;
+        }
+    }
+    return best;
+}
+
+/*
+ * FOUR-LEAF TABLES of the streamed form (plk_fused_v4q_build).  Table rows are indexed in radix nchar, the number of
+ * DECLARED character definitions, which stops the three-leaf form at nchar^3 <= 256.  Which codes a leaf really takes is a
+ * property of the patterns (node_codes[n]: bit `code` set when some site < S carries it at node n; k_node_flags, once per
+ * upload).  Where each of the four leaves below a node d takes at most four codes, the codes are re-coded per leaf into
+ * ranks 0 .. 3 and (d, the edge above it) becomes one look-up of a 256-row table.  The shapes, in the checked pair-table
+ * program's ops as plk_program_build emits them (first internal child, leaves, PUSH / further internal child / POPMUL; the
+ * MATVEC of an edge is emitted by the node above it):
+ *   A  d = (t, l2), t = (a, l1), a a cherry:  TIP_SET(pair a) TIP_MUL(l1) MATVEC(e_t) TIP_MUL(l2) MATVEC(e_d)
+ *      absorbs two products; the three-leaf candidate t inside it is not a table of its own
+ *   B  d = (a, a'), both cherries:            TIP_SET(pair a) PUSH(s) TIP_SET(pair a') POPMUL(s) MATVEC(e_d)
+ *      absorbs one product and the stack round trip
+ * directly adjacent: a SCALE in the run, a third child or data at d or t put another op in between and the node stays as it
+ * is.  What follows the last MATVEC stays an op of its own, as for three-leaf tables, so no SCALE moves.  The final MATVEC
+ * makes d a non-root node: only a parent emits it.
+ * Rows: the handlers' fp64 sequence on the handlers' operands (plk_v4t_row), A: t = row(M_et, pair(a), tip(l1)),
+ * row(M_ed, t, tip(l2)); B: row(M_ed, pair(a), pair(a')).  TIP_MUL and POPMUL multiply elementwise with v_mul_f64, which
+ * commutes bit for bit, so the operand order of the products is free.  A row whose index names a rank that does not occur
+ * is the row of rank 0 in that digit (padding sites carry code 0, which maps to rank 0 where it does not occur).
+ */
+struct PlkV4QCand { int at, shape; };
+
+static inline int plk_popcount16(int m) { int n = 0; for (int b = 0; b < 16; b++) n += (m >> b) & 1; return n; }
+/* rank of every code at a leaf with the occurring codes `mask` (at most four): increasing code order, 0 where the code does not occur */
+static inline void plk_v4q_lut(int mask, uint8_t *lut16)
+{
+    int r = 0;
+    for (int code = 0; code < 16; code++) lut16[code] = (uint8_t)(((mask >> code) & 1) && r < 4 ? r++ : 0);
+}
+/* the inverse, for the table builder: the code of rank r; a rank that does not occur names the code of rank 0 */
+static inline void plk_v4q_rank_codes(int mask, int *code4)
+{
+    int r = 0;
+    for (int code = 0; code < 16 && r < 4; code++) if ((mask >> code) & 1) code4[r++] = code;
+    if (r == 0) code4[r++] = 0;
+    for (; r < 4; r++) code4[r] = code4[0];
+}
+/* allocation units of a four-leaf table, and what a table of either shape adds to the image (can be negative) */
+PLK_HD static inline int plk_v4q_units(int nchar) { return (PLK_V4Q_ROWS + nchar - 1) / nchar; }
+static inline long plk_v4q_extra_units(int nchar, int shape) { return (long)plk_v4q_units(nchar) - (shape == PLK_V4Q_A ? nchar + 2 : 2 * nchar); }
+
+/* the nodes that qualify, in program order: index into in.vops of the first of the five ops */
+static inline void plk_v4q_candidates(const PlkFusedPT &in, int nchar, const int *node_codes, std::vector<PlkV4QCand> &at)
+{
+    at.clear();
+    if (!node_codes || nchar < 2 || nchar > 16 || in.ntriples != 0 || in.nquads != 0) return;
+    std::vector<int> table_at(std::max(in.units, 1), -1);
+    for (size_t t = 0; t < in.tab_unit.size(); t++) if (in.tab_unit[t] >= 0 && in.tab_unit[t] < in.units) table_at[in.tab_unit[t]] = (int)t;
+    const std::vector<PlkFusedPT::VOp> &v = in.vops;
+    const int nrows = (int)in.row_node.size();
+    auto leaf_ok = [&](int node) { const int m = node < 0 ? 0 : node_codes[node]; return m > 0 && m < (1 << nchar) && plk_popcount16(m) <= 4; };
+    auto is_pair = [&](const PlkFusedPT::VOp &o) {
+        if (o.unit < 0 || o.unit >= in.units || o.row < 0 || o.row >= nrows) return false;
+        const int t = table_at[o.unit];
+        return t >= 0 && in.tab_eb[t] >= 0 && in.row_node2[o.row] >= 0 && leaf_ok(in.row_node[o.row]) && leaf_ok(in.row_node2[o.row]);
+    };
+    auto is_leaf = [&](const PlkFusedPT::VOp &o) {
+        if (o.unit < 0 || o.unit >= in.units || o.row < 0 || o.row >= nrows) return false;
+        const int t = table_at[o.unit];
+        return t >= 0 && in.tab_eb[t] < 0 && in.tab_edge[t] >= 0 && in.row_node2[o.row] < 0 && leaf_ok(in.row_node[o.row]);
+    };
+    for (size_t i = 0; i + 4 < v.size(); i++) {
+        if (v[i].code != OP_TIP_SET || v[i + 4].code != OP_MATVEC || !is_pair(v[i])) continue;
+        int shape = 0;
+        if (v[i + 1].code == OP_TIP_MUL && v[i + 2].code == OP_MATVEC && v[i + 3].code == OP_TIP_MUL && is_leaf(v[i + 1]) && is_leaf(v[i + 3])) shape = PLK_V4Q_A;
+        else if (v[i + 1].code == OP_PUSH && v[i + 2].code == OP_TIP_SET && v[i + 3].code == OP_POPMUL && v[i + 3].d == v[i + 1].d && is_pair(v[i + 2])) shape = PLK_V4Q_B;
+        if (!shape) continue;
+        at.push_back(PlkV4QCand{(int)i, shape});
+        i += 4;
+    }
+}
+
+/* in: a pair-table program plk_fused_check_pt has accepted.  quad_at / quad_shape: the four-leaf nodes to take (entries that
+ * plk_v4q_candidates does not name are ignored), tri_at: the three-leaf nodes (plk_v4t_candidates; one inside a taken
+ * shape-A node is ignored), all ascending.  out.nquads == 0 && out.ntriples == 0: out is a copy of in. */
+static inline void plk_fused_v4q_build(const PlkFusedPT &in, int slots_needed, int nchar, const int *node_codes, const std::vector<int> &tri_at,
+                                       const std::vector<int> &quad_at, const std::vector<int> &quad_shape, bool fuse_set, PlkFusedPT &out)
+{
+    typedef PlkFusedPT::VOp VOp;
+    const std::vector<VOp> &v = in.vops;
+    std::vector<PlkV4QCand> qc;
+    std::vector<int> tc;
+    plk_v4q_candidates(in, nchar, node_codes, qc);
+    plk_v4t_candidates(in, nchar, tc);
+    std::vector<char> kind(v.size(), 0);                  /* 1: A, 2: B, 3: three-leaf */
+    for (size_t q = 0; q < quad_at.size() && q < quad_shape.size(); q++)
+        for (const PlkV4QCand &c : qc) if (c.at == quad_at[q] && c.shape == quad_shape[q]) kind[c.at] = (char)c.shape;
+    for (int a : tri_at) if (std::find(tc.begin(), tc.end(), a) != tc.end() && !kind[a]) kind[a] = 3;
+    PlkFusedPT o;
+    const int ntab = (int)in.tab_unit.size(), nrows = (int)in.row_node.size(), U4 = plk_v4q_units(std::max(nchar, 1));
+    std::vector<int> table_at(std::max(in.units, 1), -1), new_unit(ntab, -1), new_row(nrows, -1);
+    for (int t = 0; t < ntab; t++) table_at[in.tab_unit[t]] = t;
+    auto table = [&](int edge, int eb, int ec, int ea, int el, int shape, int et, int ef, int eg, int nunits) {
+        o.tab_unit.push_back(o.units); o.tab_edge.push_back(edge); o.tab_eb.push_back(eb); o.tab_ec.push_back(ec);
+        o.tab_ea.push_back(ea); o.tab_el.push_back(el);
+        o.tab_shape.push_back(shape); o.tab_et.push_back(et); o.tab_ef.push_back(ef); o.tab_eg.push_back(eg); o.tab_row.push_back(-1);
+        const int u = o.units; o.units += nunits; return u;
+    };
+    auto row = [&](int n1, int n2, int n3, int n4, int q) {
+        o.row_node.push_back(n1); o.row_node2.push_back(n2); o.row_node3.push_back(n3); o.row_node4.push_back(n4); o.row_lut.push_back(q);
+        return (int)o.row_node.size() - 1;
+    };
+    auto quad_row = [&](int n1, int n2, int n3, int n4) {
+        const int q = o.nquads++, nd[4] = {n1, n2, n3, n4};
+        o.lut.resize((size_t)64 * o.nquads);
+        for (int j = 0; j < 4; j++) plk_v4q_lut(node_codes[nd[j]], &o.lut[(size_t)64 * q + 16 * j]);
+        return row(n1, n2, n3, n4, q);
+    };
+    bool pseudo = false;
+    for (size_t i = 0; i < v.size(); i++) {
+        if (kind[i] == PLK_V4Q_A) {
+            const int tp = table_at[v[i].unit], t1 = table_at[v[i + 1].unit], t2 = table_at[v[i + 3].unit], rp = v[i].row;
+            const int u = table(v[i + 4].edge, in.tab_eb[tp], in.tab_ec[tp], in.tab_edge[tp], in.tab_edge[t1], PLK_V4Q_A, v[i + 2].edge, in.tab_edge[t2], -1, U4);
+            o.vops.push_back(VOp{OP_TIP_SET, u, quad_row(in.row_node[rp], in.row_node2[rp], in.row_node[v[i + 1].row], in.row_node[v[i + 3].row]), 0, -1});
+            o.tab_row.back() = o.vops.back().row;
+            i += 4;
+            continue;
+        }
+        if (kind[i] == PLK_V4Q_B) {
+            const int tp = table_at[v[i].unit], tq = table_at[v[i + 2].unit], rp = v[i].row, rq = v[i + 2].row;
+            const int u = table(v[i + 4].edge, in.tab_eb[tp], in.tab_ec[tp], in.tab_edge[tp], -1, PLK_V4Q_B, in.tab_edge[tq], in.tab_eb[tq], in.tab_ec[tq], U4);
+            o.vops.push_back(VOp{OP_TIP_SET, u, quad_row(in.row_node[rp], in.row_node2[rp], in.row_node[rq], in.row_node2[rq]), 0, -1});
+            o.tab_row.back() = o.vops.back().row;
+            i += 4;
+            continue;
+        }
+        if (kind[i] == 3) {
+            const int tp = table_at[v[i].unit], tl = table_at[v[i + 1].unit], rp = v[i].row, rl = v[i + 1].row;
+            const int u = table(v[i + 2].edge, in.tab_eb[tp], in.tab_ec[tp], in.tab_edge[tp], in.tab_edge[tl], 0, -1, -1, -1, nchar * nchar);
+            o.vops.push_back(VOp{OP_TIP_SET, u, row(in.row_node[rp], in.row_node2[rp], in.row_node[rl], -1, -1), 0, -1});
+            o.ntriples++;
+            i += 2;
+            continue;
+        }
+        VOp w = v[i];
+        if (w.code == OP_TIP_SET || w.code == OP_TIP_MUL) {
+            const int t = table_at[w.unit];
+            if (new_unit[t] < 0) {
+                new_unit[t] = table(in.tab_edge[t], in.tab_eb[t], in.tab_ec[t], -1, -1, 0, -1, -1, -1, in.tab_eb[t] >= 0 ? nchar : 1);
+                if (in.tab_eb[t] >= 0) o.npairs++;
+                if (in.tab_edge[t] < 0) pseudo = true;
+            }
+            if (new_row[w.row] < 0) new_row[w.row] = row(in.row_node[w.row], in.row_node2[w.row], -1, -1, -1);
+            w.unit = new_unit[t]; w.row = new_row[w.row];
+        } else if (w.code == OP_MATVEC) o.mat_edge.push_back(w.edge);
+        o.vops.push_back(w);
+    }
+    if (o.nquads == 0 && o.ntriples == 0) { out = in; return; }
+    if (!pseudo) table(-1, -1, -1, -1, -1, 0, -1, -1, -1, 1);
+    plk_fused_pt_words(slots_needed, fuse_set, o);
+    out = std::move(o);
+}
+
+/*
+ * plk_fused_check_v4t for formats with four-leaf tables: the words are decoded with their look-up chain into out.vops;
+ * those, with every four-leaf look-up unfolded into its five ops and every three-leaf look-up into its three, must be
+ * in.vops exactly (opcodes, stack slots, SCALE positions, tables of the same edges through rows of the same nodes); the
+ * matrix stream is consumed exactly, the absorbed matrices (two per shape A, one per shape B, one per three-leaf table)
+ * being the ones missing; every four-leaf table stands for a non-root node of the tree with exactly those children and
+ * leaves; the tables tile the unit range; every rank table is the bijection of its leaf's occurring codes (node_codes)
+ * onto 0 .. n - 1, n <= 4, in increasing order, and 0 elsewhere; unit and row fields fit the op words.
+ */
+static inline std::string plk_fused_check_v4q(int N, const int *ip, const int *ix, const PlkFusedPT &in, const PlkFusedPT &out, int nchar,
+                                              const int *node_codes)
+{
+    typedef PlkFusedPT::VOp VOp;
+    const int ntab = (int)out.tab_unit.size(), nrows = (int)out.row_node.size(), E = N - 1;
+    if (!node_codes || nchar < 2 || nchar > 16) return "v4q program: four-leaf tables need the occurring codes and nchar <= 16";
+    if ((int)out.tab_edge.size() != ntab || (int)out.tab_eb.size() != ntab || (int)out.tab_ec.size() != ntab || (int)out.tab_ea.size() != ntab ||
+        (int)out.tab_el.size() != ntab || (int)out.tab_shape.size() != ntab || (int)out.tab_et.size() != ntab || (int)out.tab_ef.size() != ntab ||
+        (int)out.tab_eg.size() != ntab || (int)out.tab_row.size() != ntab || (int)out.row_node2.size() != nrows || (int)out.row_node3.size() != nrows ||
+        (int)out.row_node4.size() != nrows || (int)out.row_lut.size() != nrows) return "v4q program: table sizes";
+    if (nrows < 1 || out.units < 1 || out.units >= 2048 || nrows >= 65536) return "v4q program: field widths";
+    if (out.nquads < 0 || out.lut.size() != (size_t)64 * out.nquads) return "v4q program: rank tables";
+    auto tkind = [&](int t) { return out.tab_shape[t] != 0 ? 4 : out.tab_el[t] >= 0 ? 3 : out.tab_eb[t] >= 0 ? 2 : 1; };
+    auto rkind = [&](long r) { return out.row_node4[r] >= 0 ? 4 : out.row_node3[r] >= 0 ? 3 : out.row_node2[r] >= 0 ? 2 : 1; };
+    std::vector<int> table_at(out.units, -1), in_table_at(std::max(in.units, 1), -1);
+    int expect = 0, ntri = 0, nquad = 0;
+    for (int t = 0; t < ntab; t++) {
+        if (out.tab_shape[t] != 0 && out.tab_shape[t] != PLK_V4Q_A && out.tab_shape[t] != PLK_V4Q_B) return "v4q program: table shape";
+        if (tkind(t) == 3 && nchar * nchar * nchar > 256) return "v4q program: the combined code must stay a byte";
+        const int nu = plk_pt_table_units(out, (size_t)t, nchar);
+        if (out.tab_unit[t] != expect || expect + nu > out.units) return "v4q program: table layout";
+        table_at[expect] = t;
+        expect += nu;
+        if (tkind(t) == 3) ntri++;
+        if (tkind(t) == 4) nquad++;
+    }
+    if (expect != out.units || ntri != out.ntriples || nquad != out.nquads) return "v4q program: table layout";
+    for (size_t t = 0; t < in.tab_unit.size(); t++) if (in.tab_unit[t] >= 0 && in.tab_unit[t] < in.units) in_table_at[in.tab_unit[t]] = (int)t;
+    /* rows: a four-leaf row names four nodes and a rank table of its own, which is the bijection of the nodes' codes */
+    {
+        std::vector<char> lut_used(std::max(out.nquads, 1), 0);
+        for (int r = 0; r < nrows; r++) {
+            const int q = out.row_lut[r];
+            if ((q >= 0) != (out.row_node4[r] >= 0)) return plk_fmt("v4q program: row %ld and its rank tables", r);
+            if (q < 0) continue;
+            if (q >= out.nquads || lut_used[q]++) return plk_fmt("v4q program: rank tables of row %ld", r);
+            const int nd[4] = {out.row_node[r], out.row_node2[r], out.row_node3[r], out.row_node4[r]};
+            for (int j = 0; j < 4; j++) {
+                if (nd[j] < 0 || nd[j] >= N) return plk_fmt("v4q program: row %ld names a node out of range", r);
+                const int m = node_codes[nd[j]];
+                if (m <= 0 || m >= (1 << nchar) || plk_popcount16(m) > 4) return plk_fmt("v4q program: leaf %ld of row %ld takes more than four codes", j, r);
+                int rank = 0;
+                for (int code = 0; code < 16; code++) {
+                    const int want = ((m >> code) & 1) ? rank++ : 0;
+                    if (out.lut[(size_t)64 * q + 16 * j + code] != want) return plk_fmt("v4q program: rank table of leaf %ld of row %ld at code %ld", j, r, code);
+                }
+            }
+        }
+    }
+    /* the words, decoded: the chain delivers (cur_unit, cur_row) to every observation handler */
+    std::vector<VOp> dec;
+    {
+        if (out.words.size() % 8 != 0 || out.words.size() < 16) return "v4q program: word buffer";
+        auto unit_ok = [&](long u) { return u >= 0 && u < out.units && table_at[u] >= 0; };
+        auto row_ok = [&](long r) { return r >= 0 && r < nrows; };
+        long cur_unit = out.first_unit, cur_row = out.first_row, next_row = out.second_row;
+        if (!unit_ok(cur_unit) || !row_ok(cur_row) || !row_ok(next_row)) return "v4q program: prologue fields";
+        if (rkind(cur_row) > tkind(table_at[cur_unit]) || (rkind(cur_row) == 4) != (tkind(table_at[cur_unit]) == 4)) return "v4q program: prologue fields";
+        bool waited = true, ended = false;
+        for (size_t wi = 0; wi < out.words.size() && !ended; wi++) {
+            const unsigned w = out.words[wi], hidx = w & 31, y = (w >> 5) & 0x7ff, z = w >> 16;
+            auto observe = [&](int code) -> bool {
+                dec.push_back(VOp{code, (int)cur_unit, (int)cur_row, 0, -1});
+                if (!unit_ok(y) || !row_ok(z)) return false;
+                /* a row's largest code must fit the table it indexes; a four-leaf row's byte is a rank index: its own kind only */
+                const int kt = tkind(table_at[y]), kr = rkind(next_row);
+                if (kr > kt || (kr == 4) != (kt == 4)) return false;
+                cur_unit = y; cur_row = next_row; next_row = z;
+                waited = false;
+                return true;
+            };
+            bool ok = true;
+            if (hidx == OP_END) ended = true;
+            else if (hidx == OP_MATVEC) { dec.push_back(VOp{OP_MATVEC, 0, 0, 0, -1}); waited = true; }
+            else if (hidx == PLK_WORD_MATVEC_TIPMUL) { dec.push_back(VOp{OP_MATVEC, 0, 0, 0, -1}); waited = true; ok = observe(OP_TIP_MUL); }
+            else if (hidx == OP_TIP_SET) ok = observe(OP_TIP_SET);
+            else if (hidx == OP_TIP_MUL) ok = observe(OP_TIP_MUL);
+            else if (hidx == PLK_WORD_TIPMUL_NOWAIT) { if (!waited) return plk_fmt("v4q program: word %ld skips a wait it needs", (long)wi); ok = observe(OP_TIP_MUL); }
+            else if (hidx == OP_SCALE) dec.push_back(VOp{OP_SCALE, 0, 0, 0, -1});
+            else if (hidx >= PLK_WORD_SET_POPMUL && hidx < PLK_WORD_SET_POPMUL + 4) { ok = observe(OP_TIP_SET); dec.push_back(VOp{OP_POPMUL, 0, 0, (int)(hidx & 3), -1}); }
+            else if (hidx >= PLK_WORD_SET_PUSH && hidx < PLK_WORD_SET_PUSH + 4) { ok = observe(OP_TIP_SET); dec.push_back(VOp{OP_PUSH, 0, 0, (int)(hidx & 3), -1}); }
+            else if (hidx >= 24) { dec.push_back(VOp{OP_MATVEC, 0, 0, 0, -1}); waited = true; dec.push_back(VOp{hidx < 28 ? OP_PUSH : OP_POPMUL, 0, 0, (int)(hidx & 3), -1}); }
+            else if (hidx >= 8 && hidx < 12) dec.push_back(VOp{OP_PUSH, 0, 0, (int)(hidx & 7), -1});
+            else if (hidx >= 16 && hidx < 20) dec.push_back(VOp{OP_POPMUL, 0, 0, (int)(hidx & 7), -1});
+            else return plk_fmt("v4q program: word %ld jumps to an empty handler slot", (long)wi);
+            if (!ok) return plk_fmt("v4q program: word %ld requests a table or a row out of range", (long)wi);
+        }
+        if (!ended) return "v4q program: no END";
+    }
+    if (dec.size() != out.vops.size()) return plk_fmt("v4q program: the words execute %ld ops, the rewritten program has %ld", (long)dec.size(), (long)out.vops.size());
+    for (size_t i = 0; i < dec.size(); i++) {
+        const VOp &a = dec[i], &b = out.vops[i];
+        const bool obs = b.code == OP_TIP_SET || b.code == OP_TIP_MUL;
+        if (a.code != b.code || (obs && (a.unit != b.unit || a.row != b.row)) || ((b.code == OP_PUSH || b.code == OP_POPMUL) && a.d != b.d))
+            return plk_fmt("v4q program: decoded op %ld is not the rewritten program's", (long)i);
+    }
+    /* the rewritten ops, unfolded, against the checked ones */
+    size_t j = 0, mi = 0;
+    int absorbed = 0, tri_seen = 0, quad_seen = 0;
+    std::vector<char> used(ntab, 0);
+    auto in_tab = [&](const VOp &b) { return b.unit < 0 || b.unit >= in.units || b.row < 0 || b.row >= (int)in.row_node.size() ? -1 : in_table_at[b.unit]; };
+    auto same_single = [&](const VOp &a, const VOp &b) {       /* a of out, b of in: one look-up of the same table through the same row */
+        const int ti = in_tab(b);
+        if (ti < 0) return false;
+        const int t = table_at[a.unit];
+        return tkind(t) <= 2 && out.tab_edge[t] == in.tab_edge[ti] && out.tab_eb[t] == in.tab_eb[ti] && out.tab_ec[t] == in.tab_ec[ti] &&
+               out.row_node[a.row] == in.row_node[b.row] && out.row_node2[a.row] == in.row_node2[b.row] && out.row_node3[a.row] == -1 && out.row_node4[a.row] == -1;
+    };
+    auto edge_ok = [&](int e) { return e >= 0 && e < E; };
+    auto is_leaf = [&](int n) { return n >= 0 && n < N && ip[n + 1] == ip[n]; };
+    /* a = ix[ea] is a cherry of the leaf edges eb, ec */
+    auto cherry = [&](int ea, int eb, int ec) {
+        if (!edge_ok(ea) || !edge_ok(eb) || !edge_ok(ec) || eb == ec) return false;
+        const int a = ix[ea];
+        return ip[a + 1] - ip[a] == 2 && plk_edge_parent(N, ip, eb) == a && plk_edge_parent(N, ip, ec) == a && is_leaf(ix[eb]) && is_leaf(ix[ec]);
+    };
+    for (size_t i = 0; i < out.vops.size(); i++) {
+        const VOp &a = out.vops[i];
+        if (j >= in.vops.size()) return "v4q program: more ops than the checked program";
+        const VOp &b = in.vops[j];
+        if (a.code == OP_TIP_SET || a.code == OP_TIP_MUL) {
+            const int t = table_at[a.unit], kt = tkind(t);
+            if (used[t]++ && out.tab_edge[t] >= 0) return plk_fmt("v4q program: table %ld used twice", (long)t);
+            if (kt <= 2) {
+                if (a.code != b.code || !same_single(a, b)) return plk_fmt("v4q program: look-up %ld is not the checked program's", (long)i);
+                j++;
+                continue;
+            }
+            const int e = out.tab_edge[t], ea = out.tab_ea[t], eb = out.tab_eb[t], ec = out.tab_ec[t];
+            if (a.code != OP_TIP_SET || !edge_ok(e)) return plk_fmt("v4q program: table look-up %ld", (long)i);
+            const int d = ix[e];
+            if (ip[d + 1] - ip[d] != 2 || !cherry(ea, eb, ec) || out.row_node[a.row] != ix[eb] || out.row_node2[a.row] != ix[ec])
+                return plk_fmt("v4q program: table %ld does not stand for a node with two children above a cherry", (long)t);
+            if (kt == 3) {
+                /* a three-leaf look-up: the checked program continues with the cherry's look-up, the leaf's and the MATVEC */
+                if (j + 2 >= in.vops.size()) return plk_fmt("v4q program: three-leaf look-up %ld", (long)i);
+                const VOp &bp = in.vops[j], &bl = in.vops[j + 1], &bm = in.vops[j + 2];
+                if (bp.code != OP_TIP_SET || bl.code != OP_TIP_MUL || bm.code != OP_MATVEC) return plk_fmt("v4q program: three-leaf look-up %ld does not stand for look-up, look-up, MATVEC", (long)i);
+                const int tp = in_tab(bp), tl = in_tab(bl), el = out.tab_el[t];
+                if (tp < 0 || tl < 0 || in.tab_eb[tp] < 0 || in.tab_eb[tl] >= 0 || in.tab_edge[tl] < 0) return plk_fmt("v4q program: three-leaf look-up %ld: not a cherry and a leaf", (long)i);
+                if (eb != in.tab_eb[tp] || ec != in.tab_ec[tp] || ea != in.tab_edge[tp] || el != in.tab_edge[tl] || e != bm.edge)
+                    return plk_fmt("v4q program: three-leaf table %ld holds other edges than the ops it stands for", (long)t);
+                if (out.row_node[a.row] != in.row_node[bp.row] || out.row_node2[a.row] != in.row_node2[bp.row] || out.row_node3[a.row] != in.row_node[bl.row] ||
+                    in.row_node2[bl.row] != -1 || out.row_node4[a.row] != -1) return plk_fmt("v4q program: row of three-leaf look-up %ld", (long)i);
+                if (!edge_ok(el) || plk_edge_parent(N, ip, ea) != d || plk_edge_parent(N, ip, el) != d || ea == el || !is_leaf(ix[el]) || out.row_node3[a.row] != ix[el])
+                    return plk_fmt("v4q program: three-leaf table %ld is not a cherry and a leaf under one node", (long)t);
+                absorbed++; tri_seen++;
+                j += 3;
+                continue;
+            }
+            if (j + 4 >= in.vops.size()) return plk_fmt("v4q program: four-leaf look-up %ld", (long)i);
+            const VOp *bb = &in.vops[j];
+            const int et = out.tab_et[t], ef = out.tab_ef[t];
+            if (out.tab_shape[t] == PLK_V4Q_A) {
+                if (bb[0].code != OP_TIP_SET || bb[1].code != OP_TIP_MUL || bb[2].code != OP_MATVEC || bb[3].code != OP_TIP_MUL || bb[4].code != OP_MATVEC)
+                    return plk_fmt("v4q program: four-leaf look-up %ld does not stand for look-up, look-up, MATVEC, look-up, MATVEC", (long)i);
+                const int tp = in_tab(bb[0]), t1 = in_tab(bb[1]), t2 = in_tab(bb[3]), el = out.tab_el[t];
+                if (tp < 0 || t1 < 0 || t2 < 0 || in.tab_eb[tp] < 0 || in.tab_eb[t1] >= 0 || in.tab_edge[t1] < 0 || in.tab_eb[t2] >= 0 || in.tab_edge[t2] < 0)
+                    return plk_fmt("v4q program: four-leaf look-up %ld: not a cherry and two leaves", (long)i);
+                if (eb != in.tab_eb[tp] || ec != in.tab_ec[tp] || ea != in.tab_edge[tp] || el != in.tab_edge[t1] || et != bb[2].edge || ef != in.tab_edge[t2] ||
+                    e != bb[4].edge || out.tab_eg[t] != -1) return plk_fmt("v4q program: four-leaf table %ld holds other edges than the ops it stands for", (long)t);
+                if (out.row_node[a.row] != in.row_node[bb[0].row] || out.row_node2[a.row] != in.row_node2[bb[0].row] || out.row_node3[a.row] != in.row_node[bb[1].row] ||
+                    out.row_node4[a.row] != in.row_node[bb[3].row] || in.row_node2[bb[1].row] != -1 || in.row_node2[bb[3].row] != -1)
+                    return plk_fmt("v4q program: row of four-leaf look-up %ld", (long)i);
+                /* the tree: d = (t, l2) under e, t = (a, l1) under et */
+                if (!edge_ok(et) || !edge_ok(ef) || !edge_ok(el) || et == ef || plk_edge_parent(N, ip, et) != d || plk_edge_parent(N, ip, ef) != d)
+                    return plk_fmt("v4q program: four-leaf table %ld: children of its node", (long)t);
+                const int tn = ix[et];
+                if (ip[tn + 1] - ip[tn] != 2 || plk_edge_parent(N, ip, ea) != tn || plk_edge_parent(N, ip, el) != tn || ea == el || !is_leaf(ix[el]) || !is_leaf(ix[ef]) ||
+                    out.row_node3[a.row] != ix[el] || out.row_node4[a.row] != ix[ef]) return plk_fmt("v4q program: four-leaf table %ld is not ((cherry, leaf), leaf)", (long)t);
+                absorbed += 2;
+            } else {
+                if (bb[0].code != OP_TIP_SET || bb[1].code != OP_PUSH || bb[2].code != OP_TIP_SET || bb[3].code != OP_POPMUL || bb[4].code != OP_MATVEC || bb[1].d != bb[3].d)
+                    return plk_fmt("v4q program: four-leaf look-up %ld does not stand for look-up, PUSH, look-up, POPMUL, MATVEC", (long)i);
+                const int tp = in_tab(bb[0]), tq = in_tab(bb[2]), eg = out.tab_eg[t];
+                if (tp < 0 || tq < 0 || in.tab_eb[tp] < 0 || in.tab_eb[tq] < 0) return plk_fmt("v4q program: four-leaf look-up %ld: not two cherries", (long)i);
+                if (eb != in.tab_eb[tp] || ec != in.tab_ec[tp] || ea != in.tab_edge[tp] || ef != in.tab_eb[tq] || eg != in.tab_ec[tq] || et != in.tab_edge[tq] ||
+                    e != bb[4].edge || out.tab_el[t] != -1) return plk_fmt("v4q program: four-leaf table %ld holds other edges than the ops it stands for", (long)t);
+                if (out.row_node[a.row] != in.row_node[bb[0].row] || out.row_node2[a.row] != in.row_node2[bb[0].row] || out.row_node3[a.row] != in.row_node[bb[2].row] ||
+                    out.row_node4[a.row] != in.row_node2[bb[2].row]) return plk_fmt("v4q program: row of four-leaf look-up %ld", (long)i);
+                if (!cherry(et, ef, eg) || ea == et || plk_edge_parent(N, ip, ea) != d || plk_edge_parent(N, ip, et) != d ||
+                    out.row_node3[a.row] != ix[ef] || out.row_node4[a.row] != ix[eg]) return plk_fmt("v4q program: four-leaf table %ld is not (cherry, cherry)", (long)t);
+                absorbed += 1;
+            }
+            if (out.tab_row[t] != a.row) return plk_fmt("v4q program: four-leaf table %ld names another row than the look-up that reads it", (long)t);
+            quad_seen++;
+            j += 5;
+            continue;
+        }
+        if (a.code != b.code) return plk_fmt("v4q program: op %ld is not the checked program's", (long)i);
+        if (a.code == OP_MATVEC) {
+            if (mi >= out.mat_edge.size() || out.mat_edge[mi] != b.edge || a.edge != b.edge) return plk_fmt("v4q program: matrix %ld is not the op's edge", (long)mi);
+            mi++;
+        } else if ((a.code == OP_PUSH || a.code == OP_POPMUL) && a.d != b.d) return plk_fmt("v4q program: stack op %ld", (long)i);
+        j++;
+    }
+    if (j != in.vops.size()) return "v4q program: the checked program's ops are not all covered";
+    if (mi != out.mat_edge.size() || out.mat_edge.size() + (size_t)absorbed != in.mat_edge.size()) return "v4q program: matrix stream not consumed exactly";
+    if (tri_seen != out.ntriples || quad_seen != out.nquads) return "v4q program: tables that no op reads";
+    return "";
+}
+
+/*
+ * The plan with four-leaf tables: for every candidate G of plk_v4t_plan the room is filled greedily by gain per unit with
+ *   a three-leaf table                      PLK_V4T_NODE_INSTS      for nchar^2 - nchar - 1 units
+ *   a shape-A table over a taken three-leaf table   + PLK_V4T_NODE_INSTS  for the difference (alone: twice, for 256 / nchar - nchar - 2)
+ *   a shape-B table                         PLK_V4T_NODE_INSTS      for 256 / nchar - 2 nchar units
+ * (tables that shrink the image first), and the G with the largest gain under plk_v4t_plan's phase charge wins.  quad = 1
+ * keeps the PLK_V4T_MIN_PASSES gate of the default, quad = 2 takes the best candidate whatever the model says of it.
+ */
+static inline PlkV4TPlan plk_v4q_plan(const PlkFusedPT &fpt, int nchar, int C, long S, int num_cus, size_t static_lds, int quad, int groups_opt,
+                                      const int *node_codes)
+{
+    PlkV4TPlan best;
+    best.Cg = C;
+    std::vector<PlkV4QCand> qc;
+    std::vector<int> tc;
+    plk_v4q_candidates(fpt, nchar, node_codes, qc);
+    if (quad == 0 || qc.empty() || C < 1 || S < 1) return best;
+    plk_v4t_candidates(fpt, nchar, tc);
+    const long nunits = (S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
+    const long waves = std::min<long>((nunits + 11) / 12, std::max(num_cus, 1)) * 12;
+    const long passes = (nunits + waves - 1) / waves;
+    if (quad == 1 && passes < PLK_V4T_MIN_PASSES) return best;
+    const size_t unit_bytes = (size_t)nchar * 32, image = (size_t)fpt.units * unit_bytes, limit = plk_pt_lds_limit(1024);
+    const long tri_units = (long)nchar * nchar - nchar - 1;
+    struct Item { int kind, at; long gain, cost; double density; };      /* kind: 0 three-leaf, PLK_V4Q_A, PLK_V4Q_B */
+    std::vector<Item> items;
+    auto item = [&](int kind, int at, long gain, long cost) { items.push_back(Item{kind, at, gain, cost, cost <= 0 ? 1e300 : (double)gain / (double)cost}); };
+    for (int a : tc) item(0, a, PLK_V4T_NODE_INSTS, tri_units);
+    for (const PlkV4QCand &c : qc) {
+        const bool over = c.shape == PLK_V4Q_A && std::find(tc.begin(), tc.end(), c.at) != tc.end();
+        if (c.shape == PLK_V4Q_A) item(PLK_V4Q_A, c.at, over ? PLK_V4T_NODE_INSTS : 2 * PLK_V4T_NODE_INSTS, plk_v4q_extra_units(nchar, PLK_V4Q_A) - (over ? tri_units : 0));
+        else item(PLK_V4Q_B, c.at, PLK_V4T_NODE_INSTS, plk_v4q_extra_units(nchar, PLK_V4Q_B));
+    }
+    std::stable_sort(items.begin(), items.end(), [](const Item &x, const Item &y) { return x.density > y.density; });
+    double best_gain = quad == 2 ? -1e300 : 0.0;
+    const int cand[3] = {1, 2, C};
+    for (int q = 0; q < 3; q++) {
+        const int G = cand[q];
+        if (G < 1 || G > C || (q > 0 && G == cand[q - 1]) || (q == 2 && G == 1)) continue;
+        if (groups_opt > 0 && G != std::min(groups_opt, C)) continue;
+        if (groups_opt == -1 && G != C) continue;
+        const int Cg = (C + G - 1) / G, groups = (C + Cg - 1) / Cg;
+        if (static_lds + (size_t)Cg * image > limit) continue;
+        long room = (long)(((limit - static_lds) / (size_t)Cg - image) / unit_bytes), units = fpt.units, insts = 0;
+        std::vector<int> tri, qa, qs;
+        auto fits = [&](long cost) { return cost <= room && units + cost < 2048; };
+        for (const Item &it : items) {
+            if (it.kind == 0) {
+                if (std::find(qa.begin(), qa.end(), it.at) != qa.end() || !fits(it.cost)) continue;
+                tri.push_back(it.at); room -= it.cost; units += it.cost; insts += it.gain;
+            } else if (it.kind == PLK_V4Q_A) {
+                const std::vector<int>::iterator inner = std::find(tri.begin(), tri.end(), it.at);
+                const bool over = std::find(tc.begin(), tc.end(), it.at) != tc.end();
+                /* priced over its three-leaf table: where that one was not taken, the whole table and both products */
+                const long cost = over && inner == tri.end() ? it.cost + tri_units : it.cost, gain = over && inner == tri.end() ? 2 * it.gain : it.gain;
+                if (!fits(cost)) continue;
+                if (inner != tri.end()) tri.erase(inner);
+                qa.push_back(it.at); qs.push_back(PLK_V4Q_A); room -= cost; units += cost; insts += gain;
+            } else {
+                if (!fits(it.cost)) continue;
+                qa.push_back(it.at); qs.push_back(PLK_V4Q_B); room -= it.cost; units += it.cost; insts += it.gain;
+            }
+        }
+        if (tri.empty() && qa.empty()) continue;
+        const double gain = (double)C * (double)insts * (double)passes -
+                            (double)(groups - 1) * (PLK_V4T_PHASE_INSTS + (double)PLK_V4T_PHASE_UNIT_INSTS * (double)passes);
+        if (gain > best_gain) {
+            best_gain = gain; best.groups = groups; best.Cg = Cg; best.nodes = (int)tri.size(); best.quads = (int)qa.size();
+            best.extra_bytes = (size_t)std::max<long>(units - fpt.units, 0) * unit_bytes;
+            std::sort(tri.begin(), tri.end());
+            std::vector<size_t> ord(qa.size());
+            for (size_t k = 0; k < ord.size(); k++) ord[k] = k;
+            std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return qa[x] < qa[y]; });
+            best.tri_at = tri; best.quad_at.clear(); best.quad_shape.clear();
+            for (size_t k : ord) { best.quad_at.push_back(qa[k]); best.quad_shape.push_back(qs[k]); }
         }
     }
     return best;
@@ -1948,13 +2448,16 @@ enum { PLK_K4_LDS_V4S_768 = 0, PLK_K4_LDS_V4_768, PLK_K4_LDS_V4_512 };     /* Pl
  * pair-product form (the folded stream with held chunks on every tree; that form needs both, so + 64 / + 128 / + 256 turn
  * it off as well), + 1024 the three-leaf form of the streamed kernel (plk_fused_v4t_build) wherever it applies, whatever the
  * site count, + 2048 never, + 4096 / + 8192 / both its categories in one group / a group per category / two groups (more
- * than one group needs the pair-product form).  The + bits are for measurements. */
-struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held, pair, triple, groups; };
+ * than one group needs the pair-product form), + 16384 the four-leaf form (plk_fused_v4q_build) wherever it applies, whatever
+ * the site count (it implies + 1024), + 32768 never; + 1024 alone keeps to three-leaf tables, + 2048 forbids both.
+ * The + bits are for measurements. */
+struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held, pair, triple, groups, quad; };
 static inline PlkPairTablesOpt plk_pair_tables_opt(long v)
 {
+    const int quad = (v & (2048 | 32768)) ? 0 : (v & 16384) ? 2 : (v & 1024) ? 0 : 1;
     return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2, (v & (64 | 256)) ? 0 : 1, (v & (64 | 128)) ? 0 : 1,
-            (v & (64 | 128 | 256 | 512)) ? 0 : 1, (v & 2048) ? 0 : (v & 1024) ? 2 : 1,
-            (v & (4096 | 8192)) == (4096 | 8192) ? 2 : (v & 4096) ? 1 : (v & 8192) ? -1 : 0};
+            (v & (64 | 128 | 256 | 512)) ? 0 : 1, (v & 2048) ? 0 : (v & 1024) || quad == 2 ? 2 : 1,
+            (v & (4096 | 8192)) == (4096 | 8192) ? 2 : (v & 4096) ? 1 : (v & 8192) ? -1 : 0, quad};
 }
 
 struct PlkK4Shape {
@@ -1963,6 +2466,7 @@ struct PlkK4Shape {
     int num_cus;
     long pair_tables, fused_asm, sites_per_lane;     /* the option values as set */
     size_t static_lds[3];                            /* of k_ll_fused4_v4s<768>, k_ll_fused4_v4<768>, k_ll_fused4_v4<512> */
+    const int *node_codes = nullptr;                 /* [N] occurring codes per node as bit masks (nchar <= 16), or none: no four-leaf tables */
 };
 
 struct PlkK4Choice {
@@ -2019,7 +2523,7 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
                 /* three-leaf tables: which nodes and how many groups (the phases exist in the pair-product instantiation only);
                  * the formats themselves are derived from fpt and replayed like the fold and the pair products */
                 if (ch.bad.empty())
-                    ch.triple = plk_v4t_plan(fpt, nchar, sh.C, sh.S, sh.num_cus, st, po.triple, ch.pair && ch.fold && ch.held ? po.groups : 1);
+                    ch.triple = plk_v4t_plan(fpt, nchar, sh.C, sh.S, sh.num_cus, st, po.triple, ch.pair && ch.fold && ch.held ? po.groups : 1, po.quad, sh.node_codes);
                 return ch;
             }
         }

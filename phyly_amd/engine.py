@@ -21,6 +21,7 @@ INFO_LL_KERNEL, INFO_STACK_SLOTS, INFO_PROGRAM_OPS, INFO_LL_KERNEL_NS, INFO_LL_T
     INFO_UPDOWN_KERNEL, INFO_CAT_POSTERIOR_KERNEL, INFO_CATEGORIES, INFO_CAT_POSTERIOR_NS, INFO_PAIR_SUMS_KERNEL, INFO_QUERY_NS, INFO_MIXTURE_SENS_KERNEL, INFO_UP4_PATH, INFO_DOWN4_KERNEL, INFO_LL_FORM, INFO_LL_FOLD, INFO_LL_PAIRMUL = range(22)
 INFO_NNI_KERNEL = 22
 INFO_LL_TRIPLE = 23
+INFO_LL_QUAD = 24
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 COEF_PRIOR, COEF_PRIOR_RATE_EDGE, COEF_PRIOR_RATE = 0, 1, 2
 FIT_EM, FIT_LBFGS = 0, 1
