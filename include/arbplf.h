@@ -79,12 +79,28 @@ char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode
  * order of the request, site outermost.  A pair that is no swap, a non-integer or an index out of range is an error; a
  * value that is not finite (likelihood 0 under the swapped tree) is refused as arbplf-ll refuses it. */
 char *arbplf_nni_string(void *userdata, const char *s_in, int *retcode);
+/* Log likelihood of the tree with a new taxon attached to an edge, for every query taxon and every listed edge (the
+ * reference has no such command): placement of reads, stepwise addition, the regraft half of an SPR move, from one pass
+ * over the current tree (plk_place_ll in plk.h) in place of one arbplf-ll per (query, edge).
+ * Input: model_and_data, an optional site_reduction exactly as for arbplf-ll, and
+ *   "placement": {"character_data": [[c_q0, c_q1, ...], ... one row per site ...], "edges": [3, 0, 7], "split": 0.5,
+ *                 "pendant_rate": 0.1}
+ * The query characters index the model's character_definitions (also for a model with character_data_file); a model with
+ * probability_array takes "probability_array": [site][query][state] instead.  "edges" are indices into the document's
+ * `edges`, repeats allowed; omitted: every edge in document order.  "split" in [0, 1] (default 0.5) is the share of the
+ * target edge's rate coefficient above the new node; "pendant_rate" (required, finite, not negative) is the rate
+ * coefficient of the new leaf's edge.  The edge (u -> b) with rate r becomes (u -> m) with rate split r, (m -> b) with
+ * rate (1 - split) r and (m -> query) with rate pendant_rate.
+ * Columns ["site", "query", "edge", "value"], without the site column under site aggregation; rows ordered by site, then
+ * query, then edge as listed.  Sites are compressed to patterns on the columns of the tree and of the queries together.  A
+ * value that is not finite (likelihood 0 under the placement) is refused as arbplf-ll refuses it. */
+char *arbplf_place_string(void *userdata, const char *s_in, int *retcode);
 
 /* Host-only validation of an input document (JSON grammar, model_and_data,
  * reductions) exactly as the corresponding query would perform it, without
  * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
  * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate" | "rate_matrix_deriv" |
- * "mixture_deriv" | "nni" (the swap list is checked by the query itself).  0 = accepted.  Where the document selects at least one site this includes the preparation of the
+ * "mixture_deriv" | "nni" (the swap list is checked by the query itself) | "place" (with its "placement" object).  0 = accepted.  Where the document selects at least one site this includes the preparation of the
  * model on the host (normalised rate matrix, category rates and priors) and the check of its values that every query
  * makes before any device work (plk_check_model_values in plk.h: non-finite or negative values, rate x length x |Qn|
  * beyond 2^40); the diagnostic names the edge in the order of the document's `edges`.  A document that selects no site

@@ -24,7 +24,8 @@
  *                          (src/arbplfmarginal.c:111-264)
  * and add what the reference does not have: plk_cat_posterior (rate-category posteriors), plk_edge_pair_sums and
  * plk_rate_matrix_sens (site-summed outer products per edge; the gradient of the log likelihood in the rate matrix),
- * plk_nni_ll (the log likelihood of every nearest-neighbour interchange of the tree from one down pass).
+ * plk_nni_ll (the log likelihood of every nearest-neighbour interchange of the tree from one down pass),
+ * plk_place_ll (the log likelihood of the tree with a new taxon attached to every edge, for many new taxa at once).
  *
  * Conventions: every function returns 0 on success and a nonzero PLK_E_* code
  * on failure (plk_last_error() gives the text).  The caller owns all buffers
@@ -168,7 +169,7 @@ int plk_set_stream(plk_engine *h, void *hip_stream);
  * where its derivatives are not finite (likelihood 0).
  *
  * Nodes with many factors: plk_deriv, plk_marginal, plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens,
- * plk_mixture_sens, plk_nni_ll, plk_second_order and plk_hess keep one rescaling factor per node.  On a tree with a node that takes
+ * plk_mixture_sens, plk_nni_ll, plk_place_ll, plk_second_order and plk_hess keep one rescaling factor per node.  On a tree with a node that takes
  * more than 32 edge factors at once (33 leaf children, or three children over 16 edges each) they first measure the
  * node products on the device; where one has no entry of at least 2^-969 at some site they return PLK_E_ARG, the
  * diagnostic naming the query and the node, and the engine stays usable.  With ordinary branch lengths nothing is refused.
@@ -331,6 +332,34 @@ int plk_mixture_chain(int mode, int n, const double *rates, const double *prior,
 int plk_nni_swaps(int N, const int *indptr, const int *indices, int *pairs_out /* NULL or [count][2] */);
 int plk_nni_ll(plk_engine *h, int n_swaps, const int *swaps, double *site_out, double *sums_out);
 
+/*
+ * Placements (the reference has no such query): the log likelihood of the current tree with a new taxon attached to an
+ * edge, for every listed edge and every query taxon, from the vectors of ONE down pass over the current tree and one up
+ * pass per 256 (query, edge) rows (plk_place.h).  A placement onto the CSR edge e = (u -> b) with rate coefficient r_e
+ * replaces e by three edges: (u -> m) with rate fl(split r_e), (m -> b) with rate fl(fl(1 - split) r_e) and (m -> q) with
+ * rate pendant_rate; m is a new node without data, q a new leaf with the query's observation.  Every other edge, node and
+ * datum, the root and the root prior stay.  What does not depend on the query is computed once per (edge, category, site)
+ * and shared by every query of that edge in the pass.
+ * q_codes: [n_queries][S] host, character codes into the definitions of plk_set_patterns_codes, for an engine that holds
+ * compact patterns (else NULL); q_dense: [n_queries][k][S] host for an engine that holds dense patterns (else NULL).
+ * edges: [n_edges] CSR edge indices, repeats allowed; NULL = every edge in CSR order, n_edges being E.  A row has the
+ * same bits wherever it stands in whatever list, alone or with others, in one site chunk or several.
+ * site_out: NULL or [n_queries][n_edges][S] host; sums_out: NULL or [n_queries][n_edges][2] double-double sums of
+ * w_s ll'_s, summed in a fixed order; with both NULL the arguments are checked and nothing runs.
+ * Nothing is divided by the likelihood of the current tree.  A placement of likelihood 0 at a site has ll' = -inf there; in the sums it behaves as in plk_ll (weight exactly 0: it adds nothing; otherwise the
+ * sum is not finite).  An all-missing query (a constant observation row) reproduces the log likelihood of the current tree.
+ * PLK_E_ARG, the diagnostic naming the argument: tree, model or patterns not set; neither or both query arrays, or the
+ * form the engine does not hold; a code >= nchar; a dense entry negative or not finite; an edge index out of range; split
+ * outside [0, 1] or not finite; pendant_rate negative or not finite; a rate the transition matrix kernel refuses
+ * (plk_check_model_values; the diagnostic names the edge and the upper part, the lower part or the pendant edge).
+ * Nothing has run then and the engine stays usable.  Preconditions as for plk_deriv (nodes with more than 32 factors: the
+ * same range check and refusal).  The transition matrices of the three new edges live in buffers of the call's own: the
+ * engine's matrices, tables and rates do not change, and the call is invisible to every later query.
+ * PLK_INFO_PLACE_KERNEL, PLK_INFO_DOWN4_KERNEL and PLK_INFO_LAST_QUERY_NS report on the call.
+ */
+int plk_place_ll(plk_engine *h, int n_queries, const uint8_t *q_codes, const double *q_dense, int n_edges, const int *edges,
+                 double split, double pendant_rate, double *site_out, double *sums_out);
+
 /* the scaled Frechet matrices coef_{c,e} * F_{c,e} themselves, [C][E][k][k] host (tests) */
 int plk_get_frechet_matrices(plk_engine *h, const double *L_hi, const double *L_lo, int coef_mode,
                              double *F_out);
@@ -425,7 +454,7 @@ enum {
     PLK_INFO_PAIR_SUMS_KERNEL = 14, /* up pass of the last plk_edge_pair_sums / plk_rate_matrix_sens: 0 = none yet, 1 = the k = 4
                                        kernel (compact codes, at most 4 categories), 2 = generic */
     PLK_INFO_LAST_QUERY_NS = 15,    /* HIP-event time from the first to the last device operation of the last plk_deriv,
-                                       plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens, plk_mixture_sens or plk_nni_ll
+                                       plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens, plk_mixture_sens, plk_nni_ll or plk_place_ll
                                        (0 when it could not be taken); for tools/time_rate_matrix_deriv.py and
                                        tools/time_mixture_deriv.py */
     PLK_INFO_MIXTURE_SENS_KERNEL = 16, /* up pass of the last plk_mixture_sens: 0 = none yet, 1 = the k = 4 kernel (compact
@@ -436,7 +465,7 @@ enum {
                                        product of two table rows), 8 = two-leaf nodes finished inside their parent's visit
                                        (one rate category); 0 when another kernel family ran */
     PLK_INFO_DOWN4_KERNEL = 18,     /* k = 4 down pass of the last query that ran on the k = 4 up/down kernels (deriv, marginal,
-                                       expectations, and the pair-sum, mixture-gradient and swap passes): 4, 8 or 16 = k_down_fused4<D>
+                                       expectations, and the pair-sum, mixture-gradient, swap and placement passes): 4, 8 or 16 = k_down_fused4<D>
                                        with a register stack of that depth, 0 = k_down_store4 (the staged code rows do not fit
                                        the LDS, or the tree needs more than 16 slots) or no such query yet */
     PLK_INFO_LL_FORM = 19,          /* form of the last ll evaluation's k = 4 pair-table kernel: 1 = streamed codes with the tables
@@ -460,13 +489,15 @@ enum {
                                        would qualify, PLK_OPT_PAIR_TABLES + 32768, or + 1024 without + 16384), else bit 0 = it ran
                                        and bits 8-23 = nodes of a category that are look-ups of a four-leaf table.
                                        PLK_INFO_LL_TRIPLE then reports the groups and the three-leaf tables beside them */
-    PLK_INFO_LL_TRIPLE = 23         /* three-leaf tables in the last ll evaluation's streamed kernel: 0 = the form did not run (another
+    PLK_INFO_LL_TRIPLE = 23,        /* three-leaf tables in the last ll evaluation's streamed kernel: 0 = the form did not run (another
                                        kernel, no node that qualifies, too few sites for the default, PLK_OPT_PAIR_TABLES + 2048, or
                                        formats that did not replay), else bit 0 = it ran, bits 4-7 = groups the categories ran in
                                        (phases of the one launch), bits 8-23 = nodes of a category that are look-ups of a
                                        three-leaf table (a cherry, a leaf and the edge above their parent in one row).
                                        PLK_INFO_PAIR_TABLES then counts the cherries that still have a table of their own, and
                                        PLK_INFO_LL_EXEC_FLOPS the stream that ran */
+    PLK_INFO_PLACE_KERNEL = 25      /* up pass of the last plk_place_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
+                                       4 categories), 2 = generic */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
@@ -577,6 +608,10 @@ int plk_group_mixture_sens(plk_group *g, double *prior_out, double *rate_out);
 /* site_out [n_swaps][S] at the global site positions; sums_out [n_swaps][2]: partial sums of the engines added in engine
  * order (long double) */
 int plk_group_nni_ll(plk_group *g, int n_swaps, const int *swaps, double *site_out, double *sums_out);
+/* arguments and outputs as plk_place_ll with S the sites of the group; each engine gets its site block of the query rows;
+ * sums_out: partial sums of the engines added in engine order (long double) */
+int plk_group_place_ll(plk_group *g, int n_queries, const uint8_t *q_codes, const double *q_dense, int n_edges, const int *edges,
+                       double split, double pendant_rate, double *site_out, double *sums_out);
 int plk_group_hess(plk_group *g, double *hess_sums_out);
 int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out);   /* either may be NULL */
 

@@ -124,6 +124,12 @@ def arbplf_nni(s):
     return _call("arbplf_nni", s)
 
 
+def arbplf_place(s):
+    """log likelihood of the tree with each query taxon of "placement" attached to each listed edge (no counterpart in the
+    reference): columns site, query, edge, value; site_reduction as for arbplf_ll"""
+    return _call("arbplf_place", s)
+
+
 def _out_of_scope(name):
     def f(s):
         raise RuntimeError("arbplf likelihood error: %s is outside the MI355X hot path of this build" % name)

@@ -78,6 +78,9 @@ typedef struct {
     long *site_to_u;   /* S entries, -1 when not selected */
     long double *w_site, div_site;  /* per-site aggregation weights (S) */
     plk_group *eng;    /* the engines of this query: one site block per device */
+    /* further per-site bytes that tell patterns apart (the query columns of a placement): [S][xrow_bytes] or NULL */
+    const unsigned char *xrows;
+    size_t xrow_bytes;
 } query;
 
 static void query_init(query *q)
@@ -170,11 +173,14 @@ static int query_prepare(query *q)
             const unsigned char *row = rows + (size_t)s * row_bytes;
             unsigned long long hsh = 1469598103934665603ULL;          /* FNV-1a */
             for (size_t b = 0; b < row_bytes; b++) { hsh ^= row[b]; hsh *= 1099511628211ULL; }
+            const unsigned char *xrow = q->xrows ? q->xrows + (size_t)s * q->xrow_bytes : NULL;
+            for (size_t b = 0; xrow && b < q->xrow_bytes; b++) { hsh ^= xrow[b]; hsh *= 1099511628211ULL; }
             size_t pos = (size_t)hsh & (tsize - 1);
             long found = -1;
             while (table[pos] >= 0) {
                 const long p = table[pos];
-                if (!memcmp(rows + (size_t)q->usites[p] * row_bytes, row, row_bytes)) { found = p; break; }
+                if (!memcmp(rows + (size_t)q->usites[p] * row_bytes, row, row_bytes) &&
+                    (!xrow || !memcmp(q->xrows + (size_t)q->usites[p] * q->xrow_bytes, xrow, q->xrow_bytes))) { found = p; break; }
                 pos = (pos + 1) & (tsize - 1);
             }
             if (found < 0) { found = q->U; table[pos] = found; q->usites[q->U++] = s; }
@@ -257,7 +263,7 @@ static int check_finite(double v, const char *what)
 }
 
 /* _parse of the drivers: kind 0 ll, 1 deriv, 2 marginal, 3 dwell, 4 trans, 5 em-update, 6 the second-order family,
- * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv, 10 mixture-deriv, 11 nni (no counterpart in the reference: its reduction grammar, its table layout)
+ * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv, 10 mixture-deriv, 11 nni, 12 place (no counterpart in the reference: its reduction grammar, its table layout)
  * (src/arbplfll.c:250-288, src/arbplfderiv.c:445-493, src/arbplfmarginal.c:348-405,
  *  src/arbplfdwell.c:507-566, src/arbplftrans.c:553-614, src/arbplfem.c:505-545) */
 static int query_parse(query *q, int kind, const jval *root)
@@ -270,8 +276,9 @@ static int query_parse(query *q, int kind, const jval *root)
     static const char *const all_trans[] = {"model_and_data", "site_reduction", "edge_reduction", "trans_reduction", NULL};
     static const char *const all_catpost[] = {"model_and_data", "site_reduction", "category_reduction", NULL};
     static const char *const all_nni[] = {"model_and_data", "site_reduction", "swaps", NULL};
+    static const char *const all_place[] = {"model_and_data", "site_reduction", "placement", NULL};
     const char *const *allowed = kind == 0 ? all_ll : kind == 1 ? all_deriv : kind == 2 ? all_marg :
-                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : kind == 7 ? all_catpost : kind == 11 ? all_nni : all_ll;
+                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : kind == 7 ? all_catpost : kind == 11 ? all_nni : kind == 12 ? all_place : all_ll;
     if (host_check_keys(root, req, allowed, "input")) return -1;
     if (host_model_parse(&q->m, j_get(root, "model_and_data"))) return -1;
     if (host_reduction_parse(&q->r_site, (int)q->m.S, "site", j_get(root, "site_reduction"))) return -1;
@@ -1122,6 +1129,240 @@ done:
     return rc;
 }
 
+/* ------------------------------------------------------------------ place (kind 12)
+ * The log likelihood of the tree with a new taxon attached to an edge (no counterpart in the reference; include/plk.h:
+ * plk_place_ll).  "placement": {"character_data": [site][query] character indices into the model's
+ * character_definitions (a model with probability_array: "probability_array": [site][query][state]), "edges": user edge
+ * indices (optional: every edge in document order; repeats allowed), "split" (optional, 0.5), "pendant_rate"}.
+ * Columns site, query, edge, value; rows ordered by site, then query, then edge as listed; the site column goes under
+ * site aggregation.  Patterns are compressed on the columns of the tree and of the queries together. */
+typedef struct {
+    int Q, n;              /* queries; listed edges */
+    int *user;             /* [n] edges as listed */
+    double split, pendant;
+    uint8_t *codes;        /* [S][Q], when the model holds codes */
+    double *prob;          /* [S][Q][k] otherwise */
+} place_req;
+
+static void place_clear(place_req *pr)
+{
+    free(pr->user); free(pr->codes); free(pr->prob);
+    memset(pr, 0, sizeof *pr);
+}
+
+/* row c of the model's character definitions: the model's own copy, or the document's where the model kept none */
+static void place_def_row(const host_model *m, const jval *defs, int c, double *out)
+{
+    if (m->defs) { memcpy(out, m->defs + (size_t)c * m->k, (size_t)m->k * sizeof(double)); return; }
+    const jval *row = j_at(defs, c);
+    for (int j = 0; j < m->k; j++) out[j] = j_number(j_at(row, j));
+}
+
+/* the model's observations back in dense form (a probability_array that had been re-expressed as codes) */
+static int place_model_to_dense(host_model *m)
+{
+    const size_t rows = (size_t)m->S * m->N, k = (size_t)m->k;
+    m->prob = malloc((rows * k + 1) * sizeof(double));
+    if (!m->prob) return -1;
+    for (size_t r = 0; r < rows; r++) memcpy(m->prob + r * k, m->defs + (size_t)m->codes8[r] * k, k * sizeof(double));
+    free(m->codes8); m->codes8 = NULL;
+    free(m->defs); m->defs = NULL;
+    m->nchar = 0;
+    return 0;
+}
+
+#define PLACE_FAIL(...) do { fprintf(stderr, __VA_ARGS__); return -1; } while (0)
+
+static int place_parse(place_req *pr, host_model *m, const jval *root)
+{
+    static const char *const req[] = {"pendant_rate", NULL};
+    static const char *const all[] = {"character_data", "probability_array", "edges", "split", "pendant_rate", NULL};
+    const jval *pl = j_get(root, "placement"), *md = j_get(root, "model_and_data");
+    if (!pl) PLACE_FAIL("error: placement is required\n");
+    if (!j_is_object(pl)) PLACE_FAIL("error: placement must be an object\n");
+    if (host_check_keys(pl, req, all, "placement")) return -1;
+    const int k = m->k, E = m->E;
+    const long S = m->S;
+    const int model_pa = j_get(md, "probability_array") && !j_is_null(j_get(md, "probability_array"));
+    const jval *cd = j_get(pl, "character_data"), *pa = j_get(pl, "probability_array");
+    if (cd && pa) PLACE_FAIL("error: placement: give either character_data or probability_array, not both\n");
+    if (model_pa && !pa) PLACE_FAIL("error: placement: the model holds a probability_array, so the queries must come as placement.probability_array\n");
+    if (!model_pa && !cd) PLACE_FAIL("error: placement: the model holds character data, so the queries must come as placement.character_data\n");
+    const jval *qd = cd ? cd : pa;
+    const char *name = cd ? "placement.character_data" : "placement.probability_array";
+    if (!j_is_array(qd)) PLACE_FAIL("error: %s: a list per site with one entry per query is required\n", name);
+    if ((long)j_len(qd) != S) PLACE_FAIL("error: %s: %ld rows, the model has %ld sites\n", name, (long)j_len(qd), S);
+    pr->Q = S > 0 && j_is_array(j_at(qd, 0)) ? (int)j_len(j_at(qd, 0)) : 0;
+    const int Q = pr->Q;
+    for (long s = 0; s < S; s++) {
+        const jval *x = j_at(qd, s);
+        if (!j_is_array(x)) PLACE_FAIL("error: %s: a list per site with one entry per query is required\n", name);
+        if ((int)j_len(x) != Q) PLACE_FAIL("error: %s: rows of unequal length (site %ld lists %d queries, site 0 lists %d)\n", name, s, (int)j_len(x), Q);
+    }
+    const jval *defs = j_get(md, "character_definitions");
+    const int ndefs = cd ? (m->defs ? m->nchar : (int)j_len(defs)) : 0;
+    /* the queries in the form the model's observations have now: codes, or dense rows */
+    pr->prob = malloc(((size_t)S * Q * k + 1) * sizeof(double));
+    if (!pr->prob) return -1;
+    for (long s = 0; s < S; s++)
+        for (int qi = 0; qi < Q; qi++) {
+            const jval *y = j_at(j_at(qd, s), qi);
+            double *row = pr->prob + ((size_t)s * Q + qi) * k;
+            if (cd) {
+                if (!j_is_int(y)) PLACE_FAIL("error: %s: a character index is not an integer\n", name);
+                if (y->u.i < 0 || y->u.i >= ndefs) PLACE_FAIL("error: %s: character index %lld is out of range: the model has %d definitions\n", name, y->u.i, ndefs);
+                place_def_row(m, defs, (int)y->u.i, row);
+            } else {
+                if (!j_is_array(y) || (int)j_len(y) != k) PLACE_FAIL("error: %s: every query needs one row of %d probabilities per site\n", name, k);
+                for (int j = 0; j < k; j++) {
+                    const jval *z = j_at(y, j);
+                    if (!j_is_number(z) || !(j_number(z) >= 0) || !isfinite(j_number(z)))
+                        PLACE_FAIL("error: %s: entries must be finite numbers that are not negative\n", name);
+                    row[j] = j_number(z);
+                }
+            }
+        }
+    if (m->codes8) {
+        /* codes: the character index itself, or for a probability_array the row's place among the definitions the model
+         * derived, which take the rows of the queries too while there is room for them */
+        pr->codes = malloc((size_t)S * Q + 1);
+        if (!pr->codes) return -1;
+        int fits = 1;
+        for (size_t r = 0; fits && r < (size_t)S * Q; r++) {
+            const double *row = pr->prob + r * k;
+            if (cd) { pr->codes[r] = (uint8_t)j_at(j_at(qd, r / Q), r % Q)->u.i; continue; }
+            int found = -1;
+            for (int c = 0; c < m->nchar && found < 0; c++)
+                if (!memcmp(m->defs + (size_t)c * k, row, (size_t)k * sizeof(double))) found = c;
+            /* room for the new row: parse_probability_array (host_model.c) allocates the derived definitions for 256 rows
+             * whatever their number, and only such models come here (cd == NULL) */
+            if (found < 0 && m->nchar < 256) { memcpy(m->defs + (size_t)m->nchar * k, row, (size_t)k * sizeof(double)); found = m->nchar++; }
+            if (found < 0) fits = 0;
+            else pr->codes[r] = (uint8_t)found;
+        }
+        if (fits) { free(pr->prob); pr->prob = NULL; }
+        else {
+            free(pr->codes); pr->codes = NULL;
+            if (place_model_to_dense(m)) return -1;
+        }
+    }
+    /* edges */
+    const jval *ed = j_get(pl, "edges");
+    if (ed && !j_is_array(ed)) PLACE_FAIL("error: placement.edges must be an array of edge indices\n");
+    pr->n = ed ? (int)j_len(ed) : E;
+    pr->user = malloc((size_t)(pr->n + 1) * sizeof(int));
+    if (!pr->user) return -1;
+    for (int i = 0; i < pr->n; i++) {
+        if (!ed) { pr->user[i] = i; continue; }
+        const jval *x = j_at(ed, i);
+        if (!j_is_int(x)) PLACE_FAIL("error: placement.edges: entry %d: edge indices must be integers\n", i);
+        if (x->u.i < 0 || x->u.i >= E) PLACE_FAIL("error: placement.edges: entry %d: edge index %lld is out of range\n", i, x->u.i);
+        pr->user[i] = (int)x->u.i;
+    }
+    const jval *sp = j_get(pl, "split"), *pe = j_get(pl, "pendant_rate");
+    pr->split = 0.5;
+    if (sp) {
+        if (!j_is_number(sp) || !(j_number(sp) >= 0 && j_number(sp) <= 1)) PLACE_FAIL("error: placement.split must be a number in [0, 1]\n");
+        pr->split = j_number(sp);
+    }
+    if (!j_is_number(pe) || !(j_number(pe) >= 0) || !isfinite(j_number(pe))) PLACE_FAIL("error: placement.pendant_rate must be a finite number that is not negative\n");
+    pr->pendant = j_number(pe);
+    return 0;
+}
+
+/* the rates of the new edges against what the transition matrix kernel accepts, naming edges as the document does;
+ * query_k0 has run */
+static int place_k1(const query *q, const place_req *pr)
+{
+    const host_model *m = &q->m;
+    const double *root_w = m->root_mode == HM_ROOT_CUSTOM ? m->root_custom : (m->root_mode == HM_ROOT_EQUILIBRIUM ? q->pi : NULL);
+    const double lower = 1.0 - pr->split;
+    for (int i = 0; i <= pr->n; i++) {
+        const double r_e = i < pr->n ? m->edge_rates_user[pr->user[i]] : 0.0;
+        const double rates[2] = {i < pr->n ? pr->split * r_e : pr->pendant, lower * r_e};
+        for (int j = 0; j < (i < pr->n ? 2 : 1); j++)
+            if (plk_k1_check_values(m->k, q->C, 1, q->Qn, q->Qn_lo, rates + j, q->cat_rates, q->cat_prior, m->root_mode, root_w, NULL, 0)) {
+                if (i == pr->n) fprintf(stderr, "error: placement.pendant_rate %g: rate x length x |Qn| is beyond 2^40, the limit of the transition matrix kernel\n", rates[j]);
+                else fprintf(stderr, "error: placement: the %s part of edge %d (rate %g): rate x length x |Qn| is beyond 2^40, the limit of the transition matrix kernel\n",
+                             j ? "lower" : "upper", pr->user[i], rates[j]);
+                return -1;
+            }
+    }
+    return 0;
+}
+
+static int run_place(const jval *root, jbuf *out)
+{
+    query q;
+    place_req pr;
+    int rc = -1;
+    int *csr = NULL;
+    uint8_t *codes = NULL;
+    double *dense = NULL, *vals = NULL;
+    query_init(&q);
+    memset(&pr, 0, sizeof pr);
+    if (query_parse(&q, 12, root)) goto done;
+    if (place_parse(&pr, &q.m, root)) goto done;
+    const host_model *m = &q.m;
+    const int Q = pr.Q, n = pr.n, k = m->k;
+    /* two sites are one pattern only when they agree on the tree's columns and on every query */
+    q.xrows = pr.codes ? (const unsigned char *)pr.codes : (const unsigned char *)pr.prob;
+    q.xrow_bytes = pr.codes ? (size_t)Q : (size_t)Q * k * sizeof(double);
+    if (query_prepare(&q)) goto done;
+    const int agg = q.r_site.agg_mode != AGG_NONE;
+    const long U = q.U;
+    if (U > 0 && place_k1(&q, &pr)) goto done;
+    csr = malloc((size_t)(n + 1) * sizeof(int));
+    if (!csr) goto done;
+    for (int i = 0; i < n; i++) csr[i] = m->edge_order[pr.user[i]];
+    /* the queries of the evaluated patterns, device layout (site fastest) */
+    if (pr.codes) {
+        codes = malloc((size_t)Q * U + 1);
+        if (!codes) goto done;
+        for (long u = 0; u < U; u++)
+            for (int qi = 0; qi < Q; qi++) codes[(size_t)qi * U + u] = pr.codes[(size_t)q.usites[u] * Q + qi];
+    } else {
+        dense = malloc(((size_t)Q * k * U + 1) * sizeof(double));
+        if (!dense) goto done;
+        for (long u = 0; u < U; u++)
+            for (int qi = 0; qi < Q; qi++)
+                for (int j = 0; j < k; j++) dense[((size_t)qi * k + j) * U + u] = pr.prob[((size_t)q.usites[u] * Q + qi) * k + j];
+    }
+    const size_t rows = (size_t)Q * n;
+    vals = malloc((rows * (agg ? 2 : (size_t)U) + 2) * sizeof(double));
+    if (!vals) goto done;
+    if (U > 0 && rows > 0 && plk_group_place_ll(q.eng, Q, codes, dense, n, csr, pr.split, pr.pendant, agg ? NULL : vals, agg ? vals : NULL)) {
+        fprintf(stderr, "error: %s\n", plk_group_last_error(q.eng));
+        goto done;
+    }
+    jbuf_puts(out, agg ? "{\"columns\": [\"query\", \"edge\", \"value\"], \"data\": ["
+                       : "{\"columns\": [\"site\", \"query\", \"edge\", \"value\"], \"data\": [");
+    int first = 1;
+    for (int si = 0; si < (agg ? 1 : q.r_site.selection_len); si++) {
+        const int s = agg ? 0 : q.r_site.selection[si];
+        for (int qi = 0; qi < Q; qi++)
+            for (int i = 0; i < n; i++) {
+                const size_t r = (size_t)qi * n + i;
+                const double v = agg ? (U > 0 ? clean(((long double)vals[2 * r] + (long double)vals[2 * r + 1]) / q.div_site) : 0.0)
+                                     : clean(vals[r * U + q.site_to_u[s]]);
+                if (check_finite(v, agg ? "the aggregated log likelihood of a placement" : "a site log likelihood of a placement")) goto done;
+                if (!first) jbuf_puts(out, ", ");
+                first = 0;
+                jbuf_puts(out, "[");
+                if (!agg) { jbuf_int(out, s); jbuf_puts(out, ", "); }
+                jbuf_int(out, qi); jbuf_puts(out, ", "); jbuf_int(out, pr.user[i]); jbuf_puts(out, ", ");
+                jbuf_real(out, v); jbuf_puts(out, "]");
+            }
+    }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(csr); free(codes); free(dense); free(vals);
+    place_clear(&pr);
+    query_clear(&q);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ string API */
 static char *string_hom(int (*run)(const jval *, jbuf *), void *userdata, const char *s_in, int *retcode)
 {
@@ -1164,12 +1405,13 @@ char *arbplf_site_rate_string(void *userdata, const char *s_in, int *retcode) { 
 char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_rate_matrix_deriv, userdata, s_in, retcode); }
 char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_mixture_deriv, userdata, s_in, retcode); }
 char *arbplf_nni_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_nni, userdata, s_in, retcode); }
+char *arbplf_place_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_place, userdata, s_in, retcode); }
 
 /* Host-only validation (JSON grammar, model, reductions and, where a site is selected, the prepared model's values
  * against what the transition matrix kernel accepts); no GPU is touched.
  * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta", "newton_update",
- * "cat_posterior", "site_rate", "rate_matrix_deriv", "mixture_deriv" or "nni" (the model and the reductions; the swap
- * list is checked by the query itself).
+ * "cat_posterior", "site_rate", "rate_matrix_deriv", "mixture_deriv", "nni" (the model and the reductions; the swap
+ * list is checked by the query itself) or "place" (with the whole "placement" object and the rates of its new edges).
  * Returns 0 when the input would be accepted. */
 int arbplf_validate_string(const char *what, const char *s_in)
 {
@@ -1178,15 +1420,20 @@ int arbplf_validate_string(const char *what, const char *s_in)
                !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 :
                (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 :
                !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : !strcmp(what, "rate_matrix_deriv") ? 9 :
-               !strcmp(what, "mixture_deriv") ? 10 : !strcmp(what, "nni") ? 11 : -1;
+               !strcmp(what, "mixture_deriv") ? 10 : !strcmp(what, "nni") ? 11 : !strcmp(what, "place") ? 12 : -1;
     if (kind < 0 || !s_in) return -1;
     json_doc *doc = json_doc_parse(s_in, err, sizeof err);
     if (!doc) { fprintf(stderr, "%s\n", err); return -1; }
     query q;
     query_init(&q);
     int rc = query_parse(&q, kind, json_doc_root(doc));
+    place_req pr;
+    memset(&pr, 0, sizeof pr);
+    if (rc == 0 && kind == 12) rc = place_parse(&pr, &q.m, json_doc_root(doc));
     /* as query_prepare: a document that selects no site is answered without preparing its model */
     if (rc == 0 && q.r_site.selection_len > 0) rc = query_k0(&q);
+    if (rc == 0 && kind == 12 && q.r_site.selection_len > 0) rc = place_k1(&q, &pr);
+    place_clear(&pr);
     query_clear(&q);
     json_doc_free(doc);
     return rc;

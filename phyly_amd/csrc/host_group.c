@@ -529,6 +529,74 @@ int plk_group_nni_ll(plk_group *g, int n_swaps, const int *swaps, double *site_o
     return rc;
 }
 
+/* log likelihood of placements: every engine gets its site block of the query rows and returns rows [query][edge][site] of
+ * its block; they are put side by side, the sums added in engine order as for the swaps.  Weak for the same reason. */
+extern int plk_place_ll(plk_engine *h, int n_queries, const uint8_t *q_codes, const double *q_dense, int n_edges, const int *edges,
+                        double split, double pendant_rate, double *site_out, double *sums_out) __attribute__((weak));
+
+typedef struct {
+    int Q, ne; const uint8_t *codes; const double *dense; const int *edges; double split, pendant;
+    double *site, *part; int want_sums;
+} place_ctx;
+
+static int job_place_ll(plk_group *g, int i, void *p)
+{
+    place_ctx *c = p;
+    const long s0 = g->s0[i], ni = g->s0[i + 1] - s0, S = g->S;
+    if (ni == 0) return PLK_OK;                            /* an engine without sites adds nothing */
+    const size_t rows = (size_t)c->Q * c->ne, qrows = c->codes ? (size_t)c->Q : (size_t)c->Q * g->k;
+    double *mine = NULL, *qd = NULL;
+    uint8_t *qc = NULL;
+    int rc = PLK_E_NOMEM;
+    if (c->site && rows > 0 && !(mine = malloc(rows * ni * sizeof(double)))) goto done;
+    if (g->G > 1 && c->codes) {
+        if (!(qc = malloc(qrows * ni + 1))) goto done;
+        for (size_t r = 0; r < qrows; r++) memcpy(qc + r * ni, c->codes + r * S + s0, (size_t)ni);
+    } else if (g->G > 1) {
+        if (!(qd = malloc((qrows * ni + 1) * sizeof(double)))) goto done;
+        for (size_t r = 0; r < qrows; r++) memcpy(qd + r * ni, c->dense + r * S + s0, (size_t)ni * sizeof(double));
+    }
+    rc = plk_place_ll(g->eng[i], c->Q, g->G > 1 ? qc : c->codes, g->G > 1 ? qd : c->dense, c->ne, c->edges, c->split, c->pendant,
+                      mine, c->want_sums ? c->part + (size_t)i * rows * 2 : NULL);
+    if (!rc && mine)
+        for (size_t r = 0; r < rows; r++) memcpy(c->site + r * S + s0, mine + r * ni, (size_t)ni * sizeof(double));
+done:
+    free(mine); free(qc); free(qd);
+    return rc;
+}
+
+int plk_group_place_ll(plk_group *g, int n_queries, const uint8_t *q_codes, const double *q_dense, int n_edges, const int *edges,
+                       double split, double pendant_rate, double *site_out, double *sums_out)
+{
+    if (!g) return PLK_E_ARG;
+    if (!plk_place_ll) return fail(g, PLK_E_UNSUPPORTED, "plk_group: the engine has no plk_place_ll");
+    if (!g->have_patterns) return fail(g, PLK_E_ARG, "plk_group: tree, model and patterns must be set");
+    if (n_queries < 0 || n_edges < 0) return fail(g, PLK_E_ARG, "plk_group_place_ll: n_queries or n_edges is negative");
+    if ((q_codes != NULL) == (q_dense != NULL)) return fail(g, PLK_E_ARG, "plk_group_place_ll: exactly one of q_codes and q_dense must be given");
+    const size_t rows = (size_t)n_queries * n_edges;
+    place_ctx c = {n_queries, n_edges, q_codes, q_dense, edges, split, pendant_rate, site_out, NULL, sums_out != NULL};
+    c.part = calloc((size_t)g->G * rows * 2 + 2, sizeof(double));
+    if (!c.part) return fail(g, PLK_E_NOMEM, "plk_group: out of host memory");
+    int rc = for_each(g, job_place_ll, &c, 1);
+    if (!rc && sums_out) {
+        for (size_t r = 0; r < rows; r++) {
+            double *dst = sums_out + 2 * r;
+            if (g->G == 1) { dst[0] = c.part[2 * r]; dst[1] = c.part[2 * r + 1]; continue; }   /* one engine: its sums, bit for bit */
+            long double acc = 0;
+            for (int i = 0; i < g->G; i++) {
+                if (g->s0[i + 1] == g->s0[i]) continue;
+                acc += (long double)c.part[((size_t)i * rows + r) * 2];
+                acc += (long double)c.part[((size_t)i * rows + r) * 2 + 1];
+            }
+            const double hi = (double)acc;
+            dst[0] = hi;
+            dst[1] = (double)(acc - (long double)hi);
+        }
+    }
+    free(c.part);
+    return rc;
+}
+
 int plk_group_hess(plk_group *g, double *hess_sums_out)
 {
     if (!g || !hess_sums_out) return PLK_E_ARG;

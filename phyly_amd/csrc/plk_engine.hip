@@ -207,6 +207,12 @@ struct plk_engine {
     double *d_mixD = nullptr; size_t mixd_cap = 0;   /* plk_mixture_sens: its direction matrices t_e Qn P[c][e] (the query's own; d_dP is not touched) */
     long info_mixture_sens_kernel = 0;
     long info_nni_kernel = 0;                        /* PLK_INFO_NNI_KERNEL: up pass of the last plk_nni_ll */
+    /* plk_place_ll: the call's own transition matrices (upper and lower part of every target edge, the pendant edge),
+     * their rates, padded streams and pendant tables, and the query observations; the engine's P, dP and tables stay */
+    dd *d_plPdd = nullptr; double *d_plP = nullptr, *d_plrates = nullptr, *d_plstream = nullptr, *d_plT = nullptr, *d_pldense = nullptr;
+    uint8_t *d_plcodes = nullptr;
+    size_t plpdd_cap = 0, plp_cap = 0, plrates_cap = 0, plstream_cap = 0, plt_cap = 0, pldense_cap = 0, plcodes_cap = 0;
+    long info_place_kernel = 0;                      /* PLK_INFO_PLACE_KERNEL: up pass of the last plk_place_ll */
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
@@ -1546,6 +1552,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_up(UpArgs a)
 #include "plk_pairsums.h"
 #include "plk_mixsens.h"
 #include "plk_nni.h"
+#include "plk_place.h"
 
 /* padded edge-indexed matrix streams for the up/down kernels:
  * mode 0: out[j*K+i] = M[i][j] (transposed), mode 1: out[i*K+j] = M[i][j] */
@@ -1642,7 +1649,8 @@ extern "C" void plk_destroy(plk_engine *h)
                     h->d_defs, h->d_B, h->d_w, h->d_ops, h->d_fops, h->d_words, h->d_mat_edge, h->d_edge_slot, h->d_op_edge, h->d_tip_edge, h->d_obs_nodes,
                     h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_quad_lut, h->d_quad_codes, h->d_llstate, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
                     h->d_cp_fops, h->d_cp_ops, h->d_cp_mat_edge, h->d_cp_tip_edge, h->d_cp_obs_nodes, h->d_cp_op_edge, h->d_cp_expo, h->d_cp_flag,
-                    h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial, h->d_mixD};
+                    h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial, h->d_mixD,
+                    h->d_plPdd, h->d_plP, h->d_plrates, h->d_plstream, h->d_plT, h->d_pldense, h->d_plcodes};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1716,6 +1724,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LAST_QUERY_NS: *out = h->info_query_ns; return PLK_OK;
     case PLK_INFO_MIXTURE_SENS_KERNEL: *out = h->info_mixture_sens_kernel; return PLK_OK;
     case PLK_INFO_NNI_KERNEL: *out = h->info_nni_kernel; return PLK_OK;
+    case PLK_INFO_PLACE_KERNEL: *out = h->info_place_kernel; return PLK_OK;
     case PLK_INFO_UP4_PATH: *out = h->info_up4_path; return PLK_OK;
     case PLK_INFO_DOWN4_KERNEL: *out = h->info_down4_kernel; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
@@ -2823,6 +2832,18 @@ static void launch_nni(plk_engine *h, const UpArgs &a, const NniOut &o, unsigned
     hipLaunchKernelGGL((k_up_nni<K, false>), dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, o);
 }
 
+/* ... the same for the placement pass (plk_place.h): the forward vectors are those of the swap pass */
+template <int K>
+static void launch_place(plk_engine *h, const UpArgs &a, const PlaceOut &o, unsigned grid, bool down)
+{
+    if (down) {
+        NniOut none = {};
+        hipLaunchKernelGGL(k_down_store<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a);
+        hipLaunchKernelGGL((k_up_nni<K, true>), dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, none);
+    }
+    hipLaunchKernelGGL(k_up_place<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, o);
+}
+
 /* ... and the mixture-gradient up pass on the same grid (plk_mixsens.h) */
 template <int K>
 static void launch_mixsens(plk_engine *h, const UpArgs &a, const MixSensOut &o, unsigned grid, unsigned pgrid)
@@ -3311,6 +3332,91 @@ static int nni_group_out(plk_engine *h, NniReq *q, int g0, int ng, long n, long 
     return PLK_OK;
 }
 
+/* plk_place_ll asks the same drivers for the placement pass (plk_place.h).  Rows are counted edge-major, t = ei Q + q
+ * for position ei of the edge list and query q, so that a pass of PLACE_MAX_ROWS rows names as few edges as it can; the
+ * caller's order [Q][n_edges] is restored when rows leave (place_group_out, plk_place_ll) */
+struct PlaceReq {
+    int Q = 0, ne = 0;
+    const int *edges = nullptr;        /* [ne] validated CSR edges */
+    std::vector<int> slot;             /* [ne] index of the edge among the distinct target edges of the call */
+    std::vector<double> rates;         /* [2 distinct + 1]: upper part, lower part of every distinct edge; the pendant edge */
+    bool compact = false;              /* the queries are codes (d_plcodes) or dense rows (d_pldense) */
+    double *site_out = nullptr;        /* null or [Q][ne][S] host */
+    std::vector<long double> acc;      /* [ne][Q] weighted site sums (filled when want_sums) */
+    bool want_sums = false;
+    std::vector<int> par, pos;         /* upper node of every CSR edge; preorder position of every node */
+    std::vector<double> stage;         /* per-site rows of one pass on their way to site_out */
+    long total() const { return (long)ne * Q; }
+};
+
+/* the call's transition matrices: one more launch of K1 over the call's rates into the call's buffers (no dP) */
+static int place_matrices(plk_engine *h, const PlaceReq &q)
+{
+    const int k = h->k, C = h->C, EQ = (int)q.rates.size();
+    const size_t kk = (size_t)k * k, nmat = (size_t)C * EQ * kk;
+    int rc;
+    if ((rc = dev_reserve(h, &h->d_plPdd, &h->plpdd_cap, nmat)) || (rc = dev_reserve(h, &h->d_plP, &h->plp_cap, nmat)) ||
+        (rc = dev_reserve(h, &h->d_plrates, &h->plrates_cap, (size_t)EQ))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_plrates, q.rates.data(), (size_t)EQ * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const int threads = kk >= 1024 ? 1024 : (kk >= 256 ? 256 : 64);
+    int use_lds;
+    const size_t lds_bytes = expm_lds_bytes((size_t)k, threads, &use_lds);
+    if (!use_lds) { if ((rc = dev_reserve(h, &h->d_scratch, &h->scratch_cap, (size_t)C * std::max(EQ, h->E) * EXPM_BUFFERS * kk))) return rc; }
+    ExpmPost ep = {};
+    ep.skip_dP = 1;
+    hipLaunchKernelGGL(k_expm_dd<false>, dim3(C * EQ), dim3(threads), lds_bytes, h->stream,
+                       k, EQ, h->d_Qn, h->d_plrates, h->d_cat_rates, h->d_plPdd, h->d_plP, (double *)nullptr,
+                       h->d_scratch, use_lds, (const double *)nullptr, 0L, 0, (const int *)nullptr, (double *)nullptr, ep);
+    HIPCHK(h, hipGetLastError());
+    return PLK_OK;
+}
+
+/* records of plk_place.h for every pass of the call; they go to the device with the call's other integer tables */
+struct PlaceGroups {
+    std::vector<size_t> off;           /* offset of the pass's records in the pack */
+    std::vector<int> nrec;
+    int rows = 0;                      /* rows of the plane: the largest pass */
+    void put(const PlaceReq &q, IntPack &pack)
+    {
+        struct Rec { int w[PLACE_REC]; };
+        for (long g0 = 0; g0 < q.total(); g0 += PLACE_MAX_ROWS) {
+            const long g1 = std::min<long>(g0 + PLACE_MAX_ROWS, q.total());
+            std::vector<Rec> recs;
+            for (long t = g0; t < g1;) {
+                const int ei = (int)(t / q.Q), q0 = (int)(t % q.Q);
+                const int cnt = (int)std::min<long>(q.Q - q0, g1 - t);
+                const int e = q.edges[ei];
+                Rec r = {{q.pos[q.par[e]], e, q.slot[ei], q0, cnt, (int)(t - g0)}};
+                recs.push_back(r);
+                t += cnt;
+            }
+            std::stable_sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) { return x.w[0] < y.w[0]; });
+            std::vector<int> out;
+            for (const Rec &r : recs) out.insert(out.end(), r.w, r.w + PLACE_REC);
+            off.push_back(pack.put(out.data(), out.size()));
+            nrec.push_back((int)recs.size());
+            rows = std::max(rows, (int)(g1 - g0));
+        }
+    }
+};
+
+/* one chunk's outputs of one pass: weighted row sums into acc (edge-major), rows of the plane to their places in site_out */
+static int place_group_out(plk_engine *h, PlaceReq *q, long g0, int ng, long n, long s0, const double *plane)
+{
+    int rc;
+    if (q->want_sums && (rc = wsum_rows(h, ng, n, plane, h->d_w ? h->d_w + s0 : nullptr, q->acc.data() + g0))) return rc;
+    if (q->site_out) {
+        q->stage.resize((size_t)ng * n);
+        HIPCHK(h, hipMemcpyAsync(q->stage.data(), plane, (size_t)ng * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < ng; i++) {
+            const long t = g0 + i, ei = t / q->Q, qi = t % q->Q;
+            std::copy(q->stage.begin() + (size_t)i * n, q->stage.begin() + (size_t)(i + 1) * n, q->site_out + ((size_t)qi * q->ne + ei) * h->S + s0);
+        }
+    }
+    return PLK_OK;
+}
+
 /* workgroups of the pair-sum passes: fixed by the device, so the partial sums never grow with S */
 static unsigned pair_sums_grid(const plk_engine *h, long nbatch) { return (unsigned)std::min<long>(nbatch, 4L * h->num_cus); }
 
@@ -3329,7 +3435,8 @@ static int pair_sums_finish(plk_engine *h, PairSumReq *ps, size_t rows, unsigned
 }
 
 static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
-                       double *site_out, double *sums_out, const double *d_M, int dzero, int nM, PairSumReq *ps = nullptr, NniReq *nni = nullptr)
+                       double *site_out, double *sums_out, const double *d_M, int dzero, int nM, PairSumReq *ps = nullptr, NniReq *nni = nullptr,
+                       PlaceReq *pl = nullptr)
 {
     int rc;
     const int N = h->N, E = h->E, C = h->C;
@@ -3415,7 +3522,7 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
                                                    any_rebuild ? rebuild_tab.data() : nullptr, pair_of.data());
         if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
     }
-    if (!ps && !nni) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
+    if (!ps && !nni && !pl) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
     const size_t ntab = (size_t)C * (ntips + 1) * h->nchar * 4;
     /* all small integer tables of this call in one host block, one upload */
     IntPack pack;
@@ -3430,6 +3537,10 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     const size_t o_rb = any_rebuild ? pack.put(rebuild_tab.data(), rebuild_tab.size()) : 0;
     NniGroups ng4;
     if (nni) ng4.put(h, *nni, true, pack);
+    PlaceGroups pg4;
+    const int pl_tip_edge = pl ? (int)pl->rates.size() - 1 : 0;      /* the pendant matrix, as the one "tip edge" of its table */
+    const size_t o_pte = pl ? pack.put(&pl_tip_edge, 1) : 0;
+    if (pl) pg4.put(*pl, pack);
     const size_t nptab = (size_t)C * npairs4 * h->nchar * h->nchar * 4;
     if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, ntab * (size_t)(1 + nM) + nptab)) || (rc = pack.upload(h))) return rc;
     int *const d_psflag = pack.flag(h);
@@ -3448,10 +3559,16 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     if (npairs4)       /* pair tables: [C][npairs * nchar units][nchar][4], the ll kernels' builder on a list of pairs only */
         hipLaunchKernelGGL(k_build_tables_pt, dim3(npairs4, C), dim3(64), 0, h->stream,
                            E, npairs4, npairs4 * h->nchar, h->nchar, d_ptabs, h->d_Pdd, h->d_defs, d_ptab4);
+    if (pl) {
+        /* pendant tables [C][nchar][4] = D defs[code], built as the tip tables are (double-double, constant rows unchanged) */
+        if ((rc = dev_reserve(h, &h->d_plT, &h->plt_cap, (size_t)C * h->nchar * 4))) return rc;
+        hipLaunchKernelGGL(k_build_tip, dim3(1, C), dim3(64), 0, h->stream,
+                           (int)pl->rates.size(), 1, h->nchar, b + o_pte, h->d_plPdd, h->d_defs, h->d_plT);
+    }
     if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
 
     const bool msum_only = marginal_sums_only(deriv, marg, site_out, sums_out);      /* per-wave sums instead of the N x 4 planes */
-    const size_t per_site = ((size_t)(2 * (size_t)nin) * C * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? ER : 0) + (marg && !msum_only ? (size_t)N * 4 : 0) + (size_t)ng4.rows) * sizeof(double);
+    const size_t per_site = ((size_t)(2 * (size_t)nin) * C * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? ER : 0) + (marg && !msum_only ? (size_t)N * 4 : 0) + (size_t)ng4.rows + (size_t)pg4.rows) * sizeof(double);
     long chunk;
     if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0), UD4_BLOCK, false, &chunk))) return rc;
     const size_t mvs_doubles = msum_only ? (size_t)N * 4 * (size_t)((chunk + UD4_BLOCK - 1) / UD4_BLOCK) * (UD4_BLOCK / 64) : 0;   /* per-wave marginal sums */
@@ -3507,6 +3624,19 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
                 if (hipGetLastError() != hipSuccess) { h->err = "plk_nni_ll: kernel launch failed"; return PLK_E_DEVICE; }
                 const int g0 = (int)gi * NNI_MAX_ROWS;
                 if ((rc = nni_group_out(h, nni, g0, std::min(NNI_MAX_ROWS, nni->n - g0), n, s0, p))) return rc;
+            }
+            continue;
+        }
+        if (pl) {
+            /* one up pass per PLACE_MAX_ROWS rows over the vectors of this chunk; the first stores the forward vectors */
+            for (size_t gi = 0; gi < pg4.off.size(); gi++) {
+                PlaceOut po = {};
+                po.rec = b + pg4.off[gi]; po.nrec = pg4.nrec[gi]; po.store_fn = gi == 0 ? 1 : 0; po.EQ = (int)pl->rates.size();
+                po.QP = h->d_plP; po.T = h->d_plT; po.q_codes = h->d_plcodes; po.plane = p;
+                hipLaunchKernelGGL(k_up4_place, dim3(grid), dim3(UD4_BLOCK), (size_t)C * h->nchar * 4 * sizeof(double), h->stream, a, po);
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_place_ll: kernel launch failed"; return PLK_E_DEVICE; }
+                const long g0 = (long)gi * PLACE_MAX_ROWS;
+                if ((rc = place_group_out(h, pl, g0, (int)std::min<long>(PLACE_MAX_ROWS, pl->total() - g0), n, s0, p))) return rc;
             }
             continue;
         }
@@ -3676,17 +3806,23 @@ static bool use_updown4(const plk_engine *h)
  * (dzero = 1: rows sum to zero), scaled Frechet matrices for dwell / trans / em-update (dzero = 0) */
 static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
                       double *site_out, double *sums_out, const double *d_M_in = nullptr, int dzero = 1, int nM = 1, PairSumReq *ps = nullptr,
-                      NniReq *nni = nullptr)
+                      NniReq *nni = nullptr, PlaceReq *pl = nullptr)
 {
     if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_deriv/plk_marginal: tree, model and patterns must be set"; return PLK_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
-    if ((rc = check_stored_range(h, nni ? "plk_nni_ll" : ps ? (ps->mix_D ? "plk_mixture_sens" : "plk_edge_pair_sums/plk_rate_matrix_sens")
+    if ((rc = check_stored_range(h, pl ? "plk_place_ll" : nni ? "plk_nni_ll" : ps ? (ps->mix_D ? "plk_mixture_sens" : "plk_edge_pair_sums/plk_rate_matrix_sens")
                                        : marg ? (deriv ? "plk_deriv/plk_marginal" : "plk_marginal") : d_M_in ? "plk_edge_expect" : "plk_deriv"))) return rc;
-    if (!d_M_in && !ps && !nni && (rc = ensure_dP(h))) return rc;
+    if (!d_M_in && !ps && !nni && !pl && (rc = ensure_dP(h))) return rc;
     const double *d_M = d_M_in ? d_M_in : h->d_dP;
-    if (!ps && !nni) h->info_up4_path = 0;
+    if (!ps && !nni && !pl) h->info_up4_path = 0;
+    if (pl) {
+        /* the k = 4 kernel takes compact codes and at most four categories, as for the swaps */
+        if ((rc = place_matrices(h, *pl))) return rc;
+        if (use_updown4(h) && h->C <= 4) { h->info_place_kernel = 1; return run_updown4(h, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, pl); }
+        h->info_place_kernel = 2;
+    } else
     if (nni) {
         /* as for the pair sums: the k = 4 kernel takes compact codes and at most four categories */
         if (use_updown4(h) && h->C <= 4) { h->info_nni_kernel = 1; return run_updown4(h, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nni); }
@@ -3702,7 +3838,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     else if (use_mfma(h)) { h->info_updown_kernel = 3; return run_updown_mfma(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
     else if (use_updown4(h)) { h->info_updown_kernel = 1; return run_updown4(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero, nM); }
     if (nM != 1) { h->err = "internal: several edge forms per pass need the k = 4 kernels"; return PLK_E_ARG; }
-    if (!ps && !nni) h->info_updown_kernel = 2;
+    if (!ps && !nni && !pl) h->info_updown_kernel = 2;
     const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
     const long S = h->S;
     /* padded edge-indexed streams in the grow-only matrix buffer; each starts at a multiple of 32 doubles (256 bytes, what
@@ -3713,7 +3849,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     const int bt = K * K >= 256 ? 256 : 64;
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, h->d_P, d_PT);
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 1, h->d_P, d_PN);
-    if (!nni && (!ps || ps->mix_D)) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
+    if (!nni && !pl && (!ps || ps->mix_D)) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
     /* the call's integer tables; of the storage maps the generic kernels take the rescaling slots only */
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
     const PlkStorageMaps sm = storage_maps(h);
@@ -3723,13 +3859,27 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     const size_t o_has = pack.put_has_data(h), o_ns = pack.put(sm.node_scale.data(), (size_t)N);
     NniGroups ngg;
     if (nni) ngg.put(h, *nni, false, pack);
+    PlaceGroups pgg;
+    if (pl) pgg.put(*pl, pack);
     if ((rc = pack.upload(h))) return rc;
+    const int EQ = pl ? (int)pl->rates.size() : 0;
+    const size_t qstrm = ((size_t)C * EQ * K * K + 31) / 32 * 32;
+    if (pl) {
+        /* the call's matrices as padded streams (transposed, plain) and, for compact codes, the pendant tables [C][nchar][K] */
+        if ((rc = dev_reserve(h, &h->d_plstream, &h->plstream_cap, 2 * qstrm)) ||
+            (rc = dev_reserve(h, &h->d_plT, &h->plt_cap, (size_t)C * std::max(h->nchar, 1) * K))) return rc;
+        hipLaunchKernelGGL(k_build_edge_stream, dim3(C * EQ), dim3(bt), 0, h->stream, k, K, 0, h->d_plP, h->d_plstream);
+        hipLaunchKernelGGL(k_build_edge_stream, dim3(C * EQ), dim3(bt), 0, h->stream, k, K, 1, h->d_plP, h->d_plstream + qstrm);
+        if (pl->compact) hipLaunchKernelGGL(k_place_table, dim3(C), dim3(256), 0, h->stream, k, K, EQ, h->nchar, h->d_plstream, h->d_defs, h->d_plT);
+        if (hipGetLastError() != hipSuccess) { h->err = "plk_place_ll: table build failed"; return PLK_E_DEVICE; }
+    }
     const int *pk = h->d_u4pack;
     const int *d_emask = edge_mask ? pk + o_em : nullptr, *d_nmask = node_mask ? pk + o_nm : nullptr, *d_has = pk + o_has, *d_ns = pk + o_ns;
     int *const d_psflag = pack.flag(h);
 
     /* chunk the site axis so that the stored vectors fit */
-    const size_t per_site = ((size_t)(E + 2 * (size_t)N) * C * k + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg ? (size_t)N * k : 0) + (size_t)ngg.rows) * sizeof(double);
+    const size_t per_site = ((size_t)(E + 2 * (size_t)N) * C * k + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg ? (size_t)N * k : 0) + (size_t)ngg.rows +
+                             (pl ? (size_t)pgg.rows + (size_t)C * k + C : 0)) * sizeof(double);
     long chunk;
     if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site, GEN_BLOCK, false, &chunk))) return rc;
     const size_t ps_rows = ps ? (ps->mix_D ? (size_t)2 * C : (size_t)C * E * k * k + (size_t)C * k) : 0;
@@ -3773,6 +3923,21 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
                 if (hipGetLastError() != hipSuccess) { h->err = "plk_nni_ll: kernel launch failed"; return PLK_E_DEVICE; }
                 const int g0 = (int)gi * NNI_MAX_ROWS;
                 if ((rc = nni_group_out(h, nni, g0, std::min(NNI_MAX_ROWS, nni->n - g0), n, s0, p))) return rc;
+            }
+            continue;
+        }
+        if (pl) {
+            /* down pass and forward vectors once per chunk (k_up_nni's FORWARD instantiation), then one pass per PLACE_MAX_ROWS rows */
+            for (size_t gi = 0; gi < pgg.off.size(); gi++) {
+                PlaceOut po = {};
+                po.rec = pk + pgg.off[gi]; po.nrec = pgg.nrec[gi]; po.store_fn = gi == 0 ? 1 : 0; po.EQ = EQ;
+                po.QPT = h->d_plstream; po.QPN = h->d_plstream + qstrm; po.T = h->d_plT;
+                po.q_codes = pl->compact ? h->d_plcodes : nullptr; po.q_dense = pl->compact ? nullptr : h->d_pldense;
+                po.plane = p; po.WS = p + (size_t)pgg.rows * n; po.XW = po.WS + (size_t)C * k * n;
+                dispatch_K(K, [&](auto Kc) { launch_place<decltype(Kc)::value>(h, a, po, grid, gi == 0); });
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_place_ll: kernel launch failed"; return PLK_E_DEVICE; }
+                const long g0 = (long)gi * PLACE_MAX_ROWS;
+                if ((rc = place_group_out(h, pl, g0, (int)std::min<long>(PLACE_MAX_ROWS, pl->total() - g0), n, s0, p))) return rc;
             }
             continue;
         }
@@ -4176,6 +4341,111 @@ extern "C" int plk_nni_ll(plk_engine *h, int n_swaps, const int *swaps, double *
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { h->err = std::string("plk_nni_ll: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
     if (sums_out) put_dd_rows(sums_out, q.acc.data(), (size_t)n_swaps);
+    return PLK_OK;
+}
+
+/*
+ * Log likelihood of the tree with a new leaf attached to an edge, for every (query, edge) of the call (plk_place.h): one
+ * down pass per site chunk, one up pass per PLACE_MAX_ROWS rows.  Every argument is checked, the rates of the three new
+ * edges by the check of the model's rates, before anything is queued.
+ */
+extern "C" int plk_place_ll(plk_engine *h, int n_queries, const uint8_t *q_codes, const double *q_dense, int n_edges, const int *edges,
+                            double split, double pendant_rate, double *site_out, double *sums_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_place_ll: tree, model and patterns must be set"; return PLK_E_ARG; }
+    if (n_queries < 0) { h->err = "plk_place_ll: n_queries is negative"; return PLK_E_ARG; }
+    if (n_edges < 0) { h->err = "plk_place_ll: n_edges is negative"; return PLK_E_ARG; }
+    if ((q_codes != nullptr) == (q_dense != nullptr)) { h->err = "plk_place_ll: exactly one of q_codes and q_dense must be given"; return PLK_E_ARG; }
+    if (q_codes && h->pat_mode != 1) { h->err = "plk_place_ll: q_codes given, but the engine holds dense patterns: give q_dense"; return PLK_E_ARG; }
+    if (q_dense && h->pat_mode != 2) { h->err = "plk_place_ll: q_dense given, but the engine holds compact patterns: give q_codes"; return PLK_E_ARG; }
+    const int N = h->N, E = h->E, k = h->k;
+    const long S = h->S;
+    if (!(split >= 0.0 && split <= 1.0)) { h->err = "plk_place_ll: split must be a number in [0, 1]"; return PLK_E_ARG; }
+    if (!(pendant_rate >= 0.0 && pendant_rate < INFINITY)) { h->err = "plk_place_ll: pendant_rate must be finite and not negative"; return PLK_E_ARG; }
+    if (!edges && n_edges != E) {
+        h->err = "plk_place_ll: edges is NULL (every edge), but n_edges is " + std::to_string(n_edges) + " and the tree has " + std::to_string(E) + " edges";
+        return PLK_E_ARG;
+    }
+    for (int i = 0; edges && i < n_edges; i++)
+        if (edges[i] < 0 || edges[i] >= E) {
+            h->err = "plk_place_ll: edges[" + std::to_string(i) + "] = " + std::to_string(edges[i]) + " is out of range";
+            return PLK_E_ARG;
+        }
+    if (q_codes)
+        for (int q = 0; q < n_queries; q++)
+            for (long s = 0; s < S; s++)
+                if (q_codes[(size_t)q * S + s] >= h->nchar) {
+                    h->err = "plk_place_ll: q_codes: query " + std::to_string(q) + ", site " + std::to_string(s) + ": code " +
+                             std::to_string((int)q_codes[(size_t)q * S + s]) + " is not below nchar = " + std::to_string(h->nchar);
+                    return PLK_E_ARG;
+                }
+    if (q_dense)
+        for (size_t i = 0; i < (size_t)n_queries * k * S; i++)
+            if (!(q_dense[i] >= 0.0 && q_dense[i] < INFINITY)) {
+                h->err = "plk_place_ll: q_dense: query " + std::to_string(i / ((size_t)k * S)) + ", state " + std::to_string(i / S % k) + ", site " +
+                         std::to_string(i % S) + " is negative or not finite";
+                return PLK_E_ARG;
+            }
+    PlaceReq q;
+    std::vector<int> all;
+    if (!edges) { all.resize((size_t)E); for (int e = 0; e < E; e++) all[e] = e; edges = all.data(); }
+    q.Q = n_queries; q.ne = n_edges; q.edges = edges; q.compact = q_codes != nullptr;
+    /* the distinct target edges in the order of their first appearance, and the rates of the call */
+    {
+        std::vector<int> slot_of((size_t)std::max(E, 1), -1);
+        const double lower = 1.0 - split;
+        for (int i = 0; i < n_edges; i++) {
+            int &sl = slot_of[edges[i]];
+            if (sl < 0) {
+                sl = (int)q.rates.size() / 2;
+                q.rates.push_back(split * h->edge_rates[edges[i]]);
+                q.rates.push_back(lower * h->edge_rates[edges[i]]);
+            }
+            q.slot.push_back(sl);
+        }
+        q.rates.push_back(pendant_rate);
+        /* Of the three, only the pendant rate can be refused today: split is in [0, 1], so both parts of an edge are at most
+         * the rate plk_set_model / plk_update_edge_rates accepted for it.  The parts are checked all the same, for a writer
+         * of h->edge_rates added later (as in run_expm). */
+        const size_t kk = (size_t)k * k;
+        for (size_t j = 0; j < q.rates.size(); j++)
+            if (plk_k1_check_values(k, h->C, 1, h->Qn.data(), h->Qn.data() + kk, &q.rates[j], h->cat_rates.data(), h->cat_prior.data(),
+                                    h->root_mode, h->root_w.data(), nullptr, 0)) {
+                char msg[200];
+                int e = -1;
+                for (int i = 0; i < n_edges && e < 0; i++) if (q.slot[i] == (int)j / 2) e = edges[i];
+                if (j + 1 == q.rates.size()) snprintf(msg, sizeof msg, "the pendant edge (rate %g)", q.rates[j]);
+                else snprintf(msg, sizeof msg, "the %s part of edge %d (rate %g)", j % 2 ? "lower" : "upper", e, q.rates[j]);
+                h->err = std::string("plk_place_ll: the transition matrix kernel refuses ") + msg +
+                         ": rate x length x |Qn| must be finite and at most 2^40" + K1_CSR_NOTE;
+                return PLK_E_ARG;
+            }
+    }
+    if (n_queries == 0 || n_edges == 0 || (!site_out && !sums_out)) return PLK_OK;      /* nothing asked for: nothing runs */
+    HIPCHK(h, hipSetDevice(h->device));
+    QueryTimer qt(h);
+    int rc;
+    if (q_codes) {
+        if ((rc = dev_reserve(h, &h->d_plcodes, &h->plcodes_cap, (size_t)n_queries * h->Spad))) return rc;
+        HIPCHK(h, hipMemsetAsync(h->d_plcodes, 0, (size_t)n_queries * h->Spad, h->stream));
+        HIPCHK(h, hipMemcpy2DAsync(h->d_plcodes, (size_t)h->Spad, q_codes, (size_t)S, (size_t)S, (size_t)n_queries, hipMemcpyHostToDevice, h->stream));
+    } else {
+        if ((rc = dev_reserve(h, &h->d_pldense, &h->pldense_cap, (size_t)n_queries * k * S))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_pldense, q_dense, (size_t)n_queries * k * S * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    q.par = edge_parents(N, h->indptr.data());
+    q.pos.assign((size_t)N, 0);
+    for (int u = 0; u < N; u++) q.pos[h->preorder[u]] = u;
+    q.site_out = site_out; q.want_sums = sums_out != nullptr;
+    q.acc.assign((size_t)q.total(), 0.0L);
+    rc = run_updown(h, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, nullptr, nullptr, &q);
+    const hipError_t e = hipStreamSynchronize(h->stream);        /* the uploads above read the caller's arrays */
+    if (rc) return rc;
+    if (e != hipSuccess) { h->err = std::string("plk_place_ll: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
+    if (sums_out)
+        for (int qi = 0; qi < n_queries; qi++)
+            for (int ei = 0; ei < n_edges; ei++) put_dd(sums_out + 2 * ((size_t)qi * n_edges + ei), q.acc[(size_t)ei * n_queries + qi]);
     return PLK_OK;
 }
 

@@ -22,6 +22,7 @@ INFO_LL_KERNEL, INFO_STACK_SLOTS, INFO_PROGRAM_OPS, INFO_LL_KERNEL_NS, INFO_LL_T
 INFO_NNI_KERNEL = 22
 INFO_LL_TRIPLE = 23
 INFO_LL_QUAD = 24
+INFO_PLACE_KERNEL = 25
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 COEF_PRIOR, COEF_PRIOR_RATE_EDGE, COEF_PRIOR_RATE = 0, 1, 2
 FIT_EM, FIT_LBFGS = 0, 1
@@ -107,6 +108,7 @@ def load_library():
                                       ctypes.POINTER(ci), ctypes.c_char_p, ctypes.c_size_t]
     lib.plk_nni_swaps.argtypes = [ci, vp, vp, vp]
     lib.plk_nni_ll.argtypes = [vp, ci, vp, vp, vp]
+    lib.plk_place_ll.argtypes = [vp, ci, vp, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]
     lib.plk_get_transition_matrices.argtypes = [vp, vp]
     lib.plk_get_info.argtypes = [vp, ci, ctypes.POINTER(cl)]
     lib.plk_set_option.argtypes = [vp, ci, cl]
@@ -364,6 +366,23 @@ class Engine:
         out = np.zeros((n, self.S)) if per_site else None
         sums = np.zeros((n, 2)) if want_sums else None
         self._check(self._lib.plk_nni_ll(self._h, n, _ptr(sw), _ptr(out), _ptr(sums)))
+        return out, sums
+
+    def place_ll(self, q_codes=None, q_dense=None, edges=None, split=0.5, pendant_rate=None, per_site=True, want_sums=True):
+        """log likelihood of the tree with each query taxon attached to each listed edge (include/plk.h:plk_place_ll);
+        q_codes: [Q][S] character codes (an engine holding compact patterns) or q_dense: [Q][k][S]; edges: CSR edge
+        indices, None = every edge -> (ll' [Q][n_edges][S] or None, sums [Q][n_edges][2] or None)"""
+        if pendant_rate is None:
+            raise TypeError("place_ll() needs pendant_rate")
+        qc = np.ascontiguousarray(q_codes, dtype=np.uint8) if q_codes is not None else None
+        qd = _f64(q_dense) if q_dense is not None else None
+        nq = qc.shape[0] if qc is not None else (qd.shape[0] if qd is not None else 0)
+        ed = _i32(edges) if edges is not None else None
+        ne = len(ed) if ed is not None else self.E
+        out = np.zeros((nq, ne, self.S)) if per_site else None
+        sums = np.zeros((nq, ne, 2)) if want_sums else None
+        self._check(self._lib.plk_place_ll(self._h, nq, _ptr(qc), _ptr(qd), ne, _ptr(ed), float(split), float(pendant_rate),
+                                           _ptr(out), _ptr(sums)))
         return out, sums
 
     def transition_matrices(self):
