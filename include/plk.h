@@ -496,15 +496,19 @@ enum {
                                        three-leaf table (a cherry, a leaf and the edge above their parent in one row).
                                        PLK_INFO_PAIR_TABLES then counts the cherries that still have a table of their own, and
                                        PLK_INFO_LL_EXEC_FLOPS the stream that ran */
-    PLK_INFO_PLACE_KERNEL = 25      /* up pass of the last plk_place_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
+    PLK_INFO_PLACE_KERNEL = 25,     /* up pass of the last plk_place_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
                                        4 categories), 2 = generic */
+    PLK_INFO_LL_BARRIER = 26        /* workgroup barrier of the last ll evaluation's streamed kernel as it was launched: 0 = another
+                                       kernel ran, else bits 0-1 = 1 the waves never met, 2 they met before every unit, 3 before
+                                       every category, and bit 4 = the engine chose it from the uploaded formats
+                                       (plk_v4s_auto_sync) rather than an option bit */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused
  * kernel applies; used by tests and by bench.py --kernel generic.
  * Which ll kernel runs is decided once, when the device formats of the program are uploaded (the engine's ll plan), not
  * per evaluation.  Setting any option that decision reads (PLK_OPT_FUSED_SITES_PER_LANE, _FUSED_ASM, _MFMA, _PAIR_TABLES,
- * _VEC_REG_STACK, _MFMA_NS2) marks the plan stale, PLK_OPT_FORCE_GENERIC the program itself: the next evaluation
+ * _VEC_REG_STACK, _MFMA_NS2, _STREAM_GRID) marks the plan stale, PLK_OPT_FORCE_GENERIC the program itself: the next evaluation
  * decides and uploads again. */
 int plk_set_option(plk_engine *h, int option, long value);
 enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PER_LANE = 2 /* 0 auto, 1, 2 */,
@@ -531,8 +535,11 @@ enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PE
                                about one byte per site and leaf or cherry) and the tables of all categories resident in
                                LDS (k_ll_fused4_v4s) wherever C x table bytes fit the LDS and the stream fits device
                                memory, otherwise as 1; the default takes that form under the same conditions.  + 8: without the
-                               scalar-cache warm-up; streamed form, + 16: its waves meet before every unit instead of every
-                               category, + 32: never (measurements); + 64: the streamed form without the folded op
+                               scalar-cache warm-up; streamed form: by default its waves meet before every category, except
+                               where one category is resident at a time (one rate category, or a group per category) and
+                               its matrix stream and op words fit the 16 KB scalar cache: then they never meet (DESIGN.md
+                               section 4); + 16: they meet before every unit, + 32: never (+ 32 wins over + 16), + 65536: before
+                               every category, whatever the plan (measurements; PLK_INFO_LL_BARRIER reports what ran); + 64: the streamed form without the folded op
                                stream and without the held first chunks (the checked stream as it is built, ADVANCE and SCALE
                                ops dispatched on their own, every category requesting the unit's first three chunks itself:
                                the kernel as it was before the fold, and what runs when the fold does not replay);
@@ -559,7 +566,10 @@ enum { PLK_OPT_FORCE_GENERIC = 0, PLK_OPT_SITE_CHUNK = 1, PLK_OPT_FUSED_SITES_PE
                                registers (2 waves per SIMD); 0: every waiting vector goes through HBM slots (round 2) */,
        PLK_OPT_MFMA_NS2 = 8 /* 1: the matrix-core ll kernel for 33 <= k <= 64 gives a wave two groups of 16 sites (every staged
                                matrix and every fragment read serve 128 sites of a workgroup); 0 (default): one group.  Measured
-                               equal at BASELINE config 5 */ };
+                               equal at BASELINE config 5 */,
+       PLK_OPT_STREAM_GRID = 9 /* 0 (default): the streamed k = 4 ll kernel launches one workgroup per CU; n > 0: at most n
+                               workgroups, and its plan (three- and four-leaf tables, category groups) is made for n CUs.
+                               For tests: with 1 or 2 workgroups every wave walks several units at a few thousand sites */ };
 
 /* ------------------------------------------------------------------------------------------------------------
  * Several GPUs in one process: a group of engines, one per listed device, behind the same calls.

@@ -200,7 +200,7 @@ struct plk_engine {
     double *d_work = nullptr; size_t work_cap = 0;   /* deriv / marginal workspace */
 
     /* options / info */
-    long opt_force_generic = 0, opt_site_chunk = 0, opt_fused_ns = 0, opt_fused_asm = 1, opt_mfma = 1, opt_up_nodes = 2, opt_pair_tables = 1, opt_vec_reg_stack = 1, opt_mfma_ns2 = 0;
+    long opt_force_generic = 0, opt_site_chunk = 0, opt_fused_ns = 0, opt_fused_asm = 1, opt_mfma = 1, opt_up_nodes = 2, opt_pair_tables = 1, opt_vec_reg_stack = 1, opt_mfma_ns2 = 0, opt_stream_grid = 0;
     void *comm = nullptr;                /* ncclComm_t of the one-process-per-GPU reduction step */
     int comm_ranks = 0;
     long info_pair_sums_kernel = 0, info_query_ns = 0;
@@ -216,7 +216,7 @@ struct plk_engine {
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
-    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_pairmul = 0, info_ll_triple = 0, info_ll_quad = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
+    long info_ll_kernel = 0, info_updown_kernel = 0, info_ll_kernel_ns = 0, info_ll_total_ns = 0, info_ll_variant = 0, info_ll_form = 0, info_ll_fold = 0, info_ll_pairmul = 0, info_ll_triple = 0, info_ll_quad = 0, info_ll_barrier = 0, info_ll_exec_flops = 0, info_cat_posterior_kernel = 0;
 };
 
 static std::string g_create_error;
@@ -1679,6 +1679,10 @@ extern "C" int plk_set_option(plk_engine *h, int option, long value)
     if (option == PLK_OPT_MFMA_NS2) { h->opt_mfma_ns2 = value; h->fmt_dirty = true; return PLK_OK; }
     if (option == PLK_OPT_VEC_REG_STACK) { h->opt_vec_reg_stack = value; h->fmt_dirty = true; return PLK_OK; }
     if (option == PLK_OPT_PAIR_TABLES) { h->opt_pair_tables = value; h->fmt_dirty = true; return PLK_OK; }
+    if (option == PLK_OPT_STREAM_GRID) {
+        if (value < 0) { h->err = "PLK_OPT_STREAM_GRID: a workgroup count, or 0 for the default"; return PLK_E_ARG; }
+        h->opt_stream_grid = value; h->fmt_dirty = true; return PLK_OK;
+    }
     h->err = "plk_set_option: unknown option";
     return PLK_E_ARG;
 }
@@ -1733,6 +1737,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_LL_PAIRMUL: *out = h->info_ll_pairmul; return PLK_OK;
     case PLK_INFO_LL_TRIPLE: *out = h->info_ll_triple; return PLK_OK;
     case PLK_INFO_LL_QUAD: *out = h->info_ll_quad; return PLK_OK;
+    case PLK_INFO_LL_BARRIER: *out = h->info_ll_barrier; return PLK_OK;
     case PLK_INFO_LL_EXEC_FLOPS: *out = h->info_ll_exec_flops; return PLK_OK;
     case PLK_INFO_PAIR_TABLES: *out = !h->fmt_dirty && h->plan.pair_tables ? h->plan.npairs : 0; return PLK_OK;
     case PLK_INFO_STACK_SLOTS: *out = h->slots_needed; return PLK_OK;
@@ -2166,6 +2171,10 @@ static int upload_pair_table_lists(plk_engine *h)
     return dev_upload(h, &h->d_tabs, tabs.data(), tabs.size());
 }
 
+/* workgroups the streamed k = 4 kernel may launch, and the CU count its plan is made for: the device's CUs, or fewer under
+ * PLK_OPT_STREAM_GRID (tests: every wave then walks several units at a few thousand sites) */
+static int stream_cus(const plk_engine *h) { return h->opt_stream_grid > 0 ? (int)std::min<long>(h->opt_stream_grid, h->num_cus) : h->num_cus; }
+
 /* k = 4 with compact codes: the fused kernel plk_k4_choose picks, or PLK_K4_NONE in p.k4.variant and nothing uploaded */
 static int upload_formats_fused4(plk_engine *h, LlPlan &p)
 {
@@ -2189,7 +2198,7 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
         else h->k4_groups_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
         h->k4_static_lds_known = true;
     }
-    PlkK4Shape sh = {h->nchar, h->C, h->S, h->num_cus, h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
+    PlkK4Shape sh = {h->nchar, h->C, h->S, stream_cus(h), h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
     std::copy(h->k4_static_lds, h->k4_static_lds + 3, sh.static_lds);
     const int *node_codes = h->nchar <= 16 && h->node_codes.size() == (size_t)h->N ? h->node_codes.data() : nullptr;
     sh.node_codes = node_codes;
@@ -2219,7 +2228,7 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
         const bool can_group = c.pair && c.fold && p.held && h->k4_pair_ok && h->k4_groups_ok;
         /* the plan is plk_k4_choose's; the engine only takes the groups back where the instantiation with phases cannot be described */
         PlkV4TPlan tp = c.triple;
-        auto one_group = [&]() { return plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, h->num_cus, c.tip_base, po.triple, 1, po.quad, node_codes); };
+        auto one_group = [&]() { return plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, stream_cus(h), c.tip_base, po.triple, 1, po.quad, node_codes); };
         if (tp.groups > 1 && !can_group) tp = one_group();
         if (tp.nodes + tp.quads > 0 && tp.groups > 1 &&
             dev_reserve(h, &h->d_llstate, &h->llstate_cap, (size_t)nunits * PLK_V4S_UNIT * 3 / 2) != PLK_OK) {
@@ -2317,6 +2326,12 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     const PlkFusedPT &f = h->fpt;
     p.pair_tables = true; p.npairs = f.npairs;
     const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? (p.pairmul ? h->fv4p.words : p.fold ? h->fv4s_fold.words : h->fv4s.words) : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
+    if (c.variant == PLK_K4_V4S && c.sync_auto) {
+        /* the barrier of the streamed form, decided again on the formats that run (plk_k4_choose decided on the plan's): the
+         * categories resident at a time, the matrix stream and the op words of one category as uploaded */
+        const int Cg = p.triple.nodes + p.triple.quads > 0 && p.triple.Cg > 0 ? p.triple.Cg : h->C;
+        p.k4.sync = plk_v4s_auto_sync(Cg, f.mat_edge.size(), (p.pairmul ? h->fv4p.stride : p.fold ? h->fv4s_fold.stride : h->fv4s.stride));
+    }
     if ((rc = dev_upload(h, &h->d_words_pt, words.data(), words.size()))) return rc;
     /* d_obs_row before the pair-table lists: the order in which these buffers were first allocated when the kernels were
      * measured (with it after them, the streamed kernel at 1.25M sites of BASELINE config 3 ran 0.3 % longer) */
@@ -2570,7 +2585,7 @@ static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool 
      * sites), every workgroup walks the tiles with a grid stride.  Streamed codes: 768 lanes per CU, a wave per 128-site
      * unit.  One partial sum per tile (per wave of the streamed form). */
     unsigned grid = (unsigned)ntiles;
-    if (c.variant == PLK_K4_V4S) grid = (unsigned)std::min<long>(((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT + 11) / 12, h->num_cus);
+    if (c.variant == PLK_K4_V4S) grid = (unsigned)std::min<long>(((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT + 11) / 12, stream_cus(h));
     else if (c.variant == PLK_K4_V4 || c.variant == PLK_K4_ASM_PT) grid = (unsigned)std::min(ntiles, c.tile == 512 ? 2 * h->num_cus : h->num_cus);
     *npartials = c.variant == PLK_K4_V4S ? grid * 12 : (unsigned)ntiles;
     int rc;
@@ -2597,6 +2612,7 @@ static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool 
             sa.pt.nwords = (int)(p.pairmul ? h->fv4p.stride : p.fold ? h->fv4s_fold.stride : h->fv4s.stride);
             sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
             sa.sync = c.sync;
+            h->info_ll_barrier = (sa.sync == 0 ? 1 : sa.sync == 1 ? 2 : 3) | (c.sync_auto ? 16 : 0);
             sa.first_y1 = p.pairmul ? h->fv4p.first_y1[0] : 0u; sa.first_b1 = p.pairmul ? h->fv4p.first_b1 : 0u;
             sa.groups = p.triple.groups; sa.cg = p.triple.Cg > 0 ? p.triple.Cg : h->C;
             sa.part_sum = h->d_llstate;
@@ -2734,6 +2750,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     if ((rc = evk_resolve(h, evi))) return rc;           /* only waits when 64 evaluations are queued */
     HIPCHK(h, hipEventRecord(h->evk[evi][0], h->stream));
     unsigned npartials = 0;
+    h->info_ll_barrier = 0;                              /* the streamed launch sets it */
     switch (p.family) {
     case LL_FUSED4: rc = launch_ll_fused4(h, p, d_out, want_sum, &npartials); break;
     case LL_VEC: rc = launch_ll_vec(h, p, d_out, want_sum, &npartials); break;

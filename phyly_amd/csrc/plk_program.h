@@ -1785,17 +1785,20 @@ static inline std::string plk_fused_check_v4t(int N, const int *ip, const int *i
  * and the round trip of the partial mixture sum (PLK_V4T_PHASE_UNIT_INSTS), and once the restaging of the tables and the
  * skew of two barriers (PLK_V4T_PHASE_INSTS, in instructions of one wave).  The best candidate with a gain is taken when
  * the option forces the form; the default also asks every wave to walk at least PLK_V4T_MIN_PASSES units per phase: the
- * smallest count at which the form was measured to win (4 at 1.25M sites of BASELINE config 3, - 16 %; 3 at config 2 was
- * even; DESIGN.md section 4, profiles/ll_k4_triple_ab.json).
- * The phase charge is fitted to the forced runs of that file at 10M sites (26 units per wave): G = 1 with 2 nodes against no
- * form prices an instruction per unit and category at 0.133 us of the launch; at that price G = 4 with 16 nodes runs 0.096 ms
- * longer than its instruction count says, G = 2 with 15 nodes does not, so two further phases cost about 0.11 ms = 830
- * instructions per unit, 415 a phase: 6000 / 26 + 180.  (One site count cannot tell the two constants apart; the fixed one is kept.)
+ * smallest count at which the form was measured to win (3 at config 2, with four-leaf tables: kernel - 26 %, whole step - 7 %,
+ * the tables' build included; DESIGN.md section 4, profiles/ll_k4_nextreq_ab.json.  With three-leaf tables alone it was even there).
+ * The phase charge was first fitted at one site count, with the waves meeting before every category: 6000 + 180 a unit.  Since
+ * the phases of one category run without that barrier (plk_v4s_auto_sync) it is fitted to forced runs at two counts, an
+ * instruction per unit priced at the 5 to 8 ns the kernel's time per executed instruction gives: at 26 units per wave G = 4 with
+ * 16 three-leaf tables runs 0.045 ms longer than G = 2 with 15 where its instructions say 0.023 to 0.036 ms shorter, so a phase
+ * costs 5200 to 6700 there; at 4 units per wave (1.25M sites) G = 4 with the mix runs 0.067 ms shorter than G = 2 with 15
+ * where the instructions alone say 0.054 to 0.082: a phase costs between nothing and 1000.  So the cost is per unit -- the
+ * prologue, the partial sums' round trip -- and the fixed part is small: 200 + 250 a unit.
  */
 #define PLK_V4T_NODE_INSTS 44
-#define PLK_V4T_PHASE_UNIT_INSTS 180
-#define PLK_V4T_PHASE_INSTS 6000
-#define PLK_V4T_MIN_PASSES 4
+#define PLK_V4T_PHASE_UNIT_INSTS 250
+#define PLK_V4T_PHASE_INSTS 200
+#define PLK_V4T_MIN_PASSES 3
 /* quads > 0: the four-leaf form (plk_fused_v4q_build) with the nodes listed, as indices into the checked program's vops:
  * quad_at / quad_shape the four-leaf nodes, tri_at the `nodes` three-leaf nodes that are not below one of them */
 struct PlkV4TPlan {
@@ -2442,7 +2445,8 @@ enum { PLK_K4_LDS_V4S_768 = 0, PLK_K4_LDS_V4_768, PLK_K4_LDS_V4_512 };     /* Pl
 
 /* PLK_OPT_PAIR_TABLES: & 7 which pair-table kernel (0 with the whole value 0: none; 1 the default order; 2, 3, 5, 6 one
  * kernel and tile, forced; 7 the streamed form wherever it fits), + 8 without the scalar-cache warm-up, + 16 / + 32 the
- * waves of the streamed form meet before every unit only / never (default: before every category), + 64 the streamed form
+ * waves of the streamed form meet before every unit only / never (+ 32 wins over + 16), + 65536 before every category whatever
+ * the plan (default: before every category, or never where one category is resident at a time: plk_v4s_auto_sync), + 64 the streamed form
  * as it was before the folded op stream and the held first chunks (the checked stream unfolded, every category requests
  * the unit's first three chunks itself), + 128 / + 256 without the held chunks only / without the fold only, + 512 without the
  * pair-product form (the folded stream with held chunks on every tree; that form needs both, so + 64 / + 128 / + 256 turn
@@ -2451,13 +2455,25 @@ enum { PLK_K4_LDS_V4S_768 = 0, PLK_K4_LDS_V4_768, PLK_K4_LDS_V4_512 };     /* Pl
  * than one group needs the pair-product form), + 16384 the four-leaf form (plk_fused_v4q_build) wherever it applies, whatever
  * the site count (it implies + 1024), + 32768 never; + 1024 alone keeps to three-leaf tables, + 2048 forbids both.
  * The + bits are for measurements. */
-struct PlkPairTablesOpt { bool on; int mode, warm, sync, fold, held, pair, triple, groups, quad; };
+struct PlkPairTablesOpt { bool on; int mode, warm, sync /* -1: the plan's choice */, fold, held, pair, triple, groups, quad; };
 static inline PlkPairTablesOpt plk_pair_tables_opt(long v)
 {
     const int quad = (v & (2048 | 32768)) ? 0 : (v & 16384) ? 2 : (v & 1024) ? 0 : 1;
-    return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : 2, (v & (64 | 256)) ? 0 : 1, (v & (64 | 128)) ? 0 : 1,
+    return {v != 0, (int)(v & 7), (v & 8) ? 0 : 1, (v & 32) ? 0 : (v & 16) ? 1 : (v & 65536) ? 2 : -1, (v & (64 | 256)) ? 0 : 1, (v & (64 | 128)) ? 0 : 1,
             (v & (64 | 128 | 256 | 512)) ? 0 : 1, (v & 2048) ? 0 : (v & 1024) || quad == 2 ? 2 : 1,
             (v & (4096 | 8192)) == (4096 | 8192) ? 2 : (v & 4096) ? 1 : (v & 8192) ? -1 : 0, quad};
+}
+
+/* Do the waves of a workgroup of the streamed form meet before every category (2) or never (0)?  The barrier keeps them on
+ * the same category's matrix stream and op words, so that the 16 KB scalar cache holds what all of them read.  Where one
+ * category is resident at a time -- one rate category, or a group per category: a phase of the launch has one -- they read
+ * the same category whatever their drift, and if its matrix stream (nmat matrices and the spare one, 128 bytes each) and op
+ * words (nwords dwords) fit the cache the barrier only costs: all twelve waves of the CU then start every unit together
+ * and, as the code reads, wait together for its first chunks from device memory (timings and counters: DESIGN.md section 4) */
+#define PLK_V4S_SCALAR_CACHE_BYTES (16 * 1024)
+static inline int plk_v4s_auto_sync(int Cg, size_t nmat, size_t nwords)
+{
+    return Cg == 1 && (nmat + 1) * 128 + nwords * 4 <= (size_t)PLK_V4S_SCALAR_CACHE_BYTES ? 0 : 2;
 }
 
 struct PlkK4Shape {
@@ -2477,6 +2493,7 @@ struct PlkK4Choice {
     size_t lds = 0;                                  /* dynamic LDS of the launch */
     unsigned tip_base = 0;                           /* v4 / v4s: LDS address of the table image = static LDS of the kernel */
     int warm = 1, sync = 2;                          /* pair-table kernels: the measurement bits of PLK_OPT_PAIR_TABLES */
+    bool sync_auto = false;                          /* v4s: sync is plk_v4s_auto_sync's choice, not an option bit's */
     int fold = 1, held = 1;                          /* v4s: folded op stream, first chunks held across the categories */
     int pair = 0;                                    /* v4s: the pair-product form is asked for and the program is within its 3 slots */
     PlkV4TPlan triple;                               /* v4s: three-leaf tables and category groups (plk_v4t_plan; nodes == 0: not taken) */
@@ -2503,7 +2520,7 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
     const bool asm_fits = NS == 1 && plk_fused_asm_ok(pg) && sh.fused_asm && lds_asm <= PLK_LDS_LIMIT;
     if (pg.slots_needed > PLK_FUSED_SLOTS || (!asm_fits && lds_cpp > PLK_LDS_LIMIT)) return ch;
     const PlkPairTablesOpt po = plk_pair_tables_opt(sh.pair_tables);
-    ch.warm = po.warm; ch.sync = po.sync; ch.fold = po.fold; ch.held = po.held;
+    ch.warm = po.warm; ch.sync = po.sync < 0 ? 2 : po.sync; ch.sync_auto = po.sync < 0; ch.fold = po.fold; ch.held = po.held;
     if (po.on && sh.fused_asm && sh.sites_per_lane != 2 && pg.slots_needed <= 4 && nchar <= 16 && !pg.obs_nodes.empty()) {
         if ((po.mode == 1 || po.mode == 7) && sh.S > 0 && allow_stream) {
             /* measured faster than the tile kernels at every shape tried (profiles/ll_k4_stream_ab.json), so no site count
@@ -2524,6 +2541,14 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
                  * the formats themselves are derived from fpt and replayed like the fold and the pair products */
                 if (ch.bad.empty())
                     ch.triple = plk_v4t_plan(fpt, nchar, sh.C, sh.S, sh.num_cus, st, po.triple, ch.pair && ch.fold && ch.held ? po.groups : 1, po.quad, sh.node_codes);
+                if (ch.sync_auto) {
+                    /* on the plan: every three-leaf table and every (cherry, cherry) table takes one product out of the matrix
+                     * stream, every ((cherry, leaf), leaf) table two; the checked stream's op words bound those of the derived ones */
+                    const bool tables = ch.triple.nodes + ch.triple.quads > 0;
+                    size_t absorbed = tables ? (size_t)ch.triple.nodes : 0;
+                    if (tables) for (int shp : ch.triple.quad_shape) absorbed += shp == PLK_V4Q_A ? 2 : 1;
+                    ch.sync = plk_v4s_auto_sync(tables && ch.triple.Cg > 0 ? ch.triple.Cg : sh.C, fpt.mat_edge.size() - std::min(absorbed, fpt.mat_edge.size()), fv4s.stride);
+                }
                 return ch;
             }
         }

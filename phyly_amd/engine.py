@@ -23,7 +23,9 @@ INFO_NNI_KERNEL = 22
 INFO_LL_TRIPLE = 23
 INFO_LL_QUAD = 24
 INFO_PLACE_KERNEL = 25
+INFO_LL_BARRIER = 26
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
+OPT_STREAM_GRID = 9
 COEF_PRIOR, COEF_PRIOR_RATE_EDGE, COEF_PRIOR_RATE = 0, 1, 2
 FIT_EM, FIT_LBFGS = 0, 1
 

@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--kernel", choices=["auto", "generic"], default="auto")
     ap.add_argument("--what", choices=["ll", "deriv", "marginal", "dwell", "em", "fit"], default="ll")
     ap.add_argument("--fused-ns", type=int, default=0)
+    ap.add_argument("--engine-option", action="append", default=[], metavar="ID=VALUE", help="plk_set_option(ID, VALUE) before the run, as bench.py's")
     args = ap.parse_args()
     from phyly_amd import synth, engine as E
     wl = synth.Workload(args.config)
@@ -32,6 +33,9 @@ def main():
         eng.set_option(E.OPT_FORCE_GENERIC, 1)
     if args.fused_ns:
         eng.set_option(E.OPT_FUSED_NS, args.fused_ns)
+    for kv in args.engine_option:
+        oid, val = kv.split("=")
+        eng.set_option(int(oid), int(val))
     # realistic codes for a block of sites, tiled to the requested size
     base = wl.simulate(min(args.sites, 4096))
     reps = -(-args.sites // base.shape[1])
