@@ -500,8 +500,8 @@ enum {
                                        4 categories), 2 = generic */
     PLK_INFO_LL_BARRIER = 26        /* workgroup barrier of the last ll evaluation's streamed kernel as it was launched: 0 = another
                                        kernel ran, else bits 0-1 = 1 the waves never met, 2 they met before every unit, 3 before
-                                       every category, and bit 4 = the engine chose it from the uploaded formats
-                                       (plk_v4s_auto_sync) rather than an option bit */
+                                       every category, and bit 4 = no bit of PLK_OPT_PAIR_TABLES forced it: it was decided, once
+                                       per upload, on the formats that run (plk_k4_stream by plk_v4s_auto_sync) */
 };
 
 /* force the generic (HBM-resident partials) traversal even where the fused

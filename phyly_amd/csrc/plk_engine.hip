@@ -50,11 +50,14 @@
 #define PLK_MAX_C 64
 
 /* Which ll kernel runs for the engine's state, and how it is launched: the only record of the choice.  upload_formats
- * writes it together with the device formats it names; ll_impl, build_tables, run_expm and plk_get_info read it. */
+ * writes it together with the device formats it names; ll_impl, build_tables, run_expm and plk_get_info read it.  What the
+ * streamed k = 4 form runs is one value, k4s (plk_k4_stream, plk_program.h): the engine uploads what it names and launches from it. */
 enum LlFamily { LL_FUSED4 = 1, LL_GENERIC = 2, LL_MFMA = 3, LL_VEC = 4 };      /* the values of PLK_INFO_LL_KERNEL */
 struct LlPlan {
     LlFamily family = LL_GENERIC;
     PlkK4Choice k4;                      /* LL_FUSED4: variant, sites per tile, NS, D, pack4, table base (plk_k4_choose) */
+    PlkK4Stream k4s;                     /* PLK_K4_V4S: the op streams that run (their pair-table format is the engine's fpt), which words are uploaded, held
+                                            chunks, tables and groups, LDS, barrier, PLK_INFO_LL_FOLD / _PAIRMUL / _TRIPLE / _QUAD */
     bool pair_tables = false;            /* LL_FUSED4, LL_VEC: the formats are the pair-table ones (fpt) ... */
     int npairs = 0;                      /* ... with so many cherries as tables (PLK_INFO_PAIR_TABLES) */
     int block = 0, wg_sites = 0;         /* lanes per workgroup; sites per workgroup (k = 4: per tile) */
@@ -64,13 +67,6 @@ struct LlPlan {
     bool vec_rs = false;                 /* LL_VEC: register stack, and its window of three slots */
     int vec_reg_lo = 0;
     long info_variant = 0, info_form = 0, info_exec_flops = 0;     /* PLK_INFO_LL_VARIANT, _FORM, _LL_EXEC_FLOPS */
-    bool fold = false, held = false;     /* streamed form: the folded op stream is the one uploaded; first chunks held */
-    long info_fold = 0;                  /* PLK_INFO_LL_FOLD */
-    bool pairmul = false;                /* streamed form: the pair-product stream is the one uploaded, k_ll_fused4_v4s<768, true, true> runs it */
-    long info_pairmul = 0;               /* PLK_INFO_LL_PAIRMUL */
-    PlkV4TPlan triple;                   /* streamed form: three-leaf tables and category groups (nodes == 0: the form does not run) */
-    long info_triple = 0;                /* PLK_INFO_LL_TRIPLE */
-    long info_quad = 0;                  /* PLK_INFO_LL_QUAD */
 };
 
 struct plk_engine {
@@ -122,8 +118,8 @@ struct plk_engine {
      * tables_dirty: the P-dependent tables (matrix stream, tip tables, A fragments) are older than P */
     bool prog_dirty = true, fmt_dirty = true, tables_dirty = true;
     LlPlan plan;                         /* which ll kernel runs, and how: written by upload_formats, valid while !fmt_dirty */
-    bool k4_held_ok = false;             /* k_ll_fused4_v4s<768, true> can be described and has the static LDS of <768, false> */
-    bool k4_pair_ok = false;             /* the same for k_ll_fused4_v4s<768, true, true> */
+    PlkK4StreamCaps k4_caps;             /* held, pair, groups: k_ll_fused4_v4s<768, true>, <768, true, true>, <768, true, true, true> can be described
+                                            and have the static LDS of <768, false> (asked once, with k4_static_lds) */
     size_t k4_static_lds[3] = {};        /* PlkK4Shape::static_lds, asked of the runtime once (k4_static_lds_known) */
     hipError_t k4_static_lds_err[3] = {};
     bool k4_static_lds_known = false;
@@ -139,9 +135,6 @@ struct plk_engine {
     unsigned *d_words_pt = nullptr;
     PlkFusedV4 fv4;                      /* 64-bit ops of the two-sites-per-lane interpreter */
     PlkVecPT vpt;                        /* the vector ll kernel's program on pair tables */
-    PlkFusedV4S fv4s;                    /* streamed codes (k_ll_fused4_v4s): one op stream per category */
-    PlkFusedV4SFold fv4s_fold;           /* ... and its folded form, the one the kernel runs unless PLK_OPT_PAIR_TABLES + 64 / + 256 */
-    PlkFusedV4P fv4p;                    /* ... and the pair-product stream of trees within 3 slots (k_ll_fused4_v4s<768, true, true>) */
     unsigned *d_cstream = nullptr; size_t cstream_cap = 0;   /* the code stream (plk_stream_dword), built by upload_formats */
     int *d_obs_row = nullptr;            /* staged row per observation of the program */
     int *d_row_nodes = nullptr, *d_tabs = nullptr;   /* [5][rows] staged-row nodes (third: the leaf of a three-leaf row; fourth and the index
@@ -151,10 +144,7 @@ struct plk_engine {
                                                         fpt.nquads four-leaf tables */
     uint8_t *d_quad_lut = nullptr;       /* four-leaf rows: PlkFusedPT::lut, [nquads][4][16] code -> rank (the stream builder's) */
     int *d_quad_codes = nullptr;         /* ... and [nquads][4][4] rank -> code (the table builder's; a rank that does not occur: the code of rank 0) */
-    PlkFusedPT fpt_t;                    /* three-leaf form: the rewritten formats while they are derived and checked (then moved to fpt) */
-    PlkFusedV4S fv4s_t;
     double *d_llstate = nullptr; size_t llstate_cap = 0;   /* category groups: per site the partial mixture sum, then the exponents */
-    bool k4_groups_ok = false;           /* k_ll_fused4_v4s<768, true, true, true> can be described and has the static LDS of <768, false> */
     int num_cus = 256;
     int2 *d_ops = nullptr;
     int4 *d_fops = nullptr;              /* fused-kernel program (C++ interpreter) */
@@ -2189,26 +2179,27 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
             else (void)hipGetLastError();
         }
         /* the held-chunks instantiation of the streamed kernel shares the plan's table base: it runs only if it has the same static LDS */
-        hipFuncAttributes fh;
-        if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true>) != hipSuccess) (void)hipGetLastError();
-        else h->k4_held_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
-        if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true, true>) != hipSuccess) (void)hipGetLastError();
-        else h->k4_pair_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
-        if (hipFuncGetAttributes(&fh, (const void *)k_ll_fused4_v4s<768, true, true, true>) != hipSuccess) (void)hipGetLastError();
-        else h->k4_groups_ok = h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
+        auto same_static_lds = [&](const void *fn) {
+            hipFuncAttributes fh;
+            if (hipFuncGetAttributes(&fh, fn) != hipSuccess) { (void)hipGetLastError(); return false; }
+            return h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess && fh.sharedSizeBytes == h->k4_static_lds[PLK_K4_LDS_V4S_768];
+        };
+        h->k4_caps.held = same_static_lds((const void *)k_ll_fused4_v4s<768, true>);
+        h->k4_caps.pair = same_static_lds((const void *)k_ll_fused4_v4s<768, true, true>);
+        h->k4_caps.groups = same_static_lds((const void *)k_ll_fused4_v4s<768, true, true, true>);
         h->k4_static_lds_known = true;
     }
     PlkK4Shape sh = {h->nchar, h->C, h->S, stream_cus(h), h->opt_pair_tables, h->opt_fused_asm, h->opt_fused_ns, {}};
     std::copy(h->k4_static_lds, h->k4_static_lds + 3, sh.static_lds);
-    const int *node_codes = h->nchar <= 16 && h->node_codes.size() == (size_t)h->N ? h->node_codes.data() : nullptr;
-    sh.node_codes = node_codes;
+    sh.node_codes = h->nchar <= 16 && h->node_codes.size() == (size_t)h->N ? h->node_codes.data() : nullptr;
     const long nunits = (h->S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT;
-    p.k4 = plk_k4_choose(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess, h->fu, h->fpt, h->fv4, h->fv4s);
-    if (p.k4.variant == PLK_K4_V4S && dev_reserve(h, &h->d_cstream, &h->cstream_cap, (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT) != PLK_OK) {
+    PlkFusedV4S fv4s;                    /* the checked stream; the one that runs is p.k4s.fv4s */
+    p.k4 = plk_k4_choose(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, h->k4_static_lds_err[PLK_K4_LDS_V4S_768] == hipSuccess, h->fu, h->fpt, h->fv4, fv4s);
+    if (p.k4.variant == PLK_K4_V4S && dev_reserve(h, &h->d_cstream, &h->cstream_cap, (size_t)nunits * fv4s.chunks * PLK_V4S_UNIT) != PLK_OK) {
         /* a stream that cannot be allocated sends the query to the tile kernels, it does not fail it */
         h->err.clear();
         (void)hipGetLastError();
-        p.k4 = plk_k4_choose(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, false, h->fu, h->fpt, h->fv4, h->fv4s);
+        p.k4 = plk_k4_choose(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, false, h->fu, h->fpt, h->fv4, fv4s);
     }
     const PlkK4Choice &c = p.k4;
     if (c.variant == PLK_K4_NONE) return PLK_OK;
@@ -2218,85 +2209,20 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     p.block = c.block; p.wg_sites = c.tile; p.lds = c.lds;
     p.info_variant = c.variant == PLK_K4_CPP ? 3 : c.variant == PLK_K4_ASM ? 1 : c.variant == PLK_K4_ASM_PT ? 5 : 6;
     p.info_form = c.variant == PLK_K4_V4S ? 1 : 0;
-    p.fold = false; p.held = c.variant == PLK_K4_V4S && c.held && h->k4_held_ok; p.info_fold = p.held ? 2 : 0;
-    p.triple = PlkV4TPlan(); p.info_triple = 0; p.info_quad = 0;
-    if (c.variant == PLK_K4_V4S && c.bad.empty()) {
-        /* three-leaf tables, and the categories in groups to make room for them: derived from the checked pair-table formats
-         * and replayed against them; formats that do not replay are not run -- the checked ones are, and the error text says why.
-         * More than one group needs the pair-product instantiation (the only one compiled with phases). */
-        const PlkPairTablesOpt po = plk_pair_tables_opt(h->opt_pair_tables);
-        const bool can_group = c.pair && c.fold && p.held && h->k4_pair_ok && h->k4_groups_ok;
-        /* the plan is plk_k4_choose's; the engine only takes the groups back where the instantiation with phases cannot be described */
-        PlkV4TPlan tp = c.triple;
-        auto one_group = [&]() { return plk_v4t_plan(h->fpt, h->nchar, h->C, h->S, stream_cus(h), c.tip_base, po.triple, 1, po.quad, node_codes); };
-        if (tp.groups > 1 && !can_group) tp = one_group();
-        if (tp.nodes + tp.quads > 0 && tp.groups > 1 &&
+    if (c.variant == PLK_K4_V4S) {
+        /* the formats that run, derived from the checked ones and replayed against them (plk_k4_stream: tables and category groups,
+         * the folded and the pair-product stream, the barrier); the engine's part is the room for the partial sums of the groups */
+        PlkK4StreamCaps caps = h->k4_caps;
+        if (c.triple.nodes + c.triple.quads > 0 && c.triple.groups > 1 && plk_k4_stream_can_group(c, caps) &&
             dev_reserve(h, &h->d_llstate, &h->llstate_cap, (size_t)nunits * PLK_V4S_UNIT * 3 / 2) != PLK_OK) {
             /* no room for the partial sums: one group */
             h->err.clear();
             (void)hipGetLastError();
-            tp = one_group();
+            caps.partial_sums = false;
         }
-        for (int attempt = 0; attempt < 2 && tp.nodes + tp.quads > 0; attempt++) {
-            std::string bad;
-            if (tp.quads > 0) {
-                /* four-leaf tables and the three-leaf tables beside them, from the plan's lists */
-                plk_fused_v4q_build(h->fpt, h->pg.slots_needed, h->nchar, node_codes, tp.tri_at, tp.quad_at, tp.quad_shape, true, h->fpt_t);
-                bad = plk_fused_check_v4q(h->N, h->indptr.data(), h->indices.data(), h->fpt, h->fpt_t, h->nchar, node_codes);
-                if (bad.empty() && h->fpt_t.nquads != tp.quads) bad = "v4q program: the builder took another number of four-leaf nodes than the plan";
-            } else {
-                plk_fused_v4t_build(h->fpt, h->pg.slots_needed, h->nchar, tp.extra_bytes, true, h->fpt_t);
-                bad = plk_fused_check_v4t(h->N, h->indptr.data(), h->indices.data(), h->fpt, h->fpt_t, h->nchar);
-            }
-            const size_t lds = plk_fused_v4s_lds_bytes(h->fpt_t, h->nchar, tp.Cg);
-            if (bad.empty() && h->fpt_t.ntriples != tp.nodes) bad = "v4t program: the builder took another number of nodes than the plan";
-            if (bad.empty()) {
-                plk_fused_v4s_words(h->fpt_t, h->nchar, h->C, c.tip_base, h->fv4s_t, tp.Cg);
-                bad = plk_fused_check_v4s(h->fpt_t, h->fv4s_t, h->nchar, h->C, c.tip_base, lds);
-            }
-            /* fewer observations: the stream fits the room reserved for the checked one */
-            if (bad.empty() && h->fv4s_t.chunks > h->fv4s.chunks) bad = "v4t program: more chunks than the checked stream";
-            if (bad.empty() && tp.groups > 1) {
-                /* the phases exist in the pair-product instantiation only: a rewritten stream that form does not take runs in one group */
-                plk_fused_v4p_build(h->fv4s_t, h->fv4p);
-                if (h->fv4p.words.empty() || !plk_fused_check_v4p(h->fv4s_t, h->fv4p).empty()) {
-                    tp = one_group();
-                    continue;
-                }
-            }
-            if (bad.empty()) {
-                h->fpt = std::move(h->fpt_t); h->fv4s = std::move(h->fv4s_t);
-                p.k4.lds = lds; p.lds = lds;
-                p.triple = tp;
-                p.info_triple = 1 | (long)std::min(tp.groups, 15) << 4 | (long)std::min(tp.nodes, 65535) << 8;
-                p.info_quad = tp.quads > 0 ? 1 | (long)std::min(tp.quads, 65535) << 8 : 0;
-            } else h->err = "internal: " + bad + (tp.quads > 0 ? " (the stream without four-leaf and three-leaf tables runs)" : " (the stream without three-leaf tables runs)");
-            break;
-        }
-    }
-    if (c.variant == PLK_K4_V4S && c.fold) {
-        /* the folded stream is derived from the checked one and replayed against it; a fold that does not replay is not
-         * run: the checked stream is, and the engine's error text says why */
-        plk_fused_v4s_fold(h->fv4s, h->fv4s_fold);
-        const std::string bad = plk_fused_check_v4s_fold(h->fv4s, h->fv4s_fold);
-        if (bad.empty()) {
-            const PlkFusedV4SFold &fo = h->fv4s_fold;
-            p.fold = true;
-            p.info_fold |= 1 | (long)(fo.scale_slots & 15) << 4 | (long)std::min(fo.standalone_scale, 255) << 8 |
-                           (long)std::min(fo.nadv[0], 255) << 16 | (long)std::min(fo.nadv[1], 127) << 24;
-        } else h->err = "internal: " + bad + " (the unfolded op stream runs)";
-    }
-    p.pairmul = false; p.info_pairmul = 0;
-    if (c.variant == PLK_K4_V4S && c.pair && p.fold && p.held && h->k4_pair_ok) {
-        /* derived from the checked stream and replayed against it like the fold.  Where the form does not apply (a table
-         * field beyond its 13 bits, an observation kind without a handler on its buffer) nothing is derived and the folded
-         * stream runs; a derived stream that does not replay is not run either, and the error text says why */
-        plk_fused_v4p_build(h->fv4s, h->fv4p);
-        if (!h->fv4p.words.empty()) {
-            const std::string bad = plk_fused_check_v4p(h->fv4s, h->fv4p);
-            if (bad.empty()) { p.pairmul = true; p.info_pairmul = 1 | (long)std::min(h->fv4p.npair, 65535) << 8; }
-            else h->err = "internal: " + bad + " (the folded op stream runs)";
-        }
+        p.k4s = plk_k4_stream(h->N, h->indptr.data(), h->indices.data(), h->pg, sh, c, caps, h->fpt, std::move(fv4s));
+        p.lds = p.k4s.lds;
+        if (!p.k4s.note.empty()) h->err = p.k4s.note;
     }
     const int ntips = (int)h->tip_edge.size();
     if (c.variant == PLK_K4_CPP || c.variant == PLK_K4_ASM) {
@@ -2325,24 +2251,19 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
      * are built from the unrounded P after it (k_build_tables_pt) */
     const PlkFusedPT &f = h->fpt;
     p.pair_tables = true; p.npairs = f.npairs;
-    const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? (p.pairmul ? h->fv4p.words : p.fold ? h->fv4s_fold.words : h->fv4s.words) : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
-    if (c.variant == PLK_K4_V4S && c.sync_auto) {
-        /* the barrier of the streamed form, decided again on the formats that run (plk_k4_choose decided on the plan's): the
-         * categories resident at a time, the matrix stream and the op words of one category as uploaded */
-        const int Cg = p.triple.nodes + p.triple.quads > 0 && p.triple.Cg > 0 ? p.triple.Cg : h->C;
-        p.k4.sync = plk_v4s_auto_sync(Cg, f.mat_edge.size(), (p.pairmul ? h->fv4p.stride : p.fold ? h->fv4s_fold.stride : h->fv4s.stride));
-    }
+    const PlkFusedV4S &vs = p.k4s.fv4s;
+    const std::vector<unsigned> &words = c.variant == PLK_K4_V4S ? p.k4s.words() : c.variant == PLK_K4_V4 ? h->fv4.words : f.words;
     if ((rc = dev_upload(h, &h->d_words_pt, words.data(), words.size()))) return rc;
     /* d_obs_row before the pair-table lists: the order in which these buffers were first allocated when the kernels were
      * measured (with it after them, the streamed kernel at 1.25M sites of BASELINE config 3 ran 0.3 % longer) */
-    if (c.variant == PLK_K4_V4S && (rc = dev_upload(h, &h->d_obs_row, h->fv4s.obs_row.data(), h->fv4s.obs_row.size()))) return rc;
+    if (c.variant == PLK_K4_V4S && (rc = dev_upload(h, &h->d_obs_row, vs.obs_row.data(), vs.obs_row.size()))) return rc;
     if ((rc = upload_pair_table_lists(h))) return rc;
     if (c.variant == PLK_K4_V4S) {
         /* streamed codes: the stream itself from the resident code rows */
-        const size_t total = (size_t)nunits * h->fv4s.chunks * PLK_V4S_UNIT;
+        const size_t total = (size_t)nunits * vs.chunks * PLK_V4S_UNIT;
         if (total > h->cstream_cap || (total + 255) / 256 > 0x7fffffffu) { h->err = "internal: code stream size"; return PLK_E_ARG; }
         hipLaunchKernelGGL(k_build_code_stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_codes, h->Spad, nunits,
-                           h->d_obs_row, h->fv4s.nobs, h->d_row_nodes, (int)f.row_node.size(), h->nchar, h->fv4s.chunks,
+                           h->d_obs_row, vs.nobs, h->d_row_nodes, (int)f.row_node.size(), h->nchar, vs.chunks,
                            f.nquads > 0 ? h->d_quad_lut : (const uint8_t *)nullptr, h->d_cstream);
         HIPCHK(h, hipGetLastError());
     }
@@ -2494,7 +2415,7 @@ static int upload_formats(plk_engine *h)
         if (rc) return rc;
     }
     p.info_exec_flops = ll_exec_flops(h, p);
-    h->plan = p;
+    h->plan = std::move(p);
     h->fmt_dirty = false;
     h->tables_dirty = true;
     return PLK_OK;
@@ -2609,20 +2530,22 @@ static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool 
         if (c.variant == PLK_K4_V4S) {
             FusedV4SArgs sa;
             sa.pt = pa;
-            sa.pt.nwords = (int)(p.pairmul ? h->fv4p.stride : p.fold ? h->fv4s_fold.stride : h->fv4s.stride);
-            sa.stream = h->d_cstream; sa.chunks = h->fv4s.chunks; sa.first_y = h->fv4s.first_y[0];
-            sa.sync = c.sync;
-            h->info_ll_barrier = (sa.sync == 0 ? 1 : sa.sync == 1 ? 2 : 3) | (c.sync_auto ? 16 : 0);
-            sa.first_y1 = p.pairmul ? h->fv4p.first_y1[0] : 0u; sa.first_b1 = p.pairmul ? h->fv4p.first_b1 : 0u;
-            sa.groups = p.triple.groups; sa.cg = p.triple.Cg > 0 ? p.triple.Cg : h->C;
+            const PlkK4Stream &r = p.k4s;
+            const bool pairmul = r.runs == PlkK4Stream::PAIR;
+            sa.pt.nwords = (int)r.stride();
+            sa.stream = h->d_cstream; sa.chunks = r.fv4s.chunks; sa.first_y = r.fv4s.first_y[0];
+            sa.sync = r.sync;
+            h->info_ll_barrier = (sa.sync == 0 ? 1 : sa.sync == 1 ? 2 : 3) | (r.sync_auto ? 16 : 0);
+            sa.first_y1 = pairmul ? r.pair.first_y1[0] : 0u; sa.first_b1 = pairmul ? r.pair.first_b1 : 0u;
+            sa.groups = r.triple.groups; sa.cg = r.triple.Cg > 0 ? r.triple.Cg : h->C;
             sa.part_sum = h->d_llstate;
             sa.part_exp = h->d_llstate ? reinterpret_cast<int *>(h->d_llstate + (size_t)((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT) * PLK_V4S_UNIT) : nullptr;
             if (sa.groups > 1) {
                 /* phases: only with the plan's checks behind it (pair products, room for the partial sums of every unit) */
-                if (!p.pairmul || !h->d_llstate || h->llstate_cap < (size_t)((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT) * PLK_V4S_UNIT * 3 / 2) { h->err = "internal: category groups without their plan"; return PLK_E_ARG; }
+                if (!pairmul || !h->d_llstate || h->llstate_cap < (size_t)((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT) * PLK_V4S_UNIT * 3 / 2) { h->err = "internal: category groups without their plan"; return PLK_E_ARG; }
                 hipLaunchKernelGGL((k_ll_fused4_v4s<768, true, true, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
-            } else if (p.pairmul) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
-            else if (p.held) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            } else if (pairmul) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
+            else if (r.held) hipLaunchKernelGGL((k_ll_fused4_v4s<768, true>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
             else hipLaunchKernelGGL((k_ll_fused4_v4s<768, false>), dim3(grid), dim3(p.block), p.lds, h->stream, sa);
         } else if (c.variant == PLK_K4_V4) {
             FusedV4Args va;
@@ -2758,7 +2681,7 @@ static int ll_impl(plk_engine *h, double *site_ll_out, int where, double *sum_ou
     default: rc = launch_ll_generic(h, p, d_out, want_sum, &npartials); break;
     }
     if (rc) return rc;
-    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.info_fold; h->info_ll_pairmul = p.info_pairmul; h->info_ll_triple = p.info_triple; h->info_ll_quad = p.info_quad; h->info_ll_exec_flops = p.info_exec_flops;
+    h->info_ll_kernel = p.family; h->info_ll_variant = p.info_variant; h->info_ll_form = p.info_form; h->info_ll_fold = p.k4s.info_fold; h->info_ll_pairmul = p.k4s.info_pairmul; h->info_ll_triple = p.k4s.info_triple; h->info_ll_quad = p.k4s.info_quad; h->info_ll_exec_flops = p.info_exec_flops;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->evk[evi][1], h->stream));
     h->evk_pending[evi] = true;

@@ -2437,7 +2437,7 @@ static inline std::string plk_fused_check_cpp(int N, const PlkProgram &pg, const
 }
 
 /* ------------------------------------------------------------------------------------------------------------ */
-/* which k = 4 ll kernel runs: the one place that decides, for the engine and for the CPU test alike              */
+/* which k = 4 ll kernel runs and which formats: the one place that decides, for the engine and the CPU tests  */
 /* ------------------------------------------------------------------------------------------------------------ */
 
 enum PlkK4Variant { PLK_K4_NONE = 0, PLK_K4_CPP, PLK_K4_ASM, PLK_K4_ASM_PT, PLK_K4_V4, PLK_K4_V4S };
@@ -2493,10 +2493,10 @@ struct PlkK4Choice {
     size_t lds = 0;                                  /* dynamic LDS of the launch */
     unsigned tip_base = 0;                           /* v4 / v4s: LDS address of the table image = static LDS of the kernel */
     int warm = 1, sync = 2;                          /* pair-table kernels: the measurement bits of PLK_OPT_PAIR_TABLES */
-    bool sync_auto = false;                          /* v4s: sync is plk_v4s_auto_sync's choice, not an option bit's */
-    int fold = 1, held = 1;                          /* v4s: folded op stream, first chunks held across the categories */
+    bool sync_auto = false;                          /* v4s: no option bit forces sync; plk_k4_stream decides it (plk_v4s_auto_sync) on the formats that run */
+    int fold = 1, held = 1;                          /* v4s, asked for: folded op stream, first chunks held across the categories */
     int pair = 0;                                    /* v4s: the pair-product form is asked for and the program is within its 3 slots */
-    PlkV4TPlan triple;                               /* v4s: three-leaf tables and category groups (plk_v4t_plan; nodes == 0: not taken) */
+    PlkV4TPlan triple;                               /* v4s: the plan of three-leaf / four-leaf tables and category groups (plk_v4t_plan; nodes + quads == 0: none) */
     std::string bad;                                 /* the replay check of the chosen variant's formats; empty: fine */
 };
 
@@ -2507,6 +2507,8 @@ struct PlkK4Choice {
  * each with as many cherries as its LDS limit takes; forced modes 2, 3, 5, 6 have one candidate.  Then the assembly
  * interpreter, then the C++ interpreter, then PLK_K4_NONE.  Builds the formats of the chosen variant (fu | fpt, fv4, fv4s)
  * and replays them once (bad).
+ * For the streamed form that is the kernel, the checked formats and the wishes (fold, held, pair, the table plan, the barrier's
+ * option bits): what runs is plk_k4_stream's to say, from this choice and from what the engine could obtain.
  */
 static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, const PlkProgram &pg, const PlkK4Shape &sh, bool allow_stream,
                                         PlkFused &fu, PlkFusedPT &fpt, PlkFusedV4 &fv4, PlkFusedV4S &fv4s)
@@ -2541,14 +2543,6 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
                  * the formats themselves are derived from fpt and replayed like the fold and the pair products */
                 if (ch.bad.empty())
                     ch.triple = plk_v4t_plan(fpt, nchar, sh.C, sh.S, sh.num_cus, st, po.triple, ch.pair && ch.fold && ch.held ? po.groups : 1, po.quad, sh.node_codes);
-                if (ch.sync_auto) {
-                    /* on the plan: every three-leaf table and every (cherry, cherry) table takes one product out of the matrix
-                     * stream, every ((cherry, leaf), leaf) table two; the checked stream's op words bound those of the derived ones */
-                    const bool tables = ch.triple.nodes + ch.triple.quads > 0;
-                    size_t absorbed = tables ? (size_t)ch.triple.nodes : 0;
-                    if (tables) for (int shp : ch.triple.quad_shape) absorbed += shp == PLK_V4Q_A ? 2 : 1;
-                    ch.sync = plk_v4s_auto_sync(tables && ch.triple.Cg > 0 ? ch.triple.Cg : sh.C, fpt.mat_edge.size() - std::min(absorbed, fpt.mat_edge.size()), fv4s.stride);
-                }
                 return ch;
             }
         }
@@ -2607,6 +2601,111 @@ static inline PlkK4Choice plk_k4_choose(int N, const int *ip, const int *ix, con
         ch.bad = plk_fused_check_cpp(N, pg, fu, nchar, ch.D, NS, lds_cpp);
     }
     return ch;
+}
+
+/*
+ * The formats the streamed form runs, derived from the checked ones of a PLK_K4_V4S choice by one host-only sequence, for the
+ * engine and for the CPU tests alike; what the engine could obtain from the runtime comes in as PlkK4StreamCaps.
+ *   1. tables (ch.triple): the groups are taken back (plk_v4t_plan with one group) where the instantiation with phases cannot run
+ *      or the partial sums have no room; the rewritten format and its words are built and replayed against the checked ones, at
+ *      most twice (a rewritten stream the pair-product form does not take is planned again with one group);
+ *   2. the folded stream, 3. the pair-product stream (with the fold, the held chunks and the capability): if derived and replayed;
+ *   4. the barrier, where no option bit forces it: plk_v4s_auto_sync on what runs.
+ * A form that does not replay is not run: the one before it is, and `note` says why (the last reason stays).
+ */
+/* k_ll_fused4_v4s<768, true>, <768, true, true> and <768, true, true, true> can run; there is room for the partial sums of the phases */
+struct PlkK4StreamCaps { bool held = true, pair = true, groups = true, partial_sums = true; };
+
+struct PlkK4Stream {
+    PlkFusedV4S fv4s;                               /* the stream that runs (of the rewritten format where tables were taken) ... */
+    PlkFusedV4SFold fold; PlkFusedV4P pair;         /* ... its folded form and its pair-product form, where derived */
+    enum Words { CHECKED, FOLDED, PAIR } runs = CHECKED;      /* the op words uploaded: fv4s.words, fold.words or pair.words */
+    bool held = false;                              /* the first chunks are held across the categories */
+    PlkV4TPlan triple;                              /* the tables taken (nodes + quads == 0: none) and their category groups */
+    size_t lds = 0;                                 /* dynamic LDS of the launch */
+    int sync = 2; bool sync_auto = false;           /* the barrier as launched; no option bit forced it */
+    long info_fold = 0, info_pairmul = 0, info_triple = 0, info_quad = 0;     /* PLK_INFO_LL_FOLD, _PAIRMUL, _TRIPLE, _QUAD */
+    std::string note;                               /* why a derived form does not run ("internal: ..."), or empty */
+    const std::vector<unsigned> &words() const { return runs == PAIR ? pair.words : runs == FOLDED ? fold.words : fv4s.words; }
+    size_t stride() const { return runs == PAIR ? pair.stride : runs == FOLDED ? fold.stride : fv4s.stride; }
+    int Cg(int C) const { return triple.nodes + triple.quads > 0 && triple.Cg > 0 ? triple.Cg : C; }     /* categories resident at a time */
+};
+
+/* more than one group: only in the pair-product instantiation, with the fold and the held chunks (the engine reserves the partial sums only then) */
+static inline bool plk_k4_stream_can_group(const PlkK4Choice &ch, const PlkK4StreamCaps &caps) { return ch.pair && ch.fold && ch.held && caps.held && caps.pair && caps.groups; }
+
+/* steps 2 and 3 on r.fv4s; pair_kept: r.pair is already that stream's pair-product form, replayed */
+static inline void plk_k4_stream_fold_pair(PlkK4Stream &r, bool fold, bool pair, bool pair_kept = false)
+{
+    r.runs = PlkK4Stream::CHECKED; r.info_fold = r.held ? 2 : 0; r.info_pairmul = 0;
+    if (fold) {
+        plk_fused_v4s_fold(r.fv4s, r.fold);
+        const std::string bad = plk_fused_check_v4s_fold(r.fv4s, r.fold);
+        if (bad.empty()) {
+            r.runs = PlkK4Stream::FOLDED;
+            r.info_fold |= 1 | (long)(r.fold.scale_slots & 15) << 4 | (long)std::min(r.fold.standalone_scale, 255) << 8 |
+                           (long)std::min(r.fold.nadv[0], 255) << 16 | (long)std::min(r.fold.nadv[1], 127) << 24;
+        } else r.note = "internal: " + bad + " (the unfolded op stream runs)";
+    }
+    if (!pair || r.runs != PlkK4Stream::FOLDED || !r.held) return;
+    /* where the form does not apply (a table field beyond its 13 bits, an observation kind without a handler on its buffer)
+     * nothing is derived and the folded stream runs */
+    if (!pair_kept) plk_fused_v4p_build(r.fv4s, r.pair);
+    if (r.pair.words.empty()) return;
+    const std::string bad = pair_kept ? "" : plk_fused_check_v4p(r.fv4s, r.pair);
+    if (bad.empty()) { r.runs = PlkK4Stream::PAIR; r.info_pairmul = 1 | (long)std::min(r.pair.npair, 65535) << 8; }
+    else r.note = "internal: " + bad + " (the folded op stream runs)";
+}
+
+/* ch: a PLK_K4_V4S choice with empty bad, of this tree, program and shape; fpt, fv4s: its checked formats.  fpt becomes the
+ * pair-table format that runs (the engine's three kernel families share that member), the rest is returned */
+static inline PlkK4Stream plk_k4_stream(int N, const int *ip, const int *ix, const PlkProgram &pg, const PlkK4Shape &sh, const PlkK4Choice &ch,
+                                        const PlkK4StreamCaps &caps, PlkFusedPT &fpt, PlkFusedV4S fv4s)
+{
+    PlkK4Stream r;
+    r.fv4s = std::move(fv4s); r.held = ch.held && caps.held; r.lds = ch.lds; r.sync = ch.sync; r.sync_auto = ch.sync_auto;
+    const PlkPairTablesOpt po = plk_pair_tables_opt(sh.pair_tables);
+    PlkV4TPlan tp = ch.triple;
+    auto one_group = [&]() { return plk_v4t_plan(fpt, sh.nchar, sh.C, sh.S, sh.num_cus, ch.tip_base, po.triple, 1, po.quad, sh.node_codes); };
+    if (tp.groups > 1 && !plk_k4_stream_can_group(ch, caps)) tp = one_group();
+    if (tp.nodes + tp.quads > 0 && tp.groups > 1 && !caps.partial_sums) tp = one_group();
+    bool pair_kept = false;
+    for (int attempt = 0; attempt < 2 && tp.nodes + tp.quads > 0; attempt++) {
+        PlkFusedPT fpt_t; PlkFusedV4S fv4s_t;        /* the rewritten formats while they are derived and checked */
+        std::string bad;
+        if (tp.quads > 0) {
+            /* four-leaf tables and the three-leaf tables beside them, from the plan's lists */
+            plk_fused_v4q_build(fpt, pg.slots_needed, sh.nchar, sh.node_codes, tp.tri_at, tp.quad_at, tp.quad_shape, true, fpt_t);
+            bad = plk_fused_check_v4q(N, ip, ix, fpt, fpt_t, sh.nchar, sh.node_codes);
+            if (bad.empty() && fpt_t.nquads != tp.quads) bad = "v4q program: the builder took another number of four-leaf nodes than the plan";
+        } else {
+            plk_fused_v4t_build(fpt, pg.slots_needed, sh.nchar, tp.extra_bytes, true, fpt_t);
+            bad = plk_fused_check_v4t(N, ip, ix, fpt, fpt_t, sh.nchar);
+        }
+        const size_t lds = plk_fused_v4s_lds_bytes(fpt_t, sh.nchar, tp.Cg);
+        if (bad.empty() && fpt_t.ntriples != tp.nodes) bad = "v4t program: the builder took another number of nodes than the plan";
+        if (bad.empty()) {
+            plk_fused_v4s_words(fpt_t, sh.nchar, sh.C, ch.tip_base, fv4s_t, tp.Cg);
+            bad = plk_fused_check_v4s(fpt_t, fv4s_t, sh.nchar, sh.C, ch.tip_base, lds);
+        }
+        /* fewer observations: the stream fits the room reserved for the checked one */
+        if (bad.empty() && fv4s_t.chunks > r.fv4s.chunks) bad = "v4t program: more chunks than the checked stream";
+        if (bad.empty() && tp.groups > 1) {
+            /* the phases exist in the pair-product instantiation only: a rewritten stream that form does not take runs in one group */
+            plk_fused_v4p_build(fv4s_t, r.pair);
+            if (r.pair.words.empty() || !plk_fused_check_v4p(fv4s_t, r.pair).empty()) { tp = one_group(); continue; }
+            pair_kept = true;
+        }
+        if (bad.empty()) {
+            fpt = std::move(fpt_t); r.fv4s = std::move(fv4s_t); r.lds = lds; r.triple = tp;
+            r.info_triple = 1 | (long)std::min(tp.groups, 15) << 4 | (long)std::min(tp.nodes, 65535) << 8;
+            r.info_quad = tp.quads > 0 ? 1 | (long)std::min(tp.quads, 65535) << 8 : 0;
+        } else r.note = "internal: " + bad + (tp.quads > 0 ? " (the stream without four-leaf and three-leaf tables runs)" : " (the stream without three-leaf tables runs)");
+        break;
+    }
+    plk_k4_stream_fold_pair(r, ch.fold != 0, ch.pair && caps.pair, pair_kept);
+    if (r.sync_auto) r.sync = plk_v4s_auto_sync(r.Cg(sh.C), fpt.mat_edge.size(), r.stride());
+    return r;
 }
 
 /* ------------------------------------------------------------------------------------------------------------ */

@@ -119,9 +119,11 @@ static std::string check_tree(const Tree &t, const std::vector<char> &has, int n
     }
     if (pg.slots_needed > 3) {
         if (!vp.words.empty()) return "a 4-slot program got a pair-product stream";
-        PlkFusedV4SFold fo;
-        plk_fused_v4s_fold(vs, fo);
-        if (!plk_fused_check_v4s_fold(vs, fo).empty()) return "the folded stream of a 4-slot program";
+        /* asked for pair products all the same, the engine's sequence runs the folded stream */
+        PlkK4Stream st;
+        st.fv4s = vs; st.held = true;
+        plk_k4_stream_fold_pair(st, true, true);
+        if (st.runs != PlkK4Stream::FOLDED || !st.note.empty() || !plk_fused_check_v4s_fold(vs, st.fold).empty()) return "the folded stream of a 4-slot program";
         g_taken4++;
         return "";
     }
@@ -133,6 +135,13 @@ static std::string check_tree(const Tree &t, const std::vector<char> &has, int n
     }
     bad = plk_fused_check_v4p(vs, vp);
     if (!bad.empty()) return bad;
+    {
+        /* and the engine's sequence runs exactly this stream */
+        PlkK4Stream st;
+        st.fv4s = vs; st.held = true;
+        plk_k4_stream_fold_pair(st, true, true);
+        if (st.runs != PlkK4Stream::PAIR || !st.note.empty() || st.pair.words != vp.words || st.stride() != vp.stride) return "the pair-product stream is not the one that runs";
+    }
     g_taken3++;
 
     std::vector<std::vector<PlkV4SOp>> pops(C);

@@ -331,20 +331,17 @@ static std::string check_tree(const Tree &t, int nchar, const std::vector<int> &
             const int Cg = (C + G - 1) / G;
             const size_t lds = plk_fused_v4s_lds_bytes(out, nchar, Cg);
             if (lds > plk_pt_lds_limit(1024)) continue;
-            PlkFusedV4S vs;
+            PlkK4Stream st;
+            PlkFusedV4S &vs = st.fv4s;
             plk_fused_v4s_words(out, nchar, C, 0, vs, Cg);
             bad = plk_fused_check_v4s(out, vs, nchar, C, 0, lds);
             if (!bad.empty()) return plk_fmt("C %ld in %ld groups: ", C, G) + bad;
             if (Cg > 1 && plk_fused_check_v4s(out, vs, nchar, C, 0, lds - 32).empty()) return "a launch with too little LDS was accepted";
-            PlkFusedV4SFold fo;
-            plk_fused_v4s_fold(vs, fo);
-            bad = plk_fused_check_v4s_fold(vs, fo);
-            if (!bad.empty()) return bad;
-            if (pg.slots_needed <= PLK_V4P_STACK_SLOTS) {
-                PlkFusedV4P vp;
-                plk_fused_v4p_build(vs, vp);
-                if (!vp.words.empty() && !(bad = plk_fused_check_v4p(vs, vp)).empty()) return bad;
-            }
+            /* what the engine derives from this stream: the fold, and within 3 stack slots the pair products, each replayed */
+            st.held = true;
+            plk_k4_stream_fold_pair(st, true, pg.slots_needed <= PLK_V4P_STACK_SLOTS);
+            if (!st.note.empty()) return st.note;
+            if (st.runs == PlkK4Stream::CHECKED) return "the fold of the rewritten stream does not run";
         }
     /* values */
     Values v;
@@ -538,12 +535,17 @@ int main(int argc, char **argv)
         int nA = 0, nB = 0;
         for (const PlkV4QCand &c : qc) (c.shape == PLK_V4Q_A ? nA : nB)++;
         const PlkV4TPlan &tp = forced.triple;
-        plk_fused_v4q_build(fpt, pg.slots_needed, 5, masks.data(), tp.tri_at, tp.quad_at, tp.quad_shape, true, out);
+        /* the formats the engine runs under that plan, every capability given (plk_k4_stream builds and replays them) */
+        PlkK4Shape shf = {5, 4, 10000000, 256, 1 + 16384, 1, 0, {4608, 4608, 4608}};
+        shf.node_codes = masks.data();
+        out = fpt;
+        const PlkK4Stream run = plk_k4_stream(t.N, t.ip.data(), t.ix.data(), pg, shf, forced, PlkK4StreamCaps(), out, fv4s);
+        if (!run.note.empty()) return fail("config 3 plan", run.note);
+        if (run.triple.quads != tp.quads || run.triple.nodes != tp.nodes || run.triple.groups != tp.groups) return fail("config 3 plan", "the plan was not taken as chosen");
         const std::string b2 = plk_fused_check_v4q(t.N, t.ip.data(), t.ix.data(), fpt, out, 5, masks.data());
         if (!b2.empty()) return fail("config 3 plan", b2);
-        PlkFusedV4S vs;
-        plk_fused_v4s_words(out, 5, 4, 4608, vs, tp.Cg);
-        const std::string b3 = plk_fused_check_v4s(out, vs, 5, 4, 4608, plk_fused_v4s_lds_bytes(out, 5, tp.Cg));
+        const PlkFusedV4S &vs = run.fv4s;
+        const std::string b3 = plk_fused_check_v4s(out, vs, 5, 4, 4608, run.lds);
         if (!b3.empty()) return fail("config 3 stream", b3);
         printf("config3 %d %d %d %d %d %d %d %d %d %d %d\n", nA, nB, tp.groups, out.nquads, out.ntriples, out.units, (int)out.mat_edge.size(), vs.nobs,
                little.triple.quads, only3.triple.quads, never.triple.quads);

@@ -1,11 +1,11 @@
 /*
  * tests/synccheck_main.cpp -- CPU driver for the barrier default of the streamed k = 4 kernel (plk_v4s_auto_sync and the
- * sync / sync_auto fields of plk_k4_choose in phyly_amd/csrc/plk_program.h), built with AddressSanitizer + UBSan by
- * tests/test_k4_sync_host.py.
+ * sync / sync_auto fields of plk_k4_stream in phyly_amd/csrc/plk_program.h: the value that is launched), built with
+ * AddressSanitizer + UBSan by tests/test_k4_sync_host.py.
  *
  * Argument: the tree of BASELINE config 3 as tests/pairmulcheck_main.cpp reads it (nchar 5; every leaf is given the four
  * codes of fully observed data, so that four-leaf tables qualify).  For a list of (categories, sites, CUs) it asks
- * plk_k4_choose for the plan and requires:
+ * plk_k4_choose for the plan and plk_k4_stream, every capability given, for the formats that run, and requires:
  *   - without sync bits: sync_auto, and sync = 0 exactly where one category is resident at a time (one rate category, or a
  *     plan with a group per category) and the matrix stream left by the plan's tables plus the op words fit 16 KB, else 2;
  *   - both outcomes occur in the list, and BASELINE config 3 itself (4 categories, 10M sites, 256 CUs) is a plan of four
@@ -60,13 +60,18 @@ int main(int argc, char **argv)
         PlkK4Shape sh = {nchar, cs.C, cs.S, cs.cus, 1, 1, 0, {0, 0, 0}};
         sh.node_codes = masks.data();
         PlkFused fu; PlkFusedPT fpt; PlkFusedV4 fv4; PlkFusedV4S fv4s;
-        const PlkK4Choice ch = plk_k4_choose(N, ip.data(), ix.data(), pg, sh, true, fu, fpt, fv4, fv4s);
-        if (!ch.bad.empty() || ch.variant != PLK_K4_V4S) { fprintf(stderr, "C %d S %ld: not the streamed form (%s)\n", cs.C, cs.S, ch.bad.c_str()); return 1; }
+        const PlkK4Choice chosen = plk_k4_choose(N, ip.data(), ix.data(), pg, sh, true, fu, fpt, fv4, fv4s);
+        if (!chosen.bad.empty() || chosen.variant != PLK_K4_V4S) { fprintf(stderr, "C %d S %ld: not the streamed form (%s)\n", cs.C, cs.S, chosen.bad.c_str()); return 1; }
+        const size_t checked_nmat = fpt.mat_edge.size();
+        const PlkK4Stream ch = plk_k4_stream(N, ip.data(), ix.data(), pg, sh, chosen, PlkK4StreamCaps(), fpt, fv4s);
+        if (!ch.note.empty()) { fprintf(stderr, "C %d S %ld: %s\n", cs.C, cs.S, ch.note.c_str()); return 1; }
         const bool tables = ch.triple.nodes + ch.triple.quads > 0;
         const int Cg = tables && ch.triple.Cg > 0 ? ch.triple.Cg : cs.C;
-        size_t nmat = fpt.mat_edge.size();
+        /* the matrix stream the plan's tables leave: counted from the plan, and what the format that runs must hold */
+        size_t nmat = checked_nmat;
         if (tables) { nmat -= (size_t)ch.triple.nodes; for (int s : ch.triple.quad_shape) nmat -= s == PLK_V4Q_A ? 2 : 1; }
-        const int want = Cg == 1 && (nmat + 1) * 128 + fv4s.stride * 4 <= 16384 ? 0 : 2;
+        if (nmat != fpt.mat_edge.size()) { fprintf(stderr, "C %d S %ld: %zu matrices run, the plan leaves %zu\n", cs.C, cs.S, fpt.mat_edge.size(), nmat); return 1; }
+        const int want = Cg == 1 && (nmat + 1) * 128 + ch.stride() * 4 <= 16384 ? 0 : 2;
         if (!ch.sync_auto || ch.sync != want) { fprintf(stderr, "C %d S %ld CUs %d: sync %d (auto %d), %d expected with %d resident categories\n", cs.C, cs.S, cs.cus, ch.sync, (int)ch.sync_auto, want, Cg); return 1; }
         if (ch.sync != cs.expect) { fprintf(stderr, "C %d S %ld CUs %d: sync %d, the plan (%d groups) was expected to give %d\n", cs.C, cs.S, cs.cus, ch.sync, ch.triple.groups, cs.expect); return 1; }
         (ch.sync ? n2 : n0)++;
@@ -77,8 +82,9 @@ int main(int argc, char **argv)
         const int forced[4] = {1, 0, 0, 2};
         for (int b = 0; b < 4; b++) {
             sh.pair_tables = 1 + bits[b];
-            const PlkK4Choice cf = plk_k4_choose(N, ip.data(), ix.data(), pg, sh, true, fu, fpt, fv4, fv4s);
-            if (cf.sync_auto || cf.sync != forced[b]) { fprintf(stderr, "C %d S %ld: + %ld gives sync %d\n", cs.C, cs.S, bits[b], cf.sync); return 1; }
+            const PlkK4Choice forced_choice = plk_k4_choose(N, ip.data(), ix.data(), pg, sh, true, fu, fpt, fv4, fv4s);
+            const PlkK4Stream cf = plk_k4_stream(N, ip.data(), ix.data(), pg, sh, forced_choice, PlkK4StreamCaps(), fpt, fv4s);
+            if (forced_choice.sync_auto || forced_choice.sync != forced[b] || cf.sync_auto || cf.sync != forced[b]) { fprintf(stderr, "C %d S %ld: + %ld gives sync %d\n", cs.C, cs.S, bits[b], cf.sync); return 1; }
         }
     }
     if (!n0 || !n2) { fprintf(stderr, "only one outcome in the list\n"); return 1; }

@@ -1,8 +1,8 @@
-"""CPU: the barrier default of the streamed k = 4 kernel (plk_v4s_auto_sync and plk_k4_choose's sync in
-phyly_amd/csrc/plk_program.h) under AddressSanitizer + UBSan.
+"""CPU: the barrier default of the streamed k = 4 kernel (plk_v4s_auto_sync and the sync that plk_k4_stream decides on the
+formats that run, phyly_amd/csrc/plk_program.h) under AddressSanitizer + UBSan.
 
 tests/synccheck_main.cpp is a stand-alone program: on the tree of BASELINE config 3 (written here from synth.Workload(3)) it
-asks for the plan of several (categories, sites, CUs) and requires the waves to meet before every category unless one
+asks for the plan of several (categories, sites, CUs) and what runs under it, and requires the waves to meet before every category unless one
 category is resident at a time and its matrix stream and op words fit the scalar cache, the option bits to force either, and
 config 3 itself, and the same alignment cut for 8 GPUs, to run without the barrier while plans below the gate keep it.
 """

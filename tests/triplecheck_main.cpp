@@ -253,7 +253,8 @@ static std::string check_tree(const Tree &t, int nchar, std::mt19937 &rng, bool 
                 const int Cg = (C + G - 1) / G;
                 const size_t lds = plk_fused_v4s_lds_bytes(out, nchar, Cg);
                 if (lds > plk_pt_lds_limit(1024)) continue;
-                PlkFusedV4S vs, vin;
+                PlkK4Stream st;
+                PlkFusedV4S &vs = st.fv4s, vin;
                 plk_fused_v4s_words(out, nchar, C, 0, vs, Cg);
                 bad = plk_fused_check_v4s(out, vs, nchar, C, 0, lds);
                 if (!bad.empty()) return plk_fmt("C %ld in %ld groups: ", C, G) + bad;
@@ -261,15 +262,11 @@ static std::string check_tree(const Tree &t, int nchar, std::mt19937 &rng, bool 
                 if (vs.nobs + (int)want != vin.nobs || vs.chunks > vin.chunks) return "observations of the rewritten stream";
                 /* one image too few must be refused */
                 if (Cg > 1 && plk_fused_check_v4s(out, vs, nchar, C, 0, lds - 32).empty()) return "a launch with too little LDS was accepted";
-                PlkFusedV4SFold fo;
-                plk_fused_v4s_fold(vs, fo);
-                bad = plk_fused_check_v4s_fold(vs, fo);
-                if (!bad.empty()) return bad;
-                if (pg.slots_needed <= PLK_V4P_STACK_SLOTS) {
-                    PlkFusedV4P vp;
-                    plk_fused_v4p_build(vs, vp);
-                    if (!vp.words.empty() && !(bad = plk_fused_check_v4p(vs, vp)).empty()) return bad;
-                }
+                /* what the engine derives from this stream: the fold, and within 3 stack slots the pair products, each replayed */
+                st.held = true;
+                plk_k4_stream_fold_pair(st, true, pg.slots_needed <= PLK_V4P_STACK_SLOTS);
+                if (!st.note.empty()) return st.note;
+                if (st.runs == PlkK4Stream::CHECKED) return "the fold of the rewritten stream does not run";
             }
         const std::vector<double> tout = build_tables(out, v);
         if (!same_values(in, out, v, tin, tout, codes, Spad, S)) return "the rewritten program computes other bits than the checked one";
