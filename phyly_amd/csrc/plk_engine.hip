@@ -145,6 +145,7 @@ struct plk_engine {
     uint8_t *d_quad_lut = nullptr;       /* four-leaf rows: PlkFusedPT::lut, [nquads][4][16] code -> rank (the stream builder's) */
     int *d_quad_codes = nullptr;         /* ... and [nquads][4][4] rank -> code (the table builder's; a rank that does not occur: the code of rank 0) */
     double *d_llstate = nullptr; size_t llstate_cap = 0;   /* category groups: per site the partial mixture sum, then the exponents */
+    PlkV4SRecord *d_v4s_rec = nullptr;   /* streamed k = 4 kernel: what its interpreter statement loads per category */
     int num_cus = 256;
     int2 *d_ops = nullptr;
     int4 *d_fops = nullptr;              /* fused-kernel program (C++ interpreter) */
@@ -1637,7 +1638,7 @@ extern "C" void plk_destroy(plk_engine *h)
     void *ptrs[] = {h->d_indptr, h->d_indices, h->d_preorder, h->d_Qn, h->d_edge_rates, h->d_cat_rates,
                     h->d_cat_prior, h->d_root_w, h->d_Pdd, h->d_P, h->d_dP, h->d_scratch, h->d_codes,
                     h->d_defs, h->d_B, h->d_w, h->d_ops, h->d_fops, h->d_words, h->d_mat_edge, h->d_edge_slot, h->d_op_edge, h->d_tip_edge, h->d_obs_nodes,
-                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_quad_lut, h->d_quad_codes, h->d_llstate, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
+                    h->d_words_pt, h->d_row_nodes, h->d_tabs, h->d_quad_lut, h->d_quad_codes, h->d_llstate, h->d_v4s_rec, h->d_cstream, h->d_obs_row, h->d_PS, h->d_tip, h->d_frag, h->d_root_wd, h->d_mops, h->d_u4pack, h->d_u4tip, h->d_uvmat, h->d_stage, h->d_exL, h->d_exF, h->d_exmask, h->d_exscr, h->d_slots, h->d_site_ll, h->d_partial, h->d_work,
                     h->d_cp_fops, h->d_cp_ops, h->d_cp_mat_edge, h->d_cp_tip_edge, h->d_cp_obs_nodes, h->d_cp_op_edge, h->d_cp_expo, h->d_cp_flag,
                     h->d_cp_PS, h->d_cp_tip, h->d_cp_out, h->d_cp_partial, h->d_mixD,
                     h->d_plPdd, h->d_plP, h->d_plrates, h->d_plstream, h->d_plT, h->d_pldense, h->d_plcodes};
@@ -2261,7 +2262,8 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     if (c.variant == PLK_K4_V4S) {
         /* streamed codes: the stream itself from the resident code rows */
         const size_t total = (size_t)nunits * vs.chunks * PLK_V4S_UNIT;
-        if (total > h->cstream_cap || (total + 255) / 256 > 0x7fffffffu) { h->err = "internal: code stream size"; return PLK_E_ARG; }
+        /* the kernel counts units in 32 bits (the grid of k_build_code_stream is the tighter bound: a unit has at least three chunks) */
+        if (total > h->cstream_cap || (total + 255) / 256 > 0x7fffffffu || nunits > 0x7fffffff) { h->err = "internal: code stream size"; return PLK_E_ARG; }
         hipLaunchKernelGGL(k_build_code_stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_codes, h->Spad, nunits,
                            h->d_obs_row, vs.nobs, h->d_row_nodes, (int)f.row_node.size(), h->nchar, vs.chunks,
                            f.nquads > 0 ? h->d_quad_lut : (const uint8_t *)nullptr, h->d_cstream);
@@ -2273,6 +2275,13 @@ static int upload_formats_fused4(plk_engine *h, LlPlan &p)
     if ((rc = dev_reserve(h, &h->d_PS, &h->ps_cap, (size_t)h->C * (f.mat_edge.size() + 1) * 16))) return rc;
     if ((rc = dev_reserve(h, &h->d_tip, &h->tip_cap, (size_t)h->C * f.units * h->nchar * 4))) return rc;
     HIPCHK(h, hipMemsetAsync(h->d_PS, 0, (size_t)h->C * (f.mat_edge.size() + 1) * 16 * sizeof(double), h->stream));
+    if (c.variant == PLK_K4_V4S) {
+        /* the records of the interpreter statement, last: they name the op words and the matrix streams where they now are, and
+         * hold the root weights of the model (a model change makes the formats stale, so this runs again after it) */
+        const std::vector<PlkV4SRecord> recs = plk_v4s_records(p.k4s, h->C, (unsigned)(f.units * h->nchar), (unsigned long long)(uintptr_t)h->d_words_pt,
+                                                               (unsigned long long)(uintptr_t)h->d_PS, f.mat_edge.size(), h->root_w.data());
+        if ((rc = dev_upload(h, &h->d_v4s_rec, recs.data(), recs.size()))) return rc;
+    }
     return PLK_OK;
 }
 
@@ -2533,11 +2542,11 @@ static int launch_ll_fused4(plk_engine *h, const LlPlan &p, double *d_out, bool 
             const PlkK4Stream &r = p.k4s;
             const bool pairmul = r.runs == PlkK4Stream::PAIR;
             sa.pt.nwords = (int)r.stride();
-            sa.stream = h->d_cstream; sa.chunks = r.fv4s.chunks; sa.first_y = r.fv4s.first_y[0];
+            sa.stream = h->d_cstream; sa.chunks = r.fv4s.chunks;
             sa.sync = r.sync;
             h->info_ll_barrier = (sa.sync == 0 ? 1 : sa.sync == 1 ? 2 : 3) | (r.sync_auto ? 16 : 0);
-            sa.first_y1 = pairmul ? r.pair.first_y1[0] : 0u; sa.first_b1 = pairmul ? r.pair.first_b1 : 0u;
             sa.groups = r.triple.groups; sa.cg = r.triple.Cg > 0 ? r.triple.Cg : h->C;
+            sa.rec = h->d_v4s_rec;
             sa.part_sum = h->d_llstate;
             sa.part_exp = h->d_llstate ? reinterpret_cast<int *>(h->d_llstate + (size_t)((S + PLK_V4S_UNIT - 1) / PLK_V4S_UNIT) * PLK_V4S_UNIT) : nullptr;
             if (sa.groups > 1) {

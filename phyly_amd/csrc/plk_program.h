@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -2630,6 +2631,40 @@ struct PlkK4Stream {
     size_t stride() const { return runs == PAIR ? pair.stride : runs == FOLDED ? fold.stride : fv4s.stride; }
     int Cg(int C) const { return triple.nodes + triple.quads > 0 && triple.Cg > 0 ? triple.Cg : C; }     /* categories resident at a time */
 };
+
+/* What the interpreter statement of the streamed kernel takes per category and per launch, one record per category in device
+ * memory: the prologue loads the first half with one scalar load and the epilogue the root weights with another (the offsets are
+ * named in tools/gen_fused4_v4.py), so that the statement's scalar operands are this record's address and the code stream.
+ * Written where the formats are uploaded; a model change makes the formats stale, so the weights follow it. */
+struct PlkV4SRecord {
+    unsigned long long ops, mstream;   /* device addresses of the category's op words and of its matrix stream */
+    unsigned first_y, first_y1, first_b1, pad;     /* LDS offset / 32 of the first and of the second observation's table in the
+                                                      category's resident image, bit offset of the second observation's code */
+    double w[4];                       /* root weights: 1 without a prior, 1/4 for the uniform one */
+};
+static_assert(sizeof(PlkV4SRecord) == 64 && offsetof(PlkV4SRecord, first_y) == 16 && offsetof(PlkV4SRecord, w) == 32, "the assembly text names these offsets");
+
+/* words, ps: device addresses of the uploaded op words (C streams of r.stride() dwords) and of the matrix streams (C x (nmat + 1)
+ * matrices); cat32: rows of a category's table image (table units x nchar); in phases category c reads the image of c % Cg */
+static inline std::vector<PlkV4SRecord> plk_v4s_records(const PlkK4Stream &r, int C, unsigned cat32, unsigned long long words, unsigned long long ps,
+                                                       size_t nmat, const double *root_w)
+{
+    std::vector<PlkV4SRecord> out((size_t)C);
+    const bool pairmul = r.runs == PlkK4Stream::PAIR;
+    const int cg = r.triple.groups > 1 && r.triple.Cg > 0 ? r.triple.Cg : C;     /* as the launch: phases only with more than one group */
+    for (int c = 0; c < C; c++) {
+        PlkV4SRecord &q = out[c];
+        q.ops = words + (unsigned long long)c * r.stride() * sizeof(unsigned);
+        q.mstream = ps + (unsigned long long)c * (nmat + 1) * 16 * sizeof(double);
+        const unsigned image = (unsigned)(c % cg) * cat32;
+        q.first_y = r.fv4s.first_y[0] + image;
+        q.first_y1 = pairmul ? r.pair.first_y1[0] + image : 0u;
+        q.first_b1 = pairmul ? r.pair.first_b1 : 0u;
+        q.pad = 0;
+        for (int i = 0; i < 4; i++) q.w[i] = root_w[i];
+    }
+    return out;
+}
 
 /* more than one group: only in the pair-product instantiation, with the fold and the held chunks (the engine reserves the partial sums only then) */
 static inline bool plk_k4_stream_can_group(const PlkK4Choice &ch, const PlkK4StreamCaps &caps) { return ch.pair && ch.fold && ch.held && caps.held && caps.pair && caps.groups; }

@@ -51,6 +51,10 @@ observation ops do not sit in LDS rows, they arrive packed four to a dword from 
   60 + d         MATVEC + POPMUL slot d, then SCALE
   Two prologues over one handler table: PLK_V4S_PROLOGUE requests the unit's first three chunks itself and waits for the
   first; PLK_V4S_PROLOGUE_HELD copies them from three 64-bit operands that the kernel loaded once per unit.
+  Scalar operands: %[rec], the category's record (PlkV4SRecord in plk_program.h: op stream, matrix stream, first_y, first_y1,
+  first_b1 at bytes 0 .. 27, the four root weights at 32 .. 63), and %[strm], the unit's code stream.  The prologue loads the
+  record's first half and moves its fields to where the handlers expect them; s[32:33] keeps the record's address and the
+  epilogue loads the weights from it into s[20:27], which are dead by then.
 
 Third emission mode, PAIR PRODUCTS (k_ll_fused4_v4s<768, true, true>, plk_fused4_v4s.h -> plk_fused4_v4p_asm.h): the streamed form for
 programs that need at most 3 stack slots.  The registers of stack slot 3 are a second look-up buffer: the row of
@@ -329,6 +333,13 @@ def emit(streamed=False, held=False, pairs=False):
 
     # ---- prologue ----
     pro = []
+    if streamed:
+        # what is per category and per launch comes from the category's record in device memory (PlkV4SRecord, plk_program.h):
+        # one scalar load, requested first so that the vector moves below run while it travels, into registers of the first
+        # matrix, which is requested after the record's fields have been moved out.  The record's address stays in s[32:33]
+        # for the root weights (epilogue).  The statement's scalar operands are the record and the stream pointer and nothing
+        # else: what the kernel's loop keeps in scalar registers stays there.
+        pro += ["s_load_dwordx8 s[36:43], %[rec], 0x0", "s_mov_b64 s[32:33], %[rec]"]
     for i in range(4):
         pro += ["v_mov_b32 v%d, 0" % (XA + 2 * i), "v_mov_b32 v%d, 0x3ff00000" % (XA + 2 * i + 1),
                 "v_mov_b32 v%d, 0" % (XB + 2 * i), "v_mov_b32 v%d, 0x3ff00000" % (XB + 2 * i + 1)]
@@ -348,22 +359,28 @@ def emit(streamed=False, held=False, pairs=False):
                 "global_load_dwordx2 %s, v76, s[34:35] offset:%d" % (pair(RING[0]), CHUNK_BYTES),
                 "global_load_dwordx2 %s, v76, s[34:35] offset:%d" % (pair(RING[1]), 2 * CHUNK_BYTES),
                 "s_add_u32 s34, s34, 0x%x" % (3 * CHUNK_BYTES), "s_addc_u32 s35, s35, 0"]
-    pro += ["v_mov_b32 v78, 0", "v_mov_b32 v79, 0"] + ([] if streamed else ["v_mov_b32 v77, %[clane]"]) + [
-            "s_mov_b64 s[20:21], %[ops]", "s_mov_b64 s[30:31], %[mstream]", "s_movk_i32 s27, 0xfc02", "s_mov_b32 m0, 0",
-            "s_load_dwordx16 s[68:83], s[20:21], 0x0", "s_load_dwordx16 s[84:99], s[20:21], 0x40",
+    pro += ["v_mov_b32 v78, 0", "v_mov_b32 v79, 0"] + ([] if streamed else ["v_mov_b32 v77, %[clane]"])
+    if streamed:
+        # s22 s23 (the op being executed: free until the first dispatch) and s28 hold first_y, first_y1, first_b1
+        pro += ["s_getpc_b64 s[24:25]", ".Lpcref_%=:", "s_add_u32 s26, s24, .Lh0_%=-.Lpcref_%=", "s_addc_u32 s25, s25, 0",
+                "s_movk_i32 s27, 0xfc02", "s_mov_b32 m0, 0", "s_waitcnt lgkmcnt(0)",
+                "s_mov_b64 s[20:21], s[36:37]", "s_mov_b64 s[30:31], s[38:39]",
+                "s_mov_b32 s22, s40", "s_mov_b32 s23, s41", "s_mov_b32 s28, s42"]
+    else:
+        pro += ["s_mov_b64 s[20:21], %[ops]", "s_mov_b64 s[30:31], %[mstream]", "s_movk_i32 s27, 0xfc02", "s_mov_b32 m0, 0"]
+    pro += ["s_load_dwordx16 s[68:83], s[20:21], 0x0", "s_load_dwordx16 s[84:99], s[20:21], 0x40",
             "s_add_u32 s20, s20, 0x80", "s_addc_u32 s21, s21, 0",
             "s_load_dwordx16 s[36:51], s[30:31], 0x0", "s_load_dwordx16 s[52:67], s[30:31], 0x40"]
     if streamed:
         # prefetch chain start: the first observation's code is byte 0 of chunk 0, its values
-        pro += ["s_getpc_b64 s[24:25]", ".Lpcref_%=:", "s_add_u32 s26, s24, .Lh0_%=-.Lpcref_%=", "s_addc_u32 s25, s25, 0",
-                ] + ([] if held else ["s_waitcnt vmcnt(2)"]) + [
+        pro += ([] if held else ["s_waitcnt vmcnt(2)"]) + [
                 "v_bfe_u32 v72, v74, 0, 8", "v_bfe_u32 v73, v75, 0, 8",
-                "v_add_lshl_u32 v72, v72, %[y0], 5", "v_add_lshl_u32 v73, v73, %[y0], 5",
+                "v_add_lshl_u32 v72, v72, s22, 5", "v_add_lshl_u32 v73, v73, s22, 5",
                 "ds_read_b128 v[56:59], v72", "ds_read_b128 v[60:63], v72 offset:16",
                 "ds_read_b128 v[64:67], v73", "ds_read_b128 v[68:71], v73 offset:16",
                 # pair products: the second observation's values into buffer 1 (its byte and table are operands: a program
                 # with one observation names the first again)
-                ] + (lookup(BUF[1], "%[b1]", "%[y1]") if pairs else []) + [
+                ] + (lookup(BUF[1], "s28", "s23") if pairs else []) + [
                 "s_waitcnt lgkmcnt(0)"]
     else:
         pro += [
@@ -386,13 +403,21 @@ def emit(streamed=False, held=False, pairs=False):
         if idx:
             ins([".p2align 9"])
         ins(h.get(idx, ["s_branch .Ldone_%="]))
-    ins([".p2align 9", ".Ldone_%=:", "s_waitcnt vmcnt(0) lgkmcnt(0)"])
+    ins([".p2align 9", ".Ldone_%=:"])
+    W = ["%%[w%d]" % i for i in range(4)]
+    if streamed:
+        # the root weights: the second half of the record, into s[20:27].  The program pointer, the op, the jump target and
+        # the scale constant are dead here, and no load in flight names them (the last prefetches of the matrix and of the ring
+        # may still be travelling into theirs), so the one wait below serves the weights too.
+        ins(["s_load_dwordx8 s[20:27], s[32:33], 0x20"])
+        W = ["s[%d:%d]" % (20 + 2 * i, 21 + 2 * i) for i in range(4)]
+    ins(["s_waitcnt vmcnt(0) lgkmcnt(0)"])
     # root dot product lh = w . x as one fma chain (weights 1 for no prior, 1/4 for the uniform prior: the same bits as the
     # plain sum and the scaled sum), so that only lh and the exponent leave the statement
     for (x, t) in ((XA, TA), (XB, TB)):
-        ins(["v_mul_f64 %s, %%[w0], %s" % (pair(t), pair(x))])
+        ins(["v_mul_f64 %s, %s, %s" % (pair(t), W[0], pair(x))])
         for i in range(1, 4):
-            ins(["v_fma_f64 %s, %%[w%d], %s, %s" % (pair(t), i, pair(x + 2 * i), pair(t))])
+            ins(["v_fma_f64 %s, %s, %s, %s" % (pair(t), W[i], pair(x + 2 * i), pair(t))])
     ins(["v_mov_b32 %%[al], v%d" % TA, "v_mov_b32 %%[ah], v%d" % (TA + 1), "v_mov_b32 %%[bl], v%d" % TB, "v_mov_b32 %%[bh], v%d" % (TB + 1)])
     ins(["v_mov_b32 %[ea], v78", "v_mov_b32 %[eb], v79", "s_nop 1"])
     return L[:npro], L[npro:]
