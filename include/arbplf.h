@@ -95,12 +95,26 @@ char *arbplf_nni_string(void *userdata, const char *s_in, int *retcode);
  * query, then edge as listed.  Sites are compressed to patterns on the columns of the tree and of the queries together.  A
  * value that is not finite (likelihood 0 under the placement) is refused as arbplf-ll refuses it. */
 char *arbplf_place_string(void *userdata, const char *s_in, int *retcode);
+/* Log likelihood of subtree prune-and-regraft moves of the tree (the reference has no such command): a whole subtree is
+ * cut and attached to another edge, from one pass over the current tree and one pass per pruned edge (plk_spr_ll in plk.h)
+ * in place of one arbplf-ll per candidate.
+ * Input: model_and_data, an optional site_reduction exactly as for arbplf-ll, and an optional
+ *   "spr": {"moves": [[prune, target], ...], "split": 0.5}
+ * in the edge indices of the document's `edges`.  A move prunes the edge prune = (w -> x) with the subtree below x and
+ * attaches it to the edge target = (u -> b), which is neither prune nor an edge below x: target becomes (u -> m) with rate
+ * split r and (m -> b) with rate (1 - split) r, prune becomes (m -> x) with its own rate; w stays with one child fewer and
+ * keeps its data.  Without "moves": every move of the tree, ordered by (prune, target); repeats are allowed.  "split" in
+ * [0, 1] (default 0.5) is the share of the target edge's rate coefficient above the new node.
+ * Columns ["site", "prune", "target", "value"], without the site column under site aggregation; rows in the order of the
+ * request, site outermost.  A pair that is no move, a non-integer or an index out of range is an error; a value that is
+ * not finite (likelihood 0 under the moved tree) is refused as arbplf-ll refuses it. */
+char *arbplf_spr_string(void *userdata, const char *s_in, int *retcode);
 
 /* Host-only validation of an input document (JSON grammar, model_and_data,
  * reductions) exactly as the corresponding query would perform it, without
  * touching the GPU.  what = "ll" | "deriv" | "marginal" | "dwell" | "trans" | "em_update" | "hess" |
  * "inv_hess" | "newton_delta" | "newton_update" | "cat_posterior" | "site_rate" | "rate_matrix_deriv" |
- * "mixture_deriv" | "nni" (the swap list is checked by the query itself) | "place" (with its "placement" object).  0 = accepted.  Where the document selects at least one site this includes the preparation of the
+ * "mixture_deriv" | "nni" (the swap list is checked by the query itself) | "place" (with its "placement" object) | "spr" (the "spr" object is checked by the query itself).  0 = accepted.  Where the document selects at least one site this includes the preparation of the
  * model on the host (normalised rate matrix, category rates and priors) and the check of its values that every query
  * makes before any device work (plk_check_model_values in plk.h: non-finite or negative values, rate x length x |Qn|
  * beyond 2^40); the diagnostic names the edge in the order of the document's `edges`.  A document that selects no site

@@ -360,6 +360,44 @@ int plk_nni_ll(plk_engine *h, int n_swaps, const int *swaps, double *site_out, d
 int plk_place_ll(plk_engine *h, int n_queries, const uint8_t *q_codes, const double *q_dense, int n_edges, const int *edges,
                  double split, double pendant_rate, double *site_out, double *sums_out);
 
+/*
+ * Subtree prune-and-regraft moves (the reference has no such query).  The tree is rooted and directed as everywhere here.
+ * A move is a pair of CSR edges (p, e), p = (w -> x) the pruned edge and e = (u -> b) the target, e neither p nor an edge
+ * of the subtree below x.  In the moved tree e is replaced by (u -> m) with rate fl(split r_e) and (m -> b) with rate
+ * fl(fl(1 - split) r_e), exactly as plk_place_ll rounds them; p becomes (m -> x) and keeps its index, its rate r_p and the
+ * whole subtree below x; m is a new node without data; w stays where it is with one child fewer (it may become unary, or a
+ * leaf whose vector is its own observation row, constant if it has no data) and keeps its data.  Every other node, datum
+ * and edge, the root and the root prior stay.  Multifurcations, unary nodes, data on internal nodes, a leaf as x, the root
+ * as w or u, a sibling edge of p (u = w) and the edge into w as the target are all allowed.  For a w with two children and
+ * no data the value equals, mathematically, the usual SPR in which the two edges at w merge.  A move with split = 0 onto
+ * a sibling edge of p gives the log likelihood of the current tree; a move whose x is a leaf equals the placement of that
+ * leaf's observations onto e in the tree without the leaf, with pendant_rate = r_p.
+ *
+ * plk_spr_moves: host only, no engine and no GPU involved.  Returns the number of moves of the tree (0 for arrays that are
+ * no tree) and, when pairs_out is not NULL, fills the canonical list [count][2], ordered by p, then by e: every (p, e) with
+ * e outside {p} and the edges below x.
+ *
+ * plk_spr_ll: the log likelihood ll'_s of every site under every listed moved tree, from the vectors of ONE down pass per
+ * site chunk over the current tree; per prune edge one pass recomputes the vectors of the tree without the pruned subtree
+ * (the down vectors on the path from w to the root and the forward vectors outside the subtree of x), and one pass per 256
+ * moves of that edge ends them as placements whose pendant vector is the message the pruned subtree sends today
+ * (plk_spr.h).  moves: [n_moves][2] CSR edge pairs (p, e); NULL = the canonical list, n_moves being its length.  Repeated
+ * moves are allowed, and a move has the same bits wherever it stands in whatever list, alone or with others, in one site
+ * chunk or several.  site_out: NULL or [n_moves][S] host; sums_out: NULL or [n_moves][2] double-double sums of w_s ll'_s,
+ * summed in a fixed order; with both NULL the arguments are checked and nothing runs.  Nothing is divided by the likelihood
+ * of the current tree.  A site of likelihood 0 under the moved tree has ll' = -inf; in the sums it behaves as in plk_ll
+ * (weight exactly 0: it adds nothing; otherwise the sum is not finite).
+ * PLK_E_ARG, the diagnostic naming the pair or the argument: tree, model or patterns not set; an index out of range;
+ * e == p; e below x; split outside [0, 1] or not finite; a rate the transition matrix kernel refuses
+ * (plk_check_model_values).  Nothing has run then and the engine stays usable.  Preconditions as for plk_deriv (nodes with
+ * more than 32 factors: the same range check and refusal).  The transition matrices of the split target edges live in
+ * buffers of the call's own: the engine's tree, matrices, tables, rates and dirty flags do not change, and the call is
+ * invisible to every later query.  PLK_INFO_SPR_KERNEL, PLK_INFO_DOWN4_KERNEL and PLK_INFO_LAST_QUERY_NS report on the call.
+ */
+int plk_spr_moves(int N, const int *indptr, const int *indices, int *pairs_out /* NULL or [count][2] */);
+int plk_spr_ll(plk_engine *h, int n_moves, const int *moves /* [n_moves][2] (p, e), NULL = canonical list */,
+               double split, double *site_out /* NULL or [n_moves][S] host */, double *sums_out /* NULL or [n_moves][2] */);
+
 /* the scaled Frechet matrices coef_{c,e} * F_{c,e} themselves, [C][E][k][k] host (tests) */
 int plk_get_frechet_matrices(plk_engine *h, const double *L_hi, const double *L_lo, int coef_mode,
                              double *F_out);
@@ -454,7 +492,7 @@ enum {
     PLK_INFO_PAIR_SUMS_KERNEL = 14, /* up pass of the last plk_edge_pair_sums / plk_rate_matrix_sens: 0 = none yet, 1 = the k = 4
                                        kernel (compact codes, at most 4 categories), 2 = generic */
     PLK_INFO_LAST_QUERY_NS = 15,    /* HIP-event time from the first to the last device operation of the last plk_deriv,
-                                       plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens, plk_mixture_sens, plk_nni_ll or plk_place_ll
+                                       plk_edge_expect(_multi), plk_edge_pair_sums, plk_rate_matrix_sens, plk_mixture_sens, plk_nni_ll, plk_place_ll or plk_spr_ll
                                        (0 when it could not be taken); for tools/time_rate_matrix_deriv.py and
                                        tools/time_mixture_deriv.py */
     PLK_INFO_MIXTURE_SENS_KERNEL = 16, /* up pass of the last plk_mixture_sens: 0 = none yet, 1 = the k = 4 kernel (compact
@@ -465,7 +503,7 @@ enum {
                                        product of two table rows), 8 = two-leaf nodes finished inside their parent's visit
                                        (one rate category); 0 when another kernel family ran */
     PLK_INFO_DOWN4_KERNEL = 18,     /* k = 4 down pass of the last query that ran on the k = 4 up/down kernels (deriv, marginal,
-                                       expectations, and the pair-sum, mixture-gradient, swap and placement passes): 4, 8 or 16 = k_down_fused4<D>
+                                       expectations, and the pair-sum, mixture-gradient, swap, placement and prune-and-regraft passes): 4, 8 or 16 = k_down_fused4<D>
                                        with a register stack of that depth, 0 = k_down_store4 (the staged code rows do not fit
                                        the LDS, or the tree needs more than 16 slots) or no such query yet */
     PLK_INFO_LL_FORM = 19,          /* form of the last ll evaluation's k = 4 pair-table kernel: 1 = streamed codes with the tables
@@ -497,6 +535,8 @@ enum {
                                        PLK_INFO_PAIR_TABLES then counts the cherries that still have a table of their own, and
                                        PLK_INFO_LL_EXEC_FLOPS the stream that ran */
     PLK_INFO_PLACE_KERNEL = 25,     /* up pass of the last plk_place_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
+                                       4 categories), 2 = generic */
+    PLK_INFO_SPR_KERNEL = 27,       /* up pass of the last plk_spr_ll: 0 = none yet, 1 = the k = 4 kernel (compact codes, at most
                                        4 categories), 2 = generic */
     PLK_INFO_LL_BARRIER = 26        /* workgroup barrier of the last ll evaluation's streamed kernel as it was launched: 0 = another
                                        kernel ran, else bits 0-1 = 1 the waves never met, 2 they met before every unit, 3 before
@@ -622,6 +662,9 @@ int plk_group_nni_ll(plk_group *g, int n_swaps, const int *swaps, double *site_o
  * sums_out: partial sums of the engines added in engine order (long double) */
 int plk_group_place_ll(plk_group *g, int n_queries, const uint8_t *q_codes, const double *q_dense, int n_edges, const int *edges,
                        double split, double pendant_rate, double *site_out, double *sums_out);
+/* arguments and outputs as plk_spr_ll with S the sites of the group: site_out [n_moves][S] at the global site positions;
+ * sums_out [n_moves][2]: partial sums of the engines added in engine order (long double) */
+int plk_group_spr_ll(plk_group *g, int n_moves, const int *moves, double split, double *site_out, double *sums_out);
 int plk_group_hess(plk_group *g, double *hess_sums_out);
 int plk_group_second_order(plk_group *g, double *grad_sums_out, double *hess_sums_out);   /* either may be NULL */
 

@@ -130,6 +130,12 @@ def arbplf_place(s):
     return _call("arbplf_place", s)
 
 
+def arbplf_spr(s):
+    """log likelihood of every subtree prune-and-regraft move of the tree, or of the listed "moves" of "spr" (no
+    counterpart in the reference): columns site, prune, target, value; site_reduction as for arbplf_ll"""
+    return _call("arbplf_spr", s)
+
+
 def _out_of_scope(name):
     def f(s):
         raise RuntimeError("arbplf likelihood error: %s is outside the MI355X hot path of this build" % name)

@@ -263,7 +263,7 @@ static int check_finite(double v, const char *what)
 }
 
 /* _parse of the drivers: kind 0 ll, 1 deriv, 2 marginal, 3 dwell, 4 trans, 5 em-update, 6 the second-order family,
- * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv, 10 mixture-deriv, 11 nni, 12 place (no counterpart in the reference: its reduction grammar, its table layout)
+ * 7 cat-posterior, 8 site-rate, 9 rate-matrix-deriv, 10 mixture-deriv, 11 nni, 12 place, 13 spr (no counterpart in the reference: its reduction grammar, its table layout)
  * (src/arbplfll.c:250-288, src/arbplfderiv.c:445-493, src/arbplfmarginal.c:348-405,
  *  src/arbplfdwell.c:507-566, src/arbplftrans.c:553-614, src/arbplfem.c:505-545) */
 static int query_parse(query *q, int kind, const jval *root)
@@ -277,8 +277,9 @@ static int query_parse(query *q, int kind, const jval *root)
     static const char *const all_catpost[] = {"model_and_data", "site_reduction", "category_reduction", NULL};
     static const char *const all_nni[] = {"model_and_data", "site_reduction", "swaps", NULL};
     static const char *const all_place[] = {"model_and_data", "site_reduction", "placement", NULL};
+    static const char *const all_spr[] = {"model_and_data", "site_reduction", "spr", NULL};
     const char *const *allowed = kind == 0 ? all_ll : kind == 1 ? all_deriv : kind == 2 ? all_marg :
-                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : kind == 7 ? all_catpost : kind == 11 ? all_nni : kind == 12 ? all_place : all_ll;
+                                 kind == 3 ? all_dwell : kind == 4 ? all_trans : kind == 7 ? all_catpost : kind == 11 ? all_nni : kind == 12 ? all_place : kind == 13 ? all_spr : all_ll;
     if (host_check_keys(root, req, allowed, "input")) return -1;
     if (host_model_parse(&q->m, j_get(root, "model_and_data"))) return -1;
     if (host_reduction_parse(&q->r_site, (int)q->m.S, "site", j_get(root, "site_reduction"))) return -1;
@@ -1129,6 +1130,118 @@ done:
     return rc;
 }
 
+/* ------------------------------------------------------------------ spr (kind 13)
+ * The log likelihood of subtree prune-and-regraft moves of the tree (no counterpart in the reference; include/plk.h:
+ * plk_spr_ll).  "spr" (optional): {"moves": [[prune, target], ...] in the user's edge indices, prune = (w -> x) and target
+ * neither prune nor an edge below x (optional: every move of the tree, ordered by (prune, target) in the user's indices;
+ * repeats allowed), "split" (optional, 0.5)}.  Columns site, prune, target, value; rows in the order of the request, site
+ * outermost; the site column goes under site aggregation. */
+static int run_spr(const jval *root, jbuf *out)
+{
+    static const char *const none[] = {NULL};
+    static const char *const all[] = {"moves", "split", NULL};
+    query q;
+    int rc = -1;
+    int *user = NULL, *csr = NULL, *user_to_csr = NULL, *canon = NULL;
+    double *vals = NULL;
+    double split = 0.5;
+    query_init(&q);
+    if (query_parse(&q, 13, root)) goto done;
+    const host_model *m = &q.m;
+    const int E = m->E;
+    const jval *sp = j_get(root, "spr"), *mv = NULL;
+    if (sp) {
+        if (!j_is_object(sp)) { fprintf(stderr, "error: spr must be an object\n"); goto done; }
+        if (host_check_keys(sp, none, all, "spr")) goto done;
+        const jval *x = j_get(sp, "split");
+        if (x) {
+            if (!j_is_number(x) || !(j_number(x) >= 0 && j_number(x) <= 1)) { fprintf(stderr, "error: spr.split must be a number in [0, 1]\n"); goto done; }
+            split = j_number(x);
+        }
+        mv = j_get(sp, "moves");
+    }
+    user_to_csr = malloc((size_t)(E + 1) * sizeof(int));
+    if (!user_to_csr) goto done;
+    for (int e = 0; e < E; e++) user_to_csr[m->csr_to_user[e]] = e;
+    const int count = plk_spr_moves(m->N, m->indptr, m->indices, NULL);
+    canon = malloc((size_t)(2 * (size_t)count + 2) * sizeof(int));
+    if (!canon) goto done;
+    plk_spr_moves(m->N, m->indptr, m->indices, canon);           /* sorted by (prune, target) in CSR indices */
+    int n = 0;
+    if (mv) {
+        if (!j_is_array(mv)) { fprintf(stderr, "error: spr.moves must be an array of pairs of edge indices\n"); goto done; }
+        n = (int)j_len(mv);
+        user = malloc((size_t)(2 * (size_t)n + 2) * sizeof(int));
+        if (!user) goto done;
+        for (int i = 0; i < n; i++) {
+            const jval *p = j_at(mv, i);
+            if (!j_is_array(p) || j_len(p) != 2) { fprintf(stderr, "error: spr.moves: entry %d is not a pair of edge indices\n", i); goto done; }
+            for (int j = 0; j < 2; j++) {
+                const jval *x = j_at(p, j);
+                if (!j_is_int(x)) { fprintf(stderr, "error: spr.moves: entry %d: edge indices must be integers\n", i); goto done; }
+                if (x->u.i < 0 || x->u.i >= E) { fprintf(stderr, "error: spr.moves: entry %d: edge index %lld is out of range\n", i, x->u.i); goto done; }
+                user[2 * i + j] = (int)x->u.i;
+            }
+        }
+    } else {
+        n = count;
+        user = malloc((size_t)(2 * (size_t)n + 2) * sizeof(int));
+        if (!user) goto done;
+        for (int i = 0; i < 2 * n; i++) user[i] = m->csr_to_user[canon[i]];
+        qsort(user, (size_t)n, 2 * sizeof(int), nni_pair_cmp);
+    }
+    csr = malloc((size_t)(2 * (size_t)n + 2) * sizeof(int));
+    if (!csr) goto done;
+    for (int i = 0; i < 2 * n; i++) csr[i] = user_to_csr[user[i]];
+    /* a pair that is no move is refused here, in the user's indices, whether or not a site is selected */
+    for (int i = 0; i < n; i++)
+        if (!bsearch(csr + 2 * i, canon, (size_t)count, 2 * sizeof(int), nni_pair_cmp)) {
+            fprintf(stderr, "error: spr.moves: entry %d: edges (%d, %d) are no move: the target must be neither the pruned edge nor "
+                            "an edge of the subtree below it\n", i, user[2 * i], user[2 * i + 1]);
+            goto done;
+        }
+    if (query_prepare(&q)) goto done;
+    const int agg = q.r_site.agg_mode != AGG_NONE;
+    const long U = q.U;
+    vals = malloc(((size_t)n * (agg ? 2 : (size_t)U) + 2) * sizeof(double));
+    if (!vals) goto done;
+    if (U > 0 && n > 0 && plk_group_spr_ll(q.eng, n, csr, split, agg ? NULL : vals, agg ? vals : NULL)) {
+        fprintf(stderr, "error: %s\n", plk_group_last_error(q.eng));
+        goto done;
+    }
+    jbuf_puts(out, agg ? "{\"columns\": [\"prune\", \"target\", \"value\"], \"data\": ["
+                       : "{\"columns\": [\"site\", \"prune\", \"target\", \"value\"], \"data\": [");
+    int first = 1;
+    if (agg) {
+        for (int i = 0; i < n; i++) {
+            const double v = U > 0 ? clean(((long double)vals[2 * i] + (long double)vals[2 * i + 1]) / q.div_site) : 0.0;
+            if (check_finite(v, "the aggregated log likelihood of a moved tree")) goto done;
+            if (!first) jbuf_puts(out, ", ");
+            first = 0;
+            jbuf_puts(out, "["); jbuf_int(out, user[2 * i]); jbuf_puts(out, ", "); jbuf_int(out, user[2 * i + 1]); jbuf_puts(out, ", ");
+            jbuf_real(out, v); jbuf_puts(out, "]");
+        }
+    } else {
+        for (int si = 0; si < q.r_site.selection_len; si++) {
+            const int s = q.r_site.selection[si];
+            for (int i = 0; i < n; i++) {
+                const double v = clean(vals[(size_t)i * U + q.site_to_u[s]]);
+                if (check_finite(v, "a site log likelihood of a moved tree")) goto done;
+                if (!first) jbuf_puts(out, ", ");
+                first = 0;
+                jbuf_puts(out, "["); jbuf_int(out, s); jbuf_puts(out, ", "); jbuf_int(out, user[2 * i]); jbuf_puts(out, ", ");
+                jbuf_int(out, user[2 * i + 1]); jbuf_puts(out, ", "); jbuf_real(out, v); jbuf_puts(out, "]");
+            }
+        }
+    }
+    jbuf_puts(out, "]}");
+    rc = 0;
+done:
+    free(user); free(csr); free(user_to_csr); free(canon); free(vals);
+    query_clear(&q);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ place (kind 12)
  * The log likelihood of the tree with a new taxon attached to an edge (no counterpart in the reference; include/plk.h:
  * plk_place_ll).  "placement": {"character_data": [site][query] character indices into the model's
@@ -1406,12 +1519,14 @@ char *arbplf_rate_matrix_deriv_string(void *userdata, const char *s_in, int *ret
 char *arbplf_mixture_deriv_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_mixture_deriv, userdata, s_in, retcode); }
 char *arbplf_nni_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_nni, userdata, s_in, retcode); }
 char *arbplf_place_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_place, userdata, s_in, retcode); }
+char *arbplf_spr_string(void *userdata, const char *s_in, int *retcode) { return string_hom(run_spr, userdata, s_in, retcode); }
 
 /* Host-only validation (JSON grammar, model, reductions and, where a site is selected, the prepared model's values
  * against what the transition matrix kernel accepts); no GPU is touched.
  * what: "ll", "deriv", "marginal", "dwell", "trans", "em_update", "hess", "inv_hess", "newton_delta", "newton_update",
  * "cat_posterior", "site_rate", "rate_matrix_deriv", "mixture_deriv", "nni" (the model and the reductions; the swap
- * list is checked by the query itself) or "place" (with the whole "placement" object and the rates of its new edges).
+ * list is checked by the query itself), "place" (with the whole "placement" object and the rates of its new edges) or
+ * "spr" (the model and the reductions; the "spr" object is checked by the query itself).
  * Returns 0 when the input would be accepted. */
 int arbplf_validate_string(const char *what, const char *s_in)
 {
@@ -1420,7 +1535,7 @@ int arbplf_validate_string(const char *what, const char *s_in)
                !strcmp(what, "dwell") ? 3 : !strcmp(what, "trans") ? 4 : !strcmp(what, "em_update") ? 5 : !strcmp(what, "hess") ? 6 :
                (!strcmp(what, "inv_hess") || !strcmp(what, "newton_delta") || !strcmp(what, "newton_update")) ? 6 :
                !strcmp(what, "cat_posterior") ? 7 : !strcmp(what, "site_rate") ? 8 : !strcmp(what, "rate_matrix_deriv") ? 9 :
-               !strcmp(what, "mixture_deriv") ? 10 : !strcmp(what, "nni") ? 11 : !strcmp(what, "place") ? 12 : -1;
+               !strcmp(what, "mixture_deriv") ? 10 : !strcmp(what, "nni") ? 11 : !strcmp(what, "place") ? 12 : !strcmp(what, "spr") ? 13 : -1;
     if (kind < 0 || !s_in) return -1;
     json_doc *doc = json_doc_parse(s_in, err, sizeof err);
     if (!doc) { fprintf(stderr, "%s\n", err); return -1; }

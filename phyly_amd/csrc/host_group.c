@@ -597,6 +597,55 @@ int plk_group_place_ll(plk_group *g, int n_queries, const uint8_t *q_codes, cons
     return rc;
 }
 
+/* log likelihood of prune-and-regraft moves: per-site rows [move][site] of the engines' blocks put side by side, sums added
+ * in engine order as for the swaps.  Weak for the same reason. */
+extern int plk_spr_ll(plk_engine *h, int n_moves, const int *moves, double split, double *site_out, double *sums_out) __attribute__((weak));
+
+typedef struct { int n; const int *moves; double split; double *site, *part; int want_sums; } spr_ctx;
+
+static int job_spr_ll(plk_group *g, int i, void *p)
+{
+    spr_ctx *c = p;
+    const long s0 = g->s0[i], ni = g->s0[i + 1] - s0, S = g->S;
+    if (ni == 0) return PLK_OK;                            /* an engine without sites adds nothing */
+    double *mine = NULL;
+    if (c->site && c->n > 0 && !(mine = malloc((size_t)c->n * ni * sizeof(double)))) return PLK_E_NOMEM;
+    const int rc = plk_spr_ll(g->eng[i], c->n, c->moves, c->split, mine, c->want_sums ? c->part + (size_t)i * c->n * 2 : NULL);
+    if (!rc && mine)
+        for (int r = 0; r < c->n; r++) memcpy(c->site + (size_t)r * S + s0, mine + (size_t)r * ni, (size_t)ni * sizeof(double));
+    free(mine);
+    return rc;
+}
+
+int plk_group_spr_ll(plk_group *g, int n_moves, const int *moves, double split, double *site_out, double *sums_out)
+{
+    if (!g) return PLK_E_ARG;
+    if (!plk_spr_ll) return fail(g, PLK_E_UNSUPPORTED, "plk_group: the engine has no plk_spr_ll");
+    if (!g->have_patterns) return fail(g, PLK_E_ARG, "plk_group: tree, model and patterns must be set");
+    if (n_moves < 0) return fail(g, PLK_E_ARG, "plk_group_spr_ll: negative number of moves");
+    spr_ctx c = {n_moves, moves, split, site_out, NULL, sums_out != NULL};
+    c.part = calloc((size_t)g->G * n_moves * 2 + 2, sizeof(double));
+    if (!c.part) return fail(g, PLK_E_NOMEM, "plk_group: out of host memory");
+    int rc = for_each(g, job_spr_ll, &c, 1);
+    if (!rc && sums_out) {
+        for (int r = 0; r < n_moves; r++) {
+            double *dst = sums_out + 2 * (size_t)r;
+            if (g->G == 1) { dst[0] = c.part[2 * r]; dst[1] = c.part[2 * r + 1]; continue; }   /* one engine: its sums, bit for bit */
+            long double acc = 0;
+            for (int i = 0; i < g->G; i++) {
+                if (g->s0[i + 1] == g->s0[i]) continue;
+                acc += (long double)c.part[((size_t)i * n_moves + r) * 2];
+                acc += (long double)c.part[((size_t)i * n_moves + r) * 2 + 1];
+            }
+            const double hi = (double)acc;
+            dst[0] = hi;
+            dst[1] = (double)(acc - (long double)hi);
+        }
+    }
+    free(c.part);
+    return rc;
+}
+
 int plk_group_hess(plk_group *g, double *hess_sums_out)
 {
     if (!g || !hess_sums_out) return PLK_E_ARG;

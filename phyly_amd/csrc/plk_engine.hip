@@ -204,6 +204,7 @@ struct plk_engine {
     uint8_t *d_plcodes = nullptr;
     size_t plpdd_cap = 0, plp_cap = 0, plrates_cap = 0, plstream_cap = 0, plt_cap = 0, pldense_cap = 0, plcodes_cap = 0;
     long info_place_kernel = 0;                      /* PLK_INFO_PLACE_KERNEL: up pass of the last plk_place_ll */
+    long info_spr_kernel = 0;                        /* PLK_INFO_SPR_KERNEL: up pass of the last plk_spr_ll */
     long info_up4_path = 0;                          /* PLK_INFO_UP4_PATH: which k = 4 up pass the last up/down query took */
     long info_down4_kernel = 0;                      /* PLK_INFO_DOWN4_KERNEL: the k = 4 down pass run_updown4 launched last */
     hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;     /* around the device work of the last timed query (PLK_INFO_LAST_QUERY_NS) */
@@ -1544,6 +1545,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_up(UpArgs a)
 #include "plk_mixsens.h"
 #include "plk_nni.h"
 #include "plk_place.h"
+#include "plk_spr.h"
 
 /* padded edge-indexed matrix streams for the up/down kernels:
  * mode 0: out[j*K+i] = M[i][j] (transposed), mode 1: out[i*K+j] = M[i][j] */
@@ -1720,6 +1722,7 @@ extern "C" int plk_get_info(plk_engine *h, int what, long *out)
     case PLK_INFO_MIXTURE_SENS_KERNEL: *out = h->info_mixture_sens_kernel; return PLK_OK;
     case PLK_INFO_NNI_KERNEL: *out = h->info_nni_kernel; return PLK_OK;
     case PLK_INFO_PLACE_KERNEL: *out = h->info_place_kernel; return PLK_OK;
+    case PLK_INFO_SPR_KERNEL: *out = h->info_spr_kernel; return PLK_OK;
     case PLK_INFO_UP4_PATH: *out = h->info_up4_path; return PLK_OK;
     case PLK_INFO_DOWN4_KERNEL: *out = h->info_down4_kernel; return PLK_OK;
     case PLK_INFO_LL_VARIANT: *out = h->info_ll_variant; return PLK_OK;
@@ -2793,6 +2796,15 @@ static void launch_place(plk_engine *h, const UpArgs &a, const PlaceOut &o, unsi
     hipLaunchKernelGGL(k_up_place<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, o);
 }
 
+/* the prune-and-regraft pass (plk_spr.h): the down pass once per chunk, the path plane and F' once per prune edge */
+template <int K>
+static void launch_spr(plk_engine *h, const UpArgs &a, const SprOut &o, unsigned grid, bool down)
+{
+    if (down) hipLaunchKernelGGL(k_down_store<K>, dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a);
+    if (o.store_fn) hipLaunchKernelGGL((k_up_spr<K, true>), dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, o);
+    hipLaunchKernelGGL((k_up_spr<K, false>), dim3(grid), dim3(GEN_BLOCK), 0, h->stream, a, o);
+}
+
 /* ... and the mixture-gradient up pass on the same grid (plk_mixsens.h) */
 template <int K>
 static void launch_mixsens(plk_engine *h, const UpArgs &a, const MixSensOut &o, unsigned grid, unsigned pgrid)
@@ -3299,14 +3311,14 @@ struct PlaceReq {
 };
 
 /* the call's transition matrices: one more launch of K1 over the call's rates into the call's buffers (no dP) */
-static int place_matrices(plk_engine *h, const PlaceReq &q)
+static int call_matrices(plk_engine *h, const std::vector<double> &rates)
 {
-    const int k = h->k, C = h->C, EQ = (int)q.rates.size();
+    const int k = h->k, C = h->C, EQ = (int)rates.size();
     const size_t kk = (size_t)k * k, nmat = (size_t)C * EQ * kk;
     int rc;
     if ((rc = dev_reserve(h, &h->d_plPdd, &h->plpdd_cap, nmat)) || (rc = dev_reserve(h, &h->d_plP, &h->plp_cap, nmat)) ||
         (rc = dev_reserve(h, &h->d_plrates, &h->plrates_cap, (size_t)EQ))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_plrates, q.rates.data(), (size_t)EQ * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_plrates, rates.data(), (size_t)EQ * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const int threads = kk >= 1024 ? 1024 : (kk >= 256 ? 256 : 64);
     int use_lds;
     const size_t lds_bytes = expm_lds_bytes((size_t)k, threads, &use_lds);
@@ -3319,6 +3331,8 @@ static int place_matrices(plk_engine *h, const PlaceReq &q)
     HIPCHK(h, hipGetLastError());
     return PLK_OK;
 }
+
+static int place_matrices(plk_engine *h, const PlaceReq &q) { return call_matrices(h, q.rates); }
 
 /* records of plk_place.h for every pass of the call; they go to the device with the call's other integer tables */
 struct PlaceGroups {
@@ -3366,6 +3380,81 @@ static int place_group_out(plk_engine *h, PlaceReq *q, long g0, int ng, long n, 
     return PLK_OK;
 }
 
+/* plk_spr_ll asks the same drivers for the prune-and-regraft pass (plk_spr.h).  The moves are grouped by their prune edge
+ * (order: by p, ties in the caller's order); rows and sums are kept in that order and leave in the caller's */
+struct SprReq {
+    int n = 0;
+    const int *moves = nullptr;        /* [n][2] validated (p, e) */
+    std::vector<int> order;            /* [n] positions in the caller's list, grouped by p */
+    std::vector<int> slot;             /* [n] (caller's order) index of e among the distinct target edges of the call */
+    std::vector<double> rates;         /* [2 distinct]: upper part, lower part of every distinct target edge */
+    double *site_out = nullptr;        /* null or [n][S] host */
+    std::vector<long double> acc;      /* [n] weighted site sums in grouped order (filled when want_sums) */
+    bool want_sums = false;
+    std::vector<int> epar;             /* upper node of every CSR edge */
+    std::vector<int> pos;              /* position of every node in the engine's order (what the records are sorted by) */
+    std::vector<int> dpos, size, depth, par, in;   /* the node tables of SprOut (dpos: depth-first preorder position) */
+    int max_depth = 0;
+    std::vector<double> stage;         /* per-site rows of one pass on their way to site_out */
+};
+
+/* the passes of the call and their records; they go to the device with the call's other integer tables */
+struct SprGroups {
+    struct Pass { int p; int first; size_t off; int nrec; int g0; };
+    std::vector<Pass> pass;
+    size_t o_pos = 0, o_size = 0, o_depth = 0, o_par = 0, o_in = 0;
+    int rows = 0;
+    void put(const SprReq &q, IntPack &pack)
+    {
+        struct Rec { int w[SPR_REC]; };
+        const int N = (int)q.pos.size();
+        o_pos = pack.put(q.dpos.data(), (size_t)N); o_size = pack.put(q.size.data(), (size_t)N); o_depth = pack.put(q.depth.data(), (size_t)N);
+        o_par = pack.put(q.par.data(), (size_t)N); o_in = pack.put(q.in.data(), (size_t)N);
+        for (int g0 = 0; g0 < q.n;) {
+            const int p = q.moves[2 * q.order[g0]];
+            int gend = g0;
+            while (gend < q.n && q.moves[2 * q.order[gend]] == p) gend++;
+            for (int t0 = g0; t0 < gend; t0 += PLACE_MAX_ROWS) {
+                const int t1 = std::min(t0 + PLACE_MAX_ROWS, gend);
+                std::vector<Rec> recs;
+                for (int t = t0; t < t1; t++) {
+                    const int i = q.order[t], e = q.moves[2 * i + 1];
+                    recs.push_back(Rec{{q.pos[q.epar[e]], e, q.slot[i], t - t0}});
+                }
+                std::stable_sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) { return x.w[0] < y.w[0]; });
+                std::vector<int> out;
+                for (const Rec &r : recs) out.insert(out.end(), r.w, r.w + SPR_REC);
+                pass.push_back(Pass{p, t0 == g0 ? 1 : 0, pack.put(out.data(), out.size()), (int)recs.size(), t0});
+                rows = std::max(rows, t1 - t0);
+            }
+            g0 = gend;
+        }
+    }
+    SprOut out(const SprReq &q, const int *b, size_t i) const
+    {
+        SprOut o = {};
+        o.rec = b + pass[i].off; o.nrec = pass[i].nrec; o.store_fn = pass[i].first; o.p = pass[i].p;
+        o.pos = b + o_pos; o.size = b + o_size; o.depth = b + o_depth; o.par = b + o_par; o.in = b + o_in;
+        o.EQ = (int)q.rates.size();
+        return o;
+    }
+};
+
+/* one chunk's outputs of one pass: weighted row sums into acc (grouped order), rows of the plane to their places in site_out */
+static int spr_group_out(plk_engine *h, SprReq *q, int g0, int ng, long n, long s0, const double *plane)
+{
+    int rc;
+    if (q->want_sums && (rc = wsum_rows(h, ng, n, plane, h->d_w ? h->d_w + s0 : nullptr, q->acc.data() + g0))) return rc;
+    if (q->site_out) {
+        q->stage.resize((size_t)ng * n);
+        HIPCHK(h, hipMemcpyAsync(q->stage.data(), plane, (size_t)ng * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < ng; i++)
+            std::copy(q->stage.begin() + (size_t)i * n, q->stage.begin() + (size_t)(i + 1) * n, q->site_out + (size_t)q->order[g0 + i] * h->S + s0);
+    }
+    return PLK_OK;
+}
+
 /* workgroups of the pair-sum passes: fixed by the device, so the partial sums never grow with S */
 static unsigned pair_sums_grid(const plk_engine *h, long nbatch) { return (unsigned)std::min<long>(nbatch, 4L * h->num_cus); }
 
@@ -3385,7 +3474,7 @@ static int pair_sums_finish(plk_engine *h, PairSumReq *ps, size_t rows, unsigned
 
 static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
                        double *site_out, double *sums_out, const double *d_M, int dzero, int nM, PairSumReq *ps = nullptr, NniReq *nni = nullptr,
-                       PlaceReq *pl = nullptr)
+                       PlaceReq *pl = nullptr, SprReq *sp = nullptr)
 {
     int rc;
     const int N = h->N, E = h->E, C = h->C;
@@ -3471,7 +3560,7 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
                                                    any_rebuild ? rebuild_tab.data() : nullptr, pair_of.data());
         if (!bad.empty()) { h->err = "internal: " + bad; return PLK_E_ARG; }
     }
-    if (!ps && !nni && !pl) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
+    if (!ps && !nni && !pl && !sp) h->info_up4_path = nodes4 ? 1 | (npairs4 > 0 ? 2 : 0) | (any_rebuild ? 4 : 0) | (inline4 ? 8 : 0) : 0;
     const size_t ntab = (size_t)C * (ntips + 1) * h->nchar * 4;
     /* all small integer tables of this call in one host block, one upload */
     IntPack pack;
@@ -3490,6 +3579,8 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     const int pl_tip_edge = pl ? (int)pl->rates.size() - 1 : 0;      /* the pendant matrix, as the one "tip edge" of its table */
     const size_t o_pte = pl ? pack.put(&pl_tip_edge, 1) : 0;
     if (pl) pg4.put(*pl, pack);
+    SprGroups sg4;
+    if (sp) sg4.put(*sp, pack);
     const size_t nptab = (size_t)C * npairs4 * h->nchar * h->nchar * 4;
     if ((rc = dev_reserve(h, &h->d_u4tip, &h->u4tip_cap, ntab * (size_t)(1 + nM) + nptab)) || (rc = pack.upload(h))) return rc;
     int *const d_psflag = pack.flag(h);
@@ -3517,7 +3608,8 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
     if (hipGetLastError() != hipSuccess) { h->err = "plk_deriv/plk_marginal: table build failed"; return PLK_E_DEVICE; }
 
     const bool msum_only = marginal_sums_only(deriv, marg, site_out, sums_out);      /* per-wave sums instead of the N x 4 planes */
-    const size_t per_site = ((size_t)(2 * (size_t)nin) * C * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? ER : 0) + (marg && !msum_only ? (size_t)N * 4 : 0) + (size_t)ng4.rows + (size_t)pg4.rows) * sizeof(double);
+    const size_t per_site = ((size_t)(2 * (size_t)nin) * C * 4 + (size_t)(nsc + 2) * C + 1 + (deriv ? ER : 0) + (marg && !msum_only ? (size_t)N * 4 : 0) + (size_t)ng4.rows + (size_t)pg4.rows +
+                             (sp ? (size_t)sg4.rows + (size_t)(sp->max_depth + 1) * C * 4 + 1 : 0)) * sizeof(double);
     long chunk;
     if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site + (msum_only ? ((size_t)N * h->k / 64 + 1) * sizeof(double) : 0), UD4_BLOCK, false, &chunk))) return rc;
     const size_t mvs_doubles = msum_only ? (size_t)N * 4 * (size_t)((chunk + UD4_BLOCK - 1) / UD4_BLOCK) * (UD4_BLOCK / 64) : 0;   /* per-wave marginal sums */
@@ -3586,6 +3678,18 @@ static int run_updown4(plk_engine *h, bool deriv, bool marg, const int *edge_mas
                 if (hipGetLastError() != hipSuccess) { h->err = "plk_place_ll: kernel launch failed"; return PLK_E_DEVICE; }
                 const long g0 = (long)gi * PLACE_MAX_ROWS;
                 if ((rc = place_group_out(h, pl, g0, (int)std::min<long>(PLACE_MAX_ROWS, pl->total() - g0), n, s0, p))) return rc;
+            }
+            continue;
+        }
+        if (sp) {
+            /* per prune edge: the first pass stores the path plane (after the rows) and F', later passes of the edge read them */
+            for (size_t gi = 0; gi < sg4.pass.size(); gi++) {
+                SprOut so = sg4.out(*sp, b, gi);
+                so.QP = h->d_plP; so.plane = p; so.LP = p + (size_t)sg4.rows * n;
+                if ((uintptr_t)so.LP & 15) so.LP++;               /* the vectors are read as pairs of doubles: the spare double of per_site */
+                hipLaunchKernelGGL(k_up4_spr, dim3(grid), dim3(UD4_BLOCK), 0, h->stream, a, so);
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_spr_ll: kernel launch failed"; return PLK_E_DEVICE; }
+                if ((rc = spr_group_out(h, sp, sg4.pass[gi].g0, sg4.pass[gi].nrec, n, s0, p))) return rc;
             }
             continue;
         }
@@ -3755,17 +3859,23 @@ static bool use_updown4(const plk_engine *h)
  * (dzero = 1: rows sum to zero), scaled Frechet matrices for dwell / trans / em-update (dzero = 0) */
 static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask, const int *node_mask,
                       double *site_out, double *sums_out, const double *d_M_in = nullptr, int dzero = 1, int nM = 1, PairSumReq *ps = nullptr,
-                      NniReq *nni = nullptr, PlaceReq *pl = nullptr)
+                      NniReq *nni = nullptr, PlaceReq *pl = nullptr, SprReq *sp = nullptr)
 {
     if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_deriv/plk_marginal: tree, model and patterns must be set"; return PLK_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (h->model_dirty) { if ((rc = run_expm(h))) return rc; }
-    if ((rc = check_stored_range(h, pl ? "plk_place_ll" : nni ? "plk_nni_ll" : ps ? (ps->mix_D ? "plk_mixture_sens" : "plk_edge_pair_sums/plk_rate_matrix_sens")
+    if ((rc = check_stored_range(h, sp ? "plk_spr_ll" : pl ? "plk_place_ll" : nni ? "plk_nni_ll" : ps ? (ps->mix_D ? "plk_mixture_sens" : "plk_edge_pair_sums/plk_rate_matrix_sens")
                                        : marg ? (deriv ? "plk_deriv/plk_marginal" : "plk_marginal") : d_M_in ? "plk_edge_expect" : "plk_deriv"))) return rc;
-    if (!d_M_in && !ps && !nni && !pl && (rc = ensure_dP(h))) return rc;
+    if (!d_M_in && !ps && !nni && !pl && !sp && (rc = ensure_dP(h))) return rc;
     const double *d_M = d_M_in ? d_M_in : h->d_dP;
-    if (!ps && !nni && !pl) h->info_up4_path = 0;
+    if (!ps && !nni && !pl && !sp) h->info_up4_path = 0;
+    if (sp) {
+        /* the k = 4 kernel takes compact codes and at most four categories, as for the placements */
+        if ((rc = call_matrices(h, sp->rates))) return rc;
+        if (use_updown4(h) && h->C <= 4) { h->info_spr_kernel = 1; return run_updown4(h, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, sp); }
+        h->info_spr_kernel = 2;
+    } else
     if (pl) {
         /* the k = 4 kernel takes compact codes and at most four categories, as for the swaps */
         if ((rc = place_matrices(h, *pl))) return rc;
@@ -3787,7 +3897,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     else if (use_mfma(h)) { h->info_updown_kernel = 3; return run_updown_mfma(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero); }
     else if (use_updown4(h)) { h->info_updown_kernel = 1; return run_updown4(h, deriv, marg, edge_mask, node_mask, site_out, sums_out, d_M, dzero, nM); }
     if (nM != 1) { h->err = "internal: several edge forms per pass need the k = 4 kernels"; return PLK_E_ARG; }
-    if (!ps && !nni && !pl) h->info_updown_kernel = 2;
+    if (!ps && !nni && !pl && !sp) h->info_updown_kernel = 2;
     const int N = h->N, E = h->E, k = h->k, K = h->K, C = h->C;
     const long S = h->S;
     /* padded edge-indexed streams in the grow-only matrix buffer; each starts at a multiple of 32 doubles (256 bytes, what
@@ -3798,7 +3908,7 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     const int bt = K * K >= 256 ? 256 : 64;
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, h->d_P, d_PT);
     hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 1, h->d_P, d_PN);
-    if (!nni && !pl && (!ps || ps->mix_D)) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
+    if (!nni && !pl && !sp && (!ps || ps->mix_D)) hipLaunchKernelGGL(k_build_edge_stream, dim3(C * E), dim3(bt), 0, h->stream, k, K, 0, ps ? ps->mix_D : d_M, d_DT);
     /* the call's integer tables; of the storage maps the generic kernels take the rescaling slots only */
     if (h->prog_dirty) { if ((rc = build_program(h))) return rc; }
     const PlkStorageMaps sm = storage_maps(h);
@@ -3810,8 +3920,10 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
     if (nni) ngg.put(h, *nni, false, pack);
     PlaceGroups pgg;
     if (pl) pgg.put(*pl, pack);
+    SprGroups sgg;
+    if (sp) sgg.put(*sp, pack);
     if ((rc = pack.upload(h))) return rc;
-    const int EQ = pl ? (int)pl->rates.size() : 0;
+    const int EQ = pl ? (int)pl->rates.size() : sp ? (int)sp->rates.size() : 0;
     const size_t qstrm = ((size_t)C * EQ * K * K + 31) / 32 * 32;
     if (pl) {
         /* the call's matrices as padded streams (transposed, plain) and, for compact codes, the pendant tables [C][nchar][K] */
@@ -3822,13 +3934,20 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
         if (pl->compact) hipLaunchKernelGGL(k_place_table, dim3(C), dim3(256), 0, h->stream, k, K, EQ, h->nchar, h->d_plstream, h->d_defs, h->d_plT);
         if (hipGetLastError() != hipSuccess) { h->err = "plk_place_ll: table build failed"; return PLK_E_DEVICE; }
     }
+    if (sp) {
+        /* the call's matrices as padded streams (transposed, plain) */
+        if ((rc = dev_reserve(h, &h->d_plstream, &h->plstream_cap, 2 * qstrm))) return rc;
+        hipLaunchKernelGGL(k_build_edge_stream, dim3(C * EQ), dim3(bt), 0, h->stream, k, K, 0, h->d_plP, h->d_plstream);
+        hipLaunchKernelGGL(k_build_edge_stream, dim3(C * EQ), dim3(bt), 0, h->stream, k, K, 1, h->d_plP, h->d_plstream + qstrm);
+        if (hipGetLastError() != hipSuccess) { h->err = "plk_spr_ll: stream build failed"; return PLK_E_DEVICE; }
+    }
     const int *pk = h->d_u4pack;
     const int *d_emask = edge_mask ? pk + o_em : nullptr, *d_nmask = node_mask ? pk + o_nm : nullptr, *d_has = pk + o_has, *d_ns = pk + o_ns;
     int *const d_psflag = pack.flag(h);
 
     /* chunk the site axis so that the stored vectors fit */
     const size_t per_site = ((size_t)(E + 2 * (size_t)N) * C * k + (size_t)(nsc + 2) * C + 1 + (deriv ? E : 0) + (marg ? (size_t)N * k : 0) + (size_t)ngg.rows +
-                             (pl ? (size_t)pgg.rows + (size_t)C * k + C : 0)) * sizeof(double);
+                             (pl ? (size_t)pgg.rows + (size_t)C * k + C : 0) + (sp ? (size_t)sgg.rows + (size_t)(sp->max_depth + 1) * C * k : 0)) * sizeof(double);
     long chunk;
     if ((rc = plan_site_chunk(h, "plk_deriv/plk_marginal", per_site, GEN_BLOCK, false, &chunk))) return rc;
     const size_t ps_rows = ps ? (ps->mix_D ? (size_t)2 * C : (size_t)C * E * k * k + (size_t)C * k) : 0;
@@ -3887,6 +4006,17 @@ static int run_updown(plk_engine *h, bool deriv, bool marg, const int *edge_mask
                 if (hipGetLastError() != hipSuccess) { h->err = "plk_place_ll: kernel launch failed"; return PLK_E_DEVICE; }
                 const long g0 = (long)gi * PLACE_MAX_ROWS;
                 if ((rc = place_group_out(h, pl, g0, (int)std::min<long>(PLACE_MAX_ROWS, pl->total() - g0), n, s0, p))) return rc;
+            }
+            continue;
+        }
+        if (sp) {
+            /* the down pass once per chunk; per prune edge the path plane and F' once, then one pass per PLACE_MAX_ROWS moves */
+            for (size_t gi = 0; gi < sgg.pass.size(); gi++) {
+                SprOut so = sgg.out(*sp, pk, gi);
+                so.QPT = h->d_plstream; so.QPN = h->d_plstream + qstrm; so.plane = p; so.LP = p + (size_t)sgg.rows * n;
+                dispatch_K(K, [&](auto Kc) { launch_spr<decltype(Kc)::value>(h, a, so, grid, gi == 0); });
+                if (hipGetLastError() != hipSuccess) { h->err = "plk_spr_ll: kernel launch failed"; return PLK_E_DEVICE; }
+                if ((rc = spr_group_out(h, sp, sgg.pass[gi].g0, sgg.pass[gi].nrec, n, s0, p))) return rc;
             }
             continue;
         }
@@ -4395,6 +4525,107 @@ extern "C" int plk_place_ll(plk_engine *h, int n_queries, const uint8_t *q_codes
     if (sums_out)
         for (int qi = 0; qi < n_queries; qi++)
             for (int ei = 0; ei < n_edges; ei++) put_dd(sums_out + 2 * ((size_t)qi * n_edges + ei), q.acc[(size_t)ei * n_queries + qi]);
+    return PLK_OK;
+}
+
+/*
+ * Log likelihood of subtree prune-and-regraft moves of the current tree (plk_spr.h): one down pass per site chunk, per
+ * prune edge one pass that stores the vectors of the pruned tree and one pass per PLACE_MAX_ROWS moves.  Every pair is
+ * checked, the rates of the two parts of every target edge by the check of the model's rates, before anything is queued.
+ */
+extern "C" int plk_spr_ll(plk_engine *h, int n_moves, const int *moves, double split, double *site_out, double *sums_out)
+{
+    if (!plk_live(h)) return PLK_E_ARG;
+    if (h->k == 0 || h->pat_mode == 0) { h->err = "plk_spr_ll: tree, model and patterns must be set"; return PLK_E_ARG; }
+    if (n_moves < 0) { h->err = "plk_spr_ll: negative number of moves"; return PLK_E_ARG; }
+    if (!(split >= 0.0 && split <= 1.0)) { h->err = "plk_spr_ll: split must be a number in [0, 1]"; return PLK_E_ARG; }
+    const int N = h->N, E = h->E, k = h->k;
+    const int *ip = h->indptr.data(), *ix = h->indices.data();
+    SprReq q;
+    q.epar = edge_parents(N, ip); q.in = in_edges(N, ip, ix);
+    q.pos.assign((size_t)N, 0); q.size.assign((size_t)N, 1); q.depth.assign((size_t)N, 0); q.par.assign((size_t)N, -1);
+    for (int u = 0; u < N; u++) q.pos[h->preorder[u]] = u;
+    for (int u = 1; u < N; u++) { const int y = h->preorder[u]; q.par[y] = q.epar[q.in[y]]; q.depth[y] = q.depth[q.par[y]] + 1; q.max_depth = std::max(q.max_depth, q.depth[y]); }
+    for (int u = N - 1; u > 0; u--) { const int y = h->preorder[u]; q.size[q.par[y]] += q.size[y]; }
+    {
+        /* depth-first positions: the subtree of a node is an interval of them, which the engine's order does not promise */
+        q.dpos.assign((size_t)N, 0);
+        std::vector<int> stack(1, h->preorder[0]);
+        int seen = 0;
+        while (!stack.empty()) {
+            const int y = stack.back();
+            stack.pop_back();
+            q.dpos[y] = seen++;
+            for (int idx = ip[y + 1] - 1; idx >= ip[y]; idx--) stack.push_back(ix[idx]);
+        }
+    }
+    std::vector<int> canon;
+    if (!moves) {
+        canon.resize((size_t)2 * std::max(1, plk_spr_moves(N, ip, ix, nullptr)));
+        const int count = plk_spr_moves(N, ip, ix, canon.data());
+        if (n_moves != count) {
+            h->err = "plk_spr_ll: the canonical list has " + std::to_string(count) + " moves, the call asks for " + std::to_string(n_moves);
+            return PLK_E_ARG;
+        }
+        moves = canon.data();
+    } else {
+        for (int i = 0; i < n_moves; i++) {
+            const int p = moves[2 * i], e = moves[2 * i + 1];
+            const char *bad = nullptr;
+            if (p < 0 || p >= E || e < 0 || e >= E) bad = "edge index out of range";
+            else if (p == e) bad = "the target is the pruned edge";
+            else {
+                const int x = ix[p], u = q.epar[e];
+                if (q.dpos[u] >= q.dpos[x] && q.dpos[u] < q.dpos[x] + q.size[x]) bad = "the target lies below the pruned edge";
+            }
+            if (bad) {
+                h->err = "plk_spr_ll: pair " + std::to_string(i) + " (" + std::to_string(p) + ", " + std::to_string(e) + ") is no move: " + bad;
+                return PLK_E_ARG;
+            }
+        }
+    }
+    /* the distinct target edges in the order of their first appearance, and the rates of the call */
+    {
+        std::vector<int> slot_of((size_t)std::max(E, 1), -1), first_of;
+        const double lower = 1.0 - split;
+        for (int i = 0; i < n_moves; i++) {
+            const int e = moves[2 * i + 1];
+            int &sl = slot_of[e];
+            if (sl < 0) {
+                sl = (int)q.rates.size() / 2;
+                q.rates.push_back(split * h->edge_rates[e]);
+                q.rates.push_back(lower * h->edge_rates[e]);
+                first_of.push_back(e);
+            }
+            q.slot.push_back(sl);
+        }
+        /* both parts of an edge are at most the rate the model's check accepted for it; they are checked all the same, as
+         * in plk_place_ll */
+        const size_t kk = (size_t)k * k;
+        for (size_t j = 0; j < q.rates.size(); j++)
+            if (plk_k1_check_values(k, h->C, 1, h->Qn.data(), h->Qn.data() + kk, &q.rates[j], h->cat_rates.data(), h->cat_prior.data(),
+                                    h->root_mode, h->root_w.data(), nullptr, 0)) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "the %s part of target edge %d (rate %g)", j % 2 ? "lower" : "upper", first_of[j / 2], q.rates[j]);
+                h->err = std::string("plk_spr_ll: the transition matrix kernel refuses ") + msg +
+                         ": rate x length x |Qn| must be finite and at most 2^40" + K1_CSR_NOTE;
+                return PLK_E_ARG;
+            }
+    }
+    if (n_moves == 0 || (!site_out && !sums_out)) return PLK_OK;      /* nothing asked for: nothing runs */
+    HIPCHK(h, hipSetDevice(h->device));
+    QueryTimer qt(h);
+    q.n = n_moves; q.moves = moves; q.site_out = site_out; q.want_sums = sums_out != nullptr;
+    q.order.resize((size_t)n_moves);
+    for (int i = 0; i < n_moves; i++) q.order[i] = i;
+    std::stable_sort(q.order.begin(), q.order.end(), [&](int x, int y) { return moves[2 * x] < moves[2 * y]; });
+    q.acc.assign((size_t)n_moves, 0.0L);
+    const int rc = run_updown(h, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, nullptr, nullptr, nullptr, &q);
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (rc) return rc;
+    if (e != hipSuccess) { h->err = std::string("plk_spr_ll: ") + hipGetErrorString(e); return PLK_E_DEVICE; }
+    if (sums_out)
+        for (int t = 0; t < n_moves; t++) put_dd(sums_out + 2 * (size_t)q.order[t], q.acc[t]);
     return PLK_OK;
 }
 

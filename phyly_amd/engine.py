@@ -23,6 +23,7 @@ INFO_NNI_KERNEL = 22
 INFO_LL_TRIPLE = 23
 INFO_LL_QUAD = 24
 INFO_PLACE_KERNEL = 25
+INFO_SPR_KERNEL = 27
 INFO_LL_BARRIER = 26
 OPT_FORCE_GENERIC, OPT_SITE_CHUNK, OPT_FUSED_NS, OPT_FUSED_ASM, OPT_MFMA, OPT_UP_NODES, OPT_PAIR_TABLES, OPT_VEC_REG_STACK, OPT_MFMA_NS2 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 OPT_STREAM_GRID = 9
@@ -60,6 +61,19 @@ def nni_swaps(indptr, indices):
     pairs = np.zeros((count, 2), dtype=np.int32)
     if count:
         lib.plk_nni_swaps(N, _ptr(indptr), _ptr(indices), _ptr(pairs))
+    return pairs
+
+
+def spr_moves(indptr, indices):
+    """plk_spr_moves: the canonical list of subtree prune-and-regraft moves of a tree in CSR form, [count][2] CSR edge
+    pairs (prune, target) ordered by prune, then by target (include/plk.h:plk_spr_ll); no engine, no GPU"""
+    lib = load_library()
+    indptr, indices = _i32(indptr), _i32(indices)
+    N = len(indptr) - 1
+    count = int(lib.plk_spr_moves(N, _ptr(indptr), _ptr(indices), None))
+    pairs = np.zeros((count, 2), dtype=np.int32)
+    if count:
+        lib.plk_spr_moves(N, _ptr(indptr), _ptr(indices), _ptr(pairs))
     return pairs
 
 
@@ -111,6 +125,8 @@ def load_library():
     lib.plk_nni_swaps.argtypes = [ci, vp, vp, vp]
     lib.plk_nni_ll.argtypes = [vp, ci, vp, vp, vp]
     lib.plk_place_ll.argtypes = [vp, ci, vp, vp, ci, vp, ctypes.c_double, ctypes.c_double, vp, vp]
+    lib.plk_spr_moves.argtypes = [ci, vp, vp, vp]
+    lib.plk_spr_ll.argtypes = [vp, ci, vp, ctypes.c_double, vp, vp]
     lib.plk_get_transition_matrices.argtypes = [vp, vp]
     lib.plk_get_info.argtypes = [vp, ci, ctypes.POINTER(cl)]
     lib.plk_set_option.argtypes = [vp, ci, cl]
@@ -385,6 +401,24 @@ class Engine:
         sums = np.zeros((nq, ne, 2)) if want_sums else None
         self._check(self._lib.plk_place_ll(self._h, nq, _ptr(qc), _ptr(qd), ne, _ptr(ed), float(split), float(pendant_rate),
                                            _ptr(out), _ptr(sums)))
+        return out, sums
+
+    def spr_ll(self, moves=None, split=0.5, per_site=True, want_sums=True):
+        """log likelihood of subtree prune-and-regraft moves of the tree (include/plk.h:plk_spr_ll); moves: [n][2] CSR
+        edge pairs (prune, target), None = the canonical list (spr_moves) -> (ll' [n][S] or None, sums [n][2] or None)"""
+        if moves is None:
+            if self._csr is None:
+                err = EngineError("plk_spr_ll: tree, model and patterns must be set")
+                err.code = E_ARG
+                raise err
+            n = len(spr_moves(*self._csr))
+            mv = None
+        else:
+            mv = _i32(moves).reshape(-1, 2)
+            n = mv.shape[0]
+        out = np.zeros((n, self.S)) if per_site else None
+        sums = np.zeros((n, 2)) if want_sums else None
+        self._check(self._lib.plk_spr_ll(self._h, n, _ptr(mv), float(split), _ptr(out), _ptr(sums)))
         return out, sums
 
     def transition_matrices(self):
